@@ -7,10 +7,16 @@ exchange.  Every rank owns an independent problem (different seed: weak scaling,
 only collective is an all-gather of one 16-byte record per rank over RCCL.
 
 Prints ONE JSON line on rank 0.  value = candidates scored per second over the whole job
-(= n_gpus * m * steps / max-over-ranks time); the fit-only rate (posterior updates/s) is timed in a second
-loop and reported beside it.  Inputs are resident in HBM before the timed region starts.
+(= n_gpus * m * steps / max-over-ranks time), ms_per_step = the time of one timed step.  Inputs are resident in HBM
+before the timed region starts.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run sets up, warms up, times the K steps and prints the line (with the sweep product's and the kernel
+build's rooflines, whose hipEvents are recorded inside the timed steps).  --full adds every measurement that takes
+runs of its own: the fit-only rate (posterior updates/s) and the update's per-kernel split, the exchange latency,
+the CPU baseline and the side configurations (--no-cpu-baseline / --no-other-configs leave those two out of it).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
        N>1 either under a launcher (python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ...
        bench.py --gpus N: WORLD_SIZE must equal N) or bare: `python bench.py --gpus N` then starts the N ranks itself
        (launch_ranks) before anything in this process touches the GPU, so n_gpus = N by construction.
@@ -50,13 +56,21 @@ def parse(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--problems-per-gpu", type=int, default=1,
                     help="independent problems (restarts/seeds) per GPU per step; 4 at 8 GPUs = BASELINE configs[3]")
-    ap.add_argument("--cpu-sample", type=int, default=8192, help="candidates in the CPU-baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beside the headline figure: fit-only loop and its per-kernel "
+                         "split, exchange latency, CPU baseline, side configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy")
+    ap.add_argument("--cpu-sample", type=int, default=8192, help="candidates in the CPU-baseline sample (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the side measurements of BASELINE configs[2] and configs[4] (N=1 only)")
+                    help="with --full: skip the side measurements of BASELINE configs[2] and configs[4] (N=1 only)")
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="test hook: every rank reports its rank variables and exits before any GPU call")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def launch_ranks(gpus: int, argv) -> int:
@@ -447,6 +461,40 @@ def other_configs(eng, dev, seed):
     return out
 
 
+DUMP_SAMPLE = 1 << 20    # entries sampled from each n x n factor (8 MiB as fp64)
+DUMP_BUDGET = 48000000  # bytes of factor samples over all ranks, well inside 64 MB for the whole directory
+
+
+def dump_sample_size(problems):
+    """Entries sampled from each of the 2 factors of each of the job's `problems` problems."""
+    return max(1, min(DUMP_SAMPLE, DUMP_BUDGET // (16 * max(problems, 1))))
+
+
+def dump_outputs(path, bv, bi, states, probs, write_best, problems=None):
+    """What the last timed step handed to its caller, as <path>/<name>.npy in fp64: the selected candidate
+    (best_value, best_index; rank 0's, i.e. the job's) and, per problem (u<unit>: its global index), the posterior
+    caches a caller keeps for its next queries: alpha (n x nrhs), and a fixed seeded sample of the entries of the
+    Cholesky factor L (lower triangle) and of W = L^-T (upper triangle) inside the n x n problem (the whole factors
+    are 128 MiB each at n = 4096).  `problems`: the problems of the whole job (all ranks write into the same
+    directory; default: this call's).  The sample positions depend on n and `problems` alone, so two builds write the
+    same entries."""
+    os.makedirs(path, exist_ok=True)
+    if write_best:
+        np.save(os.path.join(path, "best_value.npy"), bv.detach().cpu().numpy().astype(np.float64).reshape(-1))
+        np.save(os.path.join(path, "best_index.npy"), bi.detach().cpu().numpy().astype(np.float64).reshape(-1))
+    k = dump_sample_size(len(states) if problems is None else problems)
+    for st, pr in zip(states, probs):
+        unit, n = pr[4], st.n
+        np.save(os.path.join(path, f"alpha_u{unit}.npy"), st.alpha[:n].detach().cpu().numpy().astype(np.float64))
+        rng = np.random.default_rng(20240607 + n)
+        a, b = rng.integers(0, n, size=k), rng.integers(0, n, size=k)
+        lo = torch.as_tensor(np.minimum(a, b), device=st.L.device)
+        hi = torch.as_tensor(np.maximum(a, b), device=st.L.device)
+        np.save(os.path.join(path, f"chol_sample_u{unit}.npy"), st.L[hi, lo].cpu().numpy().astype(np.float64))
+        if st.W_ready:
+            np.save(os.path.join(path, f"winv_sample_u{unit}.npy"), st.W[lo, hi].cpu().numpy().astype(np.float64))
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     args = parse(argv)
@@ -481,8 +529,6 @@ def main(argv=None):
     Xb = torch.stack([p[0] for p in probs])
     yb = torch.stack([p[1] for p in probs])
     states = eng.fit_batched(Xb, yb, params) if P > 1 else [eng.fit(Xb[0], yb[0], params)]  # allocation outside
-    X_np, y_np = synthetic.problem(args.n, args.d, args.seed + 1000 * rank * P)  # cpu-baseline inputs
-    Xs_np = synthetic.sobol(args.m, args.d, args.seed + 1000 * rank * P + 1)
 
     def fit_all():
         if P > 1:
@@ -495,8 +541,10 @@ def main(argv=None):
     loc_v = torch.empty((P,), dtype=torch.float64, device=dev)
     loc_i = torch.empty((P,), dtype=torch.int64, device=dev)
 
+    last = {}  # the states of the latest step, for --dump-outputs
+
     def step():
-        sts = fit_all()
+        sts = last["states"] = fit_all()
         if P > 1:
             eng.inverse_batched(sts)  # W = L^-T of every problem for its sweep, in the same launches
         for q, (Xq, yq, Xsq, bfq, unit) in enumerate(probs):
@@ -523,27 +571,32 @@ def main(argv=None):
     eng.timing_disable()
     if any(st.pivot_failure() >= 0 for st in states):
         raise RuntimeError("Cholesky failed inside the benchmark")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, bv, bi, last["states"], probs, write_best=rank == 0, problems=world * P)
 
-    # fit-only loop: posterior updates per second (all P problems of a GPU per fit call)
+    # everything below the timed steps that takes runs of its own is measured with --full only
     fit_reps = max(args.steps, 10)
-    barrier(dist)
-    t2 = time.perf_counter()
-    for _ in range(fit_reps):
-        fit_all()
-    barrier(dist)
-    fit_elapsed = time.perf_counter() - t2
-    # per-kernel split of the update (hipEvents around each family, a separate loop so the timed one is event-free)
-    eng.timing_reset()
-    eng.timing_enable(["gram", "potrf", "alpha"])
-    for _ in range(fit_reps):
-        fit_all()
-    part = {k: eng.timing_query(k) for k in ("gram", "potrf", "alpha")}
-    eng.timing_disable()
+    fit_elapsed, part = -1.0, None
+    if args.full:
+        # fit-only loop: posterior updates per second (all P problems of a GPU per fit call)
+        barrier(dist)
+        t2 = time.perf_counter()
+        for _ in range(fit_reps):
+            fit_all()
+        barrier(dist)
+        fit_elapsed = time.perf_counter() - t2
+        # per-kernel split of the update (hipEvents around each family, a separate loop so the timed one is event-free)
+        eng.timing_reset()
+        eng.timing_enable(["gram", "potrf", "alpha"])
+        for _ in range(fit_reps):
+            fit_all()
+        part = {k: eng.timing_query(k) for k in ("gram", "potrf", "alpha")}
+        eng.timing_disable()
 
     # latency of the cross-GPU exchange alone (report it separately; xGMI bandwidth is irrelevant for a
     # 16-byte record): back-to-back gpx_allreduce_argmax calls on the step's records, outside the timed step loop
     xch_us = None
-    if exchange is not None:
+    if exchange is not None and args.full:
         try:
             xr = 50
             barrier(dist)
@@ -576,15 +629,6 @@ def main(argv=None):
         kstar_bytes = 8.0 * (npad * kc + (n + kc) * args.d)
         kstar_avg = kstar_ms / max(kstar_launches, 1)
         kstar_gbs = kstar_bytes / (kstar_avg * 1e-3) / 1e9
-        gram_bytes = P * 8.0 * (npad * (npad + 1) / 2 + n * args.d)
-        gram_avg = part["gram"][0] / max(part["gram"][1], 1)
-        gram_gbs = gram_bytes / (gram_avg * 1e-3) / 1e9
-        cpu = None
-        if world == 1 and not args.no_cpu_baseline:
-            cpu = cpu_baseline(X_np, y_np, Xs_np, args.kernel, args.acq, ls, args.cpu_sample)
-        extra = None
-        if world == 1 and not args.no_other_configs:
-            extra = other_configs(eng, dev, args.seed)
         traffic, traffic_src = pmc_traffic_record()
         out = {
             "metric": METRIC,
@@ -608,17 +652,22 @@ def main(argv=None):
                 "parallelism": f"{world * P} independent problems ({P} per GPU), RCCL 16-byte argmax all-gather",
                 "problems_per_gpu": P,
             },
-            "updates_per_s": world * P * fit_reps / fit_elapsed,
-            "fit_ms": 1e3 * fit_elapsed / fit_reps,
-            "update_breakdown_ms": {"gram": part["gram"][0] / fit_reps, "potrf": part["potrf"][0] / fit_reps,
-                                    "alpha_potrs": part["alpha"][0] / fit_reps},
-            # posterior update (Gram + Cholesky + alpha by triangular solves; the L^-T a sweep needs is built by the
-            # sweep) against the fp64 MFMA roofline at SURVEY §8d's n^3/3 flops: a latency-bound chain of n/64
-            # dependent panel launches, far from the bound
-            "updates_roofline": {"flops_per_update": n ** 3 / 3.0,
-                                 "achieved": (n ** 3 / 3.0) * P / (fit_elapsed / fit_reps) / 1e12,
-                                 "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
-                                 "frac": (n ** 3 / 3.0) * P / (fit_elapsed / fit_reps) / 1e12 / FP64_PEAK_TFLOPS},
+        }
+        if args.full:
+            out.update({
+                "updates_per_s": world * P * fit_reps / fit_elapsed,
+                "fit_ms": 1e3 * fit_elapsed / fit_reps,
+                "update_breakdown_ms": {"gram": part["gram"][0] / fit_reps, "potrf": part["potrf"][0] / fit_reps,
+                                        "alpha_potrs": part["alpha"][0] / fit_reps},
+                # posterior update (Gram + Cholesky + alpha by triangular solves; the L^-T a sweep needs is built by the
+                # sweep) against the fp64 MFMA roofline at SURVEY §8d's n^3/3 flops: a latency-bound chain of n/64
+                # dependent panel launches, far from the bound
+                "updates_roofline": {"flops_per_update": n ** 3 / 3.0,
+                                     "achieved": (n ** 3 / 3.0) * P / (fit_elapsed / fit_reps) / 1e12,
+                                     "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                     "frac": (n ** 3 / 3.0) * P / (fit_elapsed / fit_reps) / 1e12 / FP64_PEAK_TFLOPS},
+            })
+        out.update({
             "best": {"value": float(bv.item()), "index": int(bi.item())},
             "roofline": {
                 "kernel": "trmm_sumsq_kernel (V = L^-1 K*, fp64 MFMA 16x16x4)",
@@ -639,18 +688,33 @@ def main(argv=None):
                                       "achieved": kstar_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                       "frac": kstar_gbs / HBM_PEAK_GBS, "bytes_per_launch": kstar_bytes,
                                       "avg_launch_ms": kstar_avg, "launches": kstar_launches},
-            # the training-set kernel build (gram_kernel) against HBM, as the north star asks: its algorithmic traffic
-            # is the write of the lower triangle of the padded K, 8 npad (npad + 1) / 2 bytes (+ X read once)
-            "gram_roofline": {"kernel": "gram_kernel (K(X, X) + noise I, lower triangle)", "bound": "hbm",
-                              "achieved": gram_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                              "frac": gram_gbs / HBM_PEAK_GBS, "bytes_per_launch": gram_bytes,
-                              "avg_launch_ms": gram_avg, "launches": part["gram"][1]},
-            "cpu_baseline": cpu,
-            "exchange": {"collective": "RCCL all-gather of one 16-byte (value, index) record per rank + combine "
-                                       "kernel (gpx_allreduce_argmax), max over ranks", "latency_us": xch_us}
-            if world > 1 else None,
-            "other_configs": extra,
-        }
+        })
+        if args.full:
+            gram_bytes = P * 8.0 * (npad * (npad + 1) / 2 + n * args.d)
+            gram_avg = part["gram"][0] / max(part["gram"][1], 1)
+            gram_gbs = gram_bytes / (gram_avg * 1e-3) / 1e9
+            cpu = None
+            if world == 1 and not args.no_cpu_baseline:
+                X_np, y_np = synthetic.problem(n, args.d, args.seed)  # rank 0's first problem
+                Xs_np = synthetic.sobol(m, args.d, args.seed + 1)
+                cpu = cpu_baseline(X_np, y_np, Xs_np, args.kernel, args.acq, ls, args.cpu_sample)
+            extra = None
+            if world == 1 and not args.no_other_configs:
+                extra = other_configs(eng, dev, args.seed)
+            out.update({
+                # the training-set kernel build (gram_kernel) against HBM, as the north star asks: its algorithmic
+                # traffic is the write of the lower triangle of the padded K, 8 npad (npad + 1) / 2 bytes (+ X read
+                # once)
+                "gram_roofline": {"kernel": "gram_kernel (K(X, X) + noise I, lower triangle)", "bound": "hbm",
+                                  "achieved": gram_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                  "frac": gram_gbs / HBM_PEAK_GBS, "bytes_per_launch": gram_bytes,
+                                  "avg_launch_ms": gram_avg, "launches": part["gram"][1]},
+                "cpu_baseline": cpu,
+                "exchange": {"collective": "RCCL all-gather of one 16-byte (value, index) record per rank + combine "
+                                           "kernel (gpx_allreduce_argmax), max over ranks", "latency_us": xch_us}
+                if world > 1 else None,
+                "other_configs": extra,
+            })
         print(json.dumps(out))
     if exchange is not None:
         exchange.close()

@@ -4,7 +4,7 @@
 #  2. SQ pass over the sweep product (MFMA busy per SIMD, wave-cycle split) and the Cholesky's MFMA-busy per launch;
 #  3. per-launch kernel trace of the n = 4096 update, and the per-phase timeline of its launches (tools/potrf_steps_probe,
 #     built in-tree beforehand: launch gap, pre-update, the four 16-pivot blocks, factor tail, store);
-#  4. the -m gpu suite, smoke, bench (N=1), bench --problems-per-gpu 4;
+#  4. the -m gpu suite, smoke, bench --full (N=1), bench --full --problems-per-gpu 4;
 #  5. rocprofv3 --kernel-trace --stats of the bench.
 # A failing test (pytest rc 1) does not stop the measurements; a crash, abort or time limit does.
 set -o pipefail
@@ -29,8 +29,8 @@ rc=$?
 tail -3 $O/gpu_tests.log
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "gpu tests ended with $rc"; exit $rc; fi
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 &&
-timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err &&
-timeout -k 10 300 python bench.py --problems-per-gpu 4 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_p4.json 2> $O/bench_p4.err &&
+timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err &&
+timeout -k 10 300 python bench.py --full --problems-per-gpu 4 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_p4.json 2> $O/bench_p4.err &&
 cd /tmp &&
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o bench --output-format csv -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-other-configs > $O/prof_bench.json 2> $O/prof_bench.err || exit $?
 echo "EVIDENCE DONE rc=$rc"
