@@ -30,7 +30,7 @@ GPX_INFO_TIMEOUT = -(2 ** 31)  # device info word of a factorisation / solve who
 
 # per-handle options (include/gpx.h GPX_OPT_*; slot 0 is GPX_OPT_RESERVED_0, the removed potrf_schedule)
 OPTIONS = {"spin_limit": 1, "sweep_fused": 2, "gram_split": 3, "potrf_lazy": 4, "potrf_mode": 5, "potrf_switch": 6,
-           "potrf_split": 7}
+           "potrf_split": 7, "sweep_prune": 8}
 GPX_OPT_RESERVED = (0,)
 GPX_OPT_COUNT = len(OPTIONS) + len(GPX_OPT_RESERVED)
 
@@ -168,6 +168,7 @@ _PROTOS = {
     "gpx_acquire_argmax_f64": (c_int32, [_h, POINTER(KernelParamsC), c_int64, _p, c_int64, _p, c_int64, _p, _p,
                                          c_int64, c_int64, POINTER(AcqParamsC), c_int64, _p, _p, _p, _p,
                                          c_size_t]),
+    "gpx_sweep_stats": (c_int32, [_h, POINTER(c_int64)]),
     "gpx_sweep_multi_workspace_size": (c_int32, [c_int64, c_int64, POINTER(c_size_t)]),
     "gpx_acquire_argmax_multi_f64": (c_int32, [_h, POINTER(KernelParamsC), c_int64, c_int64, _p, c_int64,
                                                POINTER(c_void_p), POINTER(c_int64), POINTER(c_void_p),

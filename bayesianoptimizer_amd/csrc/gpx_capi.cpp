@@ -204,6 +204,10 @@ static gpx_status set_option(Context* c, int32_t option, int64_t v) {
       if (v != -1 && v != 1 && v != 3) return fail(c, GPX_INVALID_ARG, "potrf_split must be -1, 1 or 3");
       c->potrf_split = (int)v;
       return GPX_OK;
+    case GPX_OPT_SWEEP_PRUNE:
+      if (v < 0 || v > 2) return fail(c, GPX_INVALID_ARG, "sweep_prune must be 0, 1 or 2");
+      c->sweep_prune = (int)v;
+      return GPX_OK;
     default:
       return fail(c, GPX_INVALID_ARG, "unknown option " + std::to_string(option));
   }
@@ -212,7 +216,7 @@ static gpx_status set_option(Context* c, int32_t option, int64_t v) {
 static int option_by_name(const std::string& name) {
   // index = GPX_OPT_* number; slot 0 is reserved (the removed potrf_schedule) and has no name
   static const char* names[GPX_OPT_COUNT] = {"", "spin_limit", "sweep_fused", "gram_split", "potrf_lazy", "potrf_mode",
-                                               "potrf_switch", "potrf_split"};
+                                               "potrf_switch", "potrf_split", "sweep_prune"};
   for (int i = 1; i < GPX_OPT_COUNT; ++i)
     if (name == names[i]) return i;
   return -1;
@@ -263,6 +267,7 @@ gpx_status gpx_get_option(gpx_handle h, int32_t option, int64_t* value_host) {
     case GPX_OPT_POTRF_MODE: *value_host = c->potrf_mode; return GPX_OK;
     case GPX_OPT_POTRF_SWITCH: *value_host = c->potrf_switch; return GPX_OK;
     case GPX_OPT_POTRF_SPLIT: *value_host = c->potrf_split; return GPX_OK;
+    case GPX_OPT_SWEEP_PRUNE: *value_host = c->sweep_prune; return GPX_OK;
     default: return fail(c, GPX_INVALID_ARG, "unknown option " + std::to_string(option));
   }
 }
@@ -947,18 +952,50 @@ gpx_status gpx_acquire_argmax_f64(gpx_handle h, const gpx_kernel_params* p, int6
   GPX_TRY(check_ld(c, ldxs, p->d, "Xs", false));
   gpx::SweepBuffers b;
   GPX_TRY(carve_sweep(c, npad, 1, m, ws, ws_bytes, &b));
+  // scores_out wants every score: the full sweep
+  const bool prune = !scores_out && gpx::sweep_prune_ok(c, *p, (int)npad);
+  gpx::PruneState ps;
+  if (prune) gpx::sweep_prune_carve(b.rec_idx + (m + 255) / 256 + 1, npad, b.chunk, &ps);
   GPX_USE_DEVICE(c);
+  const bool fused = gpx::sweep_fused_ok(c, *p, (int)npad, 1);
+  c->sweep_stats[0] = m;
+  c->sweep_stats[1] = prune ? 0 : m;
+  c->sweep_stats[2] = c->sweep_stats[3] = 0;
+  c->sweep_stats_dev = prune ? ps.stats : nullptr;
   int64_t rec = 0;
   for (int64_t s = 0; s < m; s += b.chunk) {
     const int64_t mc = (m - s) < b.chunk ? (m - s) : b.chunk;
+    if (!fused) c->sweep_stats[3] += (mc + 127) / 128 * (npad / 128);
     GPX_TRY(hip_check(c,
-                      gpx::launch_sweep_chunk(c, *p, (int)n, (int)npad, X, ldx, W, ldw, alpha, 1, Xs + s * ldxs, ldxs,
-                                              mc, b, 1, a, nullptr, nullptr, nullptr, 0, nullptr,
-                                              scores_out ? scores_out + s : nullptr, rec, index_offset + s),
+                      prune ? gpx::launch_sweep_chunk_pruned(c, *p, (int)n, (int)npad, X, ldx, W, ldw, alpha,
+                                                             Xs + s * ldxs, ldxs, mc, b, ps, a, rec, index_offset + s,
+                                                             s == 0, c->sweep_stats)
+                            : gpx::launch_sweep_chunk(c, *p, (int)n, (int)npad, X, ldx, W, ldw, alpha, 1,
+                                                      Xs + s * ldxs, ldxs, mc, b, 1, a, nullptr, nullptr, nullptr, 0,
+                                                      nullptr, scores_out ? scores_out + s : nullptr, rec,
+                                                      index_offset + s),
                       "acquire"));
     rec += (mc + 255) / 256;
   }
+  if (!prune) c->sweep_stats[2] = c->sweep_stats[3];
   return hip_check(c, gpx::launch_argmax_final(c, b.rec_val, b.rec_idx, rec, best_val, best_idx), "argmax");
+}
+
+gpx_status gpx_sweep_stats(gpx_handle h, int64_t* out) {
+  Context* c = reinterpret_cast<Context*>(h);
+  if (!c) return GPX_INVALID_ARG;
+  GPX_NONNULL(c, out);
+  for (int i = 0; i < 4; ++i) out[i] = c->sweep_stats[i];
+  if (c->sweep_stats_dev) {
+    GPX_USE_DEVICE(c);
+    int64_t dev[2];
+    GPX_TRY(hip_check(c, hipMemcpyAsync(dev, c->sweep_stats_dev, sizeof(dev), hipMemcpyDeviceToHost, c->stream),
+                      "sweep_stats"));
+    GPX_TRY(hip_check(c, hipStreamSynchronize(c->stream), "sweep_stats"));
+    out[1] += dev[0];
+    out[2] += dev[1];
+  }
+  return GPX_OK;
 }
 
 gpx_status gpx_sweep_multi_workspace_size(int64_t n, int64_t m, size_t* bytes) {

@@ -40,6 +40,11 @@ struct Context {
   int potrf_mode = -1;     // multi-launch panel mode, -1 by size
   int potrf_switch = -1;   // launch at which a single fit switches schedule (gpx_potrf.hip potrf_switch), -1 by size
   int potrf_split = -1;    // panel split policy (gpx_potrf.hip step_plan): -1 fits the slots, 1 never, 3 one per CU
+  int sweep_prune = 1;     // pruned acquisition sweep: 1 where it pays, 0 never, 2 at every padded n >= 384
+  // gpx_sweep_stats of the last acquire call: the host-known parts, plus the device counters of the pruned path
+  // ({candidates computed to the last row tile, product tiles executed}; they live in that call's workspace)
+  int64_t sweep_stats[4] = {0, 0, 0, 0};
+  const int64_t* sweep_stats_dev = nullptr;
 };
 
 // Scoped device switch of one C ABI call: makes the handle's device current and restores the caller's current device
@@ -154,6 +159,44 @@ hipError_t launch_sweep_chunk(Context* c, const gpx_kernel_params& p, int n, int
                               const gpx_acq_params* a, const double* y_mean, const double* y_scale,
                               double* mean_out, int64_t ldmean, double* var_out, double* scores_out,
                               int64_t rec_offset, int64_t index_offset, const MultiOutput* mo = nullptr);
+
+// ---- pruned acquisition sweep (gpx_sweep.hip) ----------------------------------------------
+// The product's row tiles run in stages [R_s, R_{s+1}); after each stage but the last, candidates whose score upper
+// bound (variance bound from the row tiles done so far) lies below the incumbent are dropped, and the surviving K*
+// columns are gathered into a compact buffer once they are at most half of the active ones.  All state is on the device.
+constexpr int PRUNE_MIN_NPAD = 384;     // below: the fused sweep, or one or two row tiles (nothing to stage)
+constexpr int PRUNE_DEFAULT_NPAD = 384; // sweep_prune = 1 prunes from this padded n on
+constexpr int PRUNE_SEED = 1024;        // leading candidates of a call scored in full: the first incumbent
+constexpr int PRUNE_MAX_STAGES = 8;
+struct PruneDesc {  // the active column set of one stage (written by the launch before it, read by its launches)
+  int buf;     // 0: the chunk's K*, 1 / 2: the compact buffers
+  int col0;    // first column in the buffer (buf 0 only: the columns after the seed block)
+  int ncols;   // active candidates (slots 0 .. ncols-1)
+  int ntiles;  // 128-column tiles covering them
+  int list;    // -1: slot s is chunk column col0 + s; 0 / 1: the index list mapping slots to chunk columns
+  int pad[3];
+};
+struct PruneState {  // device pointers into the sweep workspace
+  double* cbuf[2];   // compact K* buffers (npad rows)
+  int64_t ldc[2];    // C/2 and C/4 columns (rounded up to the tile)
+  int2* list[2];     // {chunk column (-1: padding), slot in the buffer the list was built from}; C entries each
+  PruneDesc* desc;   // one per stage
+  int* count;        // survivors after each stage
+  unsigned long long* tau;  // the incumbent, as an order-preserving key (atomic max)
+  int64_t* stats;    // {candidates computed to the last row tile, 128 x 128 product tiles executed}
+};
+size_t sweep_prune_bytes(int64_t npad, int64_t m);
+void sweep_prune_carve(void* base, int64_t npad, int64_t C, PruneState* ps);
+bool sweep_fused_ok(const Context* c, const gpx_kernel_params& p, int npad, int nrhs);
+// the pruned path applies: unfused sweep, padded n >= the option's threshold (the caller excludes scores_out != NULL)
+bool sweep_prune_ok(const Context* c, const gpx_kernel_params& p, int npad);
+// One chunk of gpx_acquire_argmax_f64 through the staged product; first: the call's first chunk (resets the incumbent
+// and the counters, scores the seed block in full).  host_stats[1], [2] gain the seed block's share.
+hipError_t launch_sweep_chunk_pruned(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X,
+                                     int64_t ldx, const double* W, int64_t ldw, const double* alpha, const double* Xs,
+                                     int64_t ldxs, int64_t m_chunk, const SweepBuffers& b, const PruneState& ps,
+                                     const gpx_acq_params* a, int64_t rec_offset, int64_t index_offset, bool first,
+                                     int64_t* host_stats);
 hipError_t launch_multi_score(Context* c, const MultiOutput& mo, const gpx_acq_params& a, int64_t m_chunk,
                               double* scores_out, double* rec_val, int64_t* rec_idx, int64_t index_offset);
 hipError_t launch_argmax_final(Context* c, const double* vals, const int64_t* idx, int64_t count, double* best_val,

@@ -14,6 +14,12 @@
 //                    GPyTorch/BoTorch variance floors, Standardize untransform, analytic acquisition, and a
 //                    256-candidate block argmax record (max value, then lowest index; NaN never wins).
 // launch_argmax_final reduces the records of the whole sweep in one workgroup.
+//
+// gpx_acquire_argmax_f64 without scores_out takes the PRUNED form of launch 2 (launch_sweep_chunk_pruned):
+// the row tiles run in stages (trmm_stage_kernel); after each stage finalize_kernel mode 4 bounds every active
+// candidate's score from the partials it has, drops those that cannot reach the best score computed in full so far,
+// and prune_compact_kernel gathers the surviving K* columns; finalize scores the survivors of the last stage.  The
+// (value, index) pair has the bits of the full sweep.
 #include "gpx_internal.h"
 #include "gpx_device.h"
 #include "gpx_trmm_asm.h"
@@ -74,6 +80,16 @@ __device__ __forceinline__ void argmax_merge(double& v, int64_t& i, double v2, i
     v = v2;
     i = i2;
   }
+}
+
+// The pruned sweep's incumbent as an unsigned key with the order of the doubles (NaN never stored), so that the best
+// exact score so far is one atomicMax whatever the order of the workgroups.
+__device__ __forceinline__ unsigned long long tau_key(double v) {
+  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double tau_value(unsigned long long k) {
+  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
 }
 
 template <int DMAX>
@@ -276,49 +292,92 @@ constexpr int TT = 128;  // trmm tile (rows of V x candidates)
 using TrmmTile = MfmaTile<TT, TT, 16, true, true>;  // its accumulator layout (row_of / col_of) and LDS size
 static_assert(TrmmTile::LDS_DOUBLES * 8 == trmm_asm::LDS_BYTES, "hand-placed tile uses MfmaTile's LDS image");
 
+// Workgroup b of a launch over `nrows` row tiles x `ncb` candidate tiles -> (l, cb), l = 0 the heaviest row tile.
+// Candidate tiles in groups of G = 64 (every row tile of a group, heaviest first, before the next group), and inside a
+// group XCD-aware: workgroups b, b+8, ... share an XCD (dispatch is round-robin; speed only, never correctness), so
+// XCD x gets the group's candidate tiles cb = x (mod 8) and walks them row tile by row tile.  Groups keep the K*
+// panels the resident workgroups read to a quarter of the chunk at n = 4096: 7.65 vs 8.03 ms per launch (tools/
+// trmm_asm_bench.hip A4 vs A2, profiles/r05_trmm_asm_groups.log; groups of 16 / 32 / 128: 8.17 / 7.91 / 7.82 ms).
+__device__ __forceinline__ void trmm_tile_order(int b, int nrows, int ncb, int& l, int& cb) {
+  constexpr int G = 64;
+  if ((ncb % G) == 0) {
+    const int g = b / (nrows * G), bb = b % (nrows * G);
+    const int x = bb & 7, q = bb >> 3;
+    l = q / (G / 8);
+    cb = g * G + 8 * (q % (G / 8)) + x;
+  } else if ((ncb & 7) == 0) {
+    const int x = b & 7, q = b >> 3, per = ncb >> 3;
+    l = q / per;
+    cb = 8 * (q % per) + x;
+  } else {
+    l = b / ncb;
+    cb = b % ncb;
+  }
+}
+
+// The buffers a stage of the pruned sweep can read its K* columns from, and the two index lists (PruneDesc).
+struct PruneBufs {
+  const double* kstar;
+  double* c1;
+  double* c2;
+  int64_t ld0, ld1, ld2;
+  int2* list0;
+  int2* list1;
+};
+// One stage of the pruned sweep (trmm_stage_kernel).
+struct PruneStage {
+  PruneBufs pb;
+  const PruneDesc* desc;  // the active columns, written by an earlier launch
+  int I0, nrows;          // the stage's row tiles I0 .. I0 + nrows - 1
+};
+
 // kfull = 0: W upper triangular (k < (I+1)*128); kfull = 1: W is a full npad x npad matrix (the SVGP's
 // W2 = L^{-T} S term, gpx_svgp.hip), k over all nI row tiles.
 // With W2 (the SVGP's second product, grid.y = 2): blockIdx.y = 0 runs W2 with kfull = 1 into ss2 (the heavier,
 // full-k tiles dispatched first), blockIdx.y = 1 the product given by (W, ss_part, kfull): both products of a chunk in
 // one launch share its K* and one launch tail (two launches before).
-__global__ void __launch_bounds__(WG) trmm_sumsq_kernel(const double* __restrict__ W, int64_t ldw,
-                                                        const double* __restrict__ kstar, int64_t C, int nI, int ncb,
-                                                        double* __restrict__ ss_part, int kfull,
-                                                        const double* __restrict__ W2 = nullptr,
-                                                        double* __restrict__ ss2 = nullptr) {
-  __shared__ __attribute__((aligned(16))) double smem[TrmmTile::LDS_DOUBLES];
+// STAGED (trmm_stage_kernel, a stage of the pruned sweep): row tiles st.I0 .. st.I0 + st.nrows - 1 of the columns active in
+// *st.desc.  The grid covers every candidate tile the chunk could still have; workgroups beyond the active tiles
+// return at once.  Same tile, same order (heaviest row tile first, XCD-aware) and, for a column, the same MFMA chain
+// whatever slot of whatever buffer it sits in; its sums go to ss_part at the column's place in the chunk, so the
+// partials of a candidate are the ones the plain product writes.
+template <bool STAGED>
+__device__ __forceinline__ void trmm_sumsq_body(const double* __restrict__ W, int64_t ldw,
+                                                const double* __restrict__ kstar, int64_t C, int nI, int ncb,
+                                                double* __restrict__ ss_part, int kfull,
+                                                const double* __restrict__ W2, double* __restrict__ ss2,
+                                                PruneStage st, double* smem) {
   if (W2 && blockIdx.y == 0) {
     W = W2;
     ss_part = ss2;
     kfull = 1;
   }
-  // Candidate tiles in groups of G = 64 (every row tile of a group, heaviest first, before the next group), and inside a
-  // group XCD-aware: workgroups b, b+8, ... share an XCD (dispatch is round-robin; speed only, never correctness), so
-  // XCD x gets the group's candidate tiles cb = x (mod 8) and walks them row tile by row tile.  Groups keep the K*
-  // panels the resident workgroups read to a quarter of the chunk at n = 4096: 7.65 vs 8.03 ms per launch (tools/
-  // trmm_asm_bench.hip A4 vs A2, profiles/r05_trmm_asm_groups.log; groups of 16 / 32 / 128: 8.17 / 7.91 / 7.82 ms).
-  const int b = blockIdx.x;
-  int I, cb;
-  constexpr int G = 64;
-  if ((ncb % G) == 0) {
-    const int g = b / (nI * G), bb = b % (nI * G);
-    const int x = bb & 7, l = bb >> 3;
-    I = nI - 1 - l / (G / 8);
-    cb = g * G + 8 * (l % (G / 8)) + x;
-  } else if ((ncb & 7) == 0) {
-    const int x = b & 7, l = b >> 3, per = ncb >> 3;
-    I = nI - 1 - l / per;
-    cb = 8 * (l % per) + x;
-  } else {
-    I = nI - 1 - b / ncb;
-    cb = b % ncb;
+  int I0 = 0, nrows = nI, col0 = 0;
+  int64_t ldb = C;
+  const int2* list = nullptr;
+  if constexpr (STAGED) {
+    // (the tile's buffer descriptors want base and pitch in scalar registers: make the uniformity explicit)
+    const int buf = __builtin_amdgcn_readfirstlane(st.desc->buf);
+    const int li = __builtin_amdgcn_readfirstlane(st.desc->list);
+    col0 = __builtin_amdgcn_readfirstlane(st.desc->col0);
+    ncb = __builtin_amdgcn_readfirstlane(st.desc->ntiles);
+    I0 = st.I0;
+    nrows = st.nrows;
+    if ((int)blockIdx.x >= ncb * nrows) return;
+    kstar = buf == 0 ? st.pb.kstar : buf == 1 ? st.pb.c1 : st.pb.c2;
+    ldb = buf == 0 ? st.pb.ld0 : buf == 1 ? st.pb.ld1 : st.pb.ld2;
+    list = li < 0 ? nullptr : li ? st.pb.list1 : st.pb.list0;
   }
-  const double* Ab = W + (int64_t)I * TT;            // A(m=i,k) = W[k][I*128 + i]
-  const double* Bb = kstar + (int64_t)cb * TT;       // B(k,n=c) = K*[k][cb*128 + c]
+  int l, cb;
+  trmm_tile_order(blockIdx.x, nrows, ncb, l, cb);
+  const int I = I0 + nrows - 1 - l;
+  const double* Ab = W + (int64_t)I * TT;               // A(m=i,k) = W[k][I*128 + i]
+  const double* Bb = kstar + col0 + (int64_t)cb * TT;   // B(k,n=c) = K*[k][col0 + cb*128 + c]
   // the k loop with a hand-placed instruction stream (gpx_trmm_asm.h; same MFMA sequence per accumulator as
-  // MfmaTile::run, so the same bits); for the triangular W, the waves of rows 0-63 skip the diagonal tile's zero half
-  trmm_asm::Tile tile;
-  tile.run(Ab, ldw, Bb, C, (kfull ? nI : I + 1) * (TT / 16), smem, !kfull);
+  // MfmaTile::run, so the same bits); for the triangular W every wave skips the zero 16 x 16 blocks of the diagonal
+  // 128-tile (trmm_asm::TileT::run_tri)
+  trmm_asm::TileTag<STAGED ? 1 : 0> tile;  // (a tag per kernel: gpx_trmm_asm.h TileT)
+  tile.run(Ab, ldw, Bb, ldb, (kfull ? nI : I + 1) * (TT / 16), smem, !kfull);
   // column sums of squares over this wave's rows, then over the lanes holding the same column
   double s[TrmmTile::WN];
 #pragma unroll
@@ -344,9 +403,29 @@ __global__ void __launch_bounds__(WG) trmm_sumsq_kernel(const double* __restrict
 #pragma unroll
     for (int j = 0; j < TrmmTile::WN; ++j) {
       const int col = TrmmTile::col_of(j);
-      ss_part[(int64_t)I * C + (int64_t)cb * TT + col] = s[j] + red[col];
+      if constexpr (STAGED) {
+        const int slot = cb * TT + col;
+        const int c = list ? list[slot].x : col0 + slot;  // -1: a padding column of the last compact tile
+        if (c >= 0) ss_part[(int64_t)I * C + c] = s[j] + red[col];
+      } else {
+        ss_part[(int64_t)I * C + (int64_t)cb * TT + col] = s[j] + red[col];
+      }
     }
   }
+}
+
+__global__ void __launch_bounds__(WG)
+trmm_sumsq_kernel(const double* __restrict__ W, int64_t ldw, const double* __restrict__ kstar, int64_t C, int nI,
+                  int ncb, double* __restrict__ ss_part, int kfull, const double* __restrict__ W2 = nullptr,
+                  double* __restrict__ ss2 = nullptr) {
+  __shared__ __attribute__((aligned(16))) double smem[TrmmTile::LDS_DOUBLES];
+  trmm_sumsq_body<false>(W, ldw, kstar, C, nI, ncb, ss_part, kfull, W2, ss2, PruneStage{}, smem);
+}
+__global__ void __launch_bounds__(WG)
+trmm_stage_kernel(const double* __restrict__ W, int64_t ldw, int64_t C, int nI, double* __restrict__ ss_part,
+                  PruneStage st) {
+  __shared__ __attribute__((aligned(16))) double smem[TrmmTile::LDS_DOUBLES];
+  trmm_sumsq_body<true>(W, ldw, nullptr, C, nI, 0, ss_part, 0, nullptr, nullptr, st, smem);
 }
 
 // ---- 1+2 fused, small n (npad <= 256) ----------------------------------------------------------
@@ -509,8 +588,23 @@ struct FinalizeArgs {
   double* acc_var;   // sum_t w_t^2 y_scale_t^2 max(k** - |v_t|^2, 1e-10)      (chunk-sized)
 };
 
+// The pruned sweep's view of a finalize launch (all nullptr: the plain sweep).  desc: thread t is slot t of the active
+// column set instead of chunk column t.  tau: mode 1 raises the incumbent to its block's best score.  Mode 4 appends
+// the survivors to the list that *desc does not use and counts them in *count.
+struct PruneSel {
+  const PruneDesc* desc;
+  int2* list0;
+  int2* list1;
+  int* count;
+  unsigned long long* tau;
+};
+constexpr double PRUNE_EPS = 1e-9;  // margin of the bound test over acq_score's rounding
+
 // mode 0: posterior (mean / variance out); 1: acquisition + 256-candidate block argmax; 2: one output of a multi-output
-// objective into the accumulators; 3: acquisition + block argmax of the accumulated objective (no partials read).
+// objective into the accumulators; 3: acquisition + block argmax of the accumulated objective (no partials read);
+// 4: bound and select of the pruned sweep: mode 1's score from the first nI row tiles' partials only, an upper bound of
+// the candidate's score (the variance can only shrink with further tiles, and every acquisition grows with it), and the
+// candidate survives unless the bound lies below the incumbent by more than the margin (a NaN bound survives).
 // Variance floors: GPyTorch's 1e-10 per output in the standardised space, BoTorch's 1e-12 on the scored variance
 // [upstream] (T = 1, w = 1: modes 2 + 3 give mode 1's value bit for bit).
 __global__ void __launch_bounds__(WG) finalize_kernel(FinalizeArgs fa, int mode, const double* __restrict__ Xs,
@@ -520,10 +614,19 @@ __global__ void __launch_bounds__(WG) finalize_kernel(FinalizeArgs fa, int mode,
                                                       double* __restrict__ mean_out, int64_t ldmean,
                                                       double* __restrict__ var_out, double* __restrict__ scores_out,
                                                       double* __restrict__ rec_val, int64_t* __restrict__ rec_idx,
-                                                      int64_t index_base) {
+                                                      int64_t index_base, PruneSel ps) {
   const gpx_kernel_params& p = fa.p;
-  const int64_t c = (int64_t)blockIdx.x * WG + threadIdx.x;
-  const bool valid = c < m_chunk;
+  const int64_t t = (int64_t)blockIdx.x * WG + threadIdx.x;
+  int64_t c = t;
+  bool valid = t < m_chunk;
+  int2* survivors = nullptr;
+  if (ps.desc) {
+    const PruneDesc d = *ps.desc;
+    if (mode == 4 && (int64_t)blockIdx.x * WG >= d.ncols) return;
+    valid = t < d.ncols;
+    c = !valid ? 0 : d.list < 0 ? d.col0 + t : (d.list ? ps.list1 : ps.list0)[t].x;
+    survivors = d.list == 0 ? ps.list1 : ps.list0;
+  }
   double score = -INFINITY;
   if (valid) {
     double mu, var;
@@ -565,9 +668,23 @@ __global__ void __launch_bounds__(WG) finalize_kernel(FinalizeArgs fa, int mode,
     }
     score = acq_score(fa.acq_kind, mu, var, fa.best_f, fa.beta);
     if (scores_out) scores_out[c] = score;
-    if (score != score) score = -INFINITY;
+    if (score != score && mode != 4) score = -INFINITY;
   }
   if (mode == 0 || mode == 2) return;
+  if (mode == 4) {
+    // survivors as a compact list: one ballot and one atomic add per wave; the slot order may vary from run to run,
+    // no result depends on it
+    const double tau = tau_value(*ps.tau);
+    const bool keep = valid && !(score + PRUNE_EPS * (fabs(score) + fabs(tau) + 1.0) < tau);
+    const unsigned long long mask = __ballot(keep);
+    if (mask == 0) return;
+    const int lane = threadIdx.x & 63;
+    int base = 0;
+    if (lane == 0) base = atomicAdd(ps.count, __popcll(mask));
+    base = __shfl(base, 0);
+    if (keep) survivors[base + __popcll(mask & ((1ull << lane) - 1))] = make_int2((int)c, (int)t);
+    return;
+  }
   // block argmax
   double bv = score;
   int64_t bi = valid ? index_base + c : INT64_MAX;
@@ -589,7 +706,75 @@ __global__ void __launch_bounds__(WG) finalize_kernel(FinalizeArgs fa, int mode,
     for (int q = 1; q < 4; ++q) argmax_merge(bv, bi, wv[q], wi[q]);
     rec_val[blockIdx.x] = bv;
     rec_idx[blockIdx.x] = bi;
+    if (ps.tau) atomicMax(ps.tau, tau_key(bv));
   }
+}
+
+// The pruned sweep's per-chunk reset (one thread): the first stage's column set (the chunk's columns from col0 on, in
+// place), zero survivor counts, and on the call's first chunk the incumbent (-inf) and the counters.
+__global__ void prune_init_kernel(PruneDesc* __restrict__ desc, int* __restrict__ count,
+                                  unsigned long long* __restrict__ tau, int64_t* __restrict__ stats, int col0,
+                                  int ncols, int rows0, int last, int first) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  PruneDesc d;
+  d.buf = 0;
+  d.col0 = col0;
+  d.ncols = ncols;
+  d.ntiles = (ncols + TT - 1) / TT;
+  d.list = -1;
+  d.pad[0] = d.pad[1] = d.pad[2] = 0;
+  desc[0] = d;
+  for (int s = 0; s < PRUNE_MAX_STAGES; ++s) count[s] = 0;
+  if (first) {
+    *tau = tau_key(-INFINITY);
+    stats[0] = stats[1] = 0;
+  }
+  stats[1] += (int64_t)d.ntiles * rows0;
+  if (last) stats[0] += ncols;
+}
+
+// After a stage's bound and select: the next stage's column set.  If the survivors are at most half of the active
+// columns, their K* columns are gathered into the other compact buffer (dense 128-column tiles, the last one padded
+// with zero columns whose list entry is -1), else the next stage keeps the buffer and the columns it has: the copy
+// traffic stays below the K* it replaces, and an unprunable chunk pays only the bound passes.  Every workgroup takes
+// the same decision from what earlier launches wrote; thread 0 of workgroup (0, 0) writes the next descriptor (read by
+// later launches only) and the counters.  Workgroup (x, y): slots 256 x .., rows rows_per_wg * y ...
+__global__ void __launch_bounds__(WG) prune_compact_kernel(PruneBufs pb, const PruneDesc* __restrict__ din,
+                                                           PruneDesc* __restrict__ dout,
+                                                           const int* __restrict__ count, int rows_per_wg,
+                                                           int next_rows, int last, int64_t* __restrict__ stats) {
+  const PruneDesc d = *din;
+  const int surv = *count;
+  const bool compact = 2 * (int64_t)surv <= d.ncols;
+  const int ntl = (surv + TT - 1) / TT;
+  const int out_list = d.list == 0 ? 1 : 0;
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+    PruneDesc o = d;
+    if (compact) {
+      o.buf = d.buf == 1 ? 2 : 1;
+      o.col0 = 0;
+      o.ncols = surv;
+      o.ntiles = ntl;
+      o.list = out_list;
+    }
+    *dout = o;
+    stats[1] += (int64_t)o.ntiles * next_rows;
+    if (last) stats[0] += o.ncols;
+  }
+  if (!compact) return;
+  const int slot = blockIdx.x * WG + threadIdx.x;
+  if (slot >= ntl * TT) return;
+  int2* list = out_list ? pb.list1 : pb.list0;
+  const double* src = d.buf == 0 ? pb.kstar : d.buf == 1 ? pb.c1 : pb.c2;
+  const int64_t lds = d.buf == 0 ? pb.ld0 : d.buf == 1 ? pb.ld1 : pb.ld2;
+  double* dst = d.buf == 1 ? pb.c2 : pb.c1;
+  const int64_t ldd = d.buf == 1 ? pb.ld2 : pb.ld1;
+  const bool real = slot < surv;
+  if (!real && blockIdx.y == 0) list[slot] = make_int2(-1, 0);
+  const int64_t sc = real ? d.col0 + list[slot].y : 0;
+  const int r0 = blockIdx.y * rows_per_wg;
+#pragma unroll 8
+  for (int r = r0; r < r0 + rows_per_wg; ++r) dst[(int64_t)r * ldd + slot] = real ? src[(int64_t)r * lds + sc] : 0.0;
 }
 
 // records e = 0 .. count-1 at vals[e * stride] / idx[e * stride] (stride 1: separate arrays; 2: packed 16-byte
@@ -650,8 +835,41 @@ size_t sweep_workspace_bytes(int64_t npad, int64_t nrhs, int64_t m) {
   b += (size_t)(npad / NB) * nrhs * C * 8;   // mu_part
   b += (size_t)(npad / TT) * C * 8;          // ss_part
   b += (size_t)nrec * 16;                    // records
+  if (nrhs == 1) b += sweep_prune_bytes(npad, m);
   return b + 256;
 }
+
+// The pruned sweep's part of the workspace, after the records: descriptors, counts, incumbent and counters (256 bytes
+// each), the two index lists, and the compact K* buffers of C/2 and C/4 columns (a compaction at least halves the
+// active columns, so they alternate: DESIGN §3).
+static int64_t prune_ld(int64_t C, int which) {
+  const int64_t cols = which == 0 ? C / 2 : C / 4;
+  return ((cols + TT - 1) / TT) * TT;
+}
+size_t sweep_prune_bytes(int64_t npad, int64_t m) {
+  if (npad < PRUNE_MIN_NPAD) return 0;
+  const int64_t C = sweep_chunk_size(npad, m);
+  static_assert(sizeof(PruneDesc) * PRUNE_MAX_STAGES <= 256 && sizeof(int) * PRUNE_MAX_STAGES <= 256, "header slots");
+  return 256 + 3 * 256 + 2 * (size_t)C * sizeof(int2) + (size_t)npad * (prune_ld(C, 0) + prune_ld(C, 1)) * 8;
+}
+void sweep_prune_carve(void* base, int64_t npad, int64_t C, PruneState* ps) {
+  char* q = reinterpret_cast<char*>(((uintptr_t)base + 255) & ~(uintptr_t)255);
+  ps->desc = reinterpret_cast<PruneDesc*>(q);
+  ps->count = reinterpret_cast<int*>(q + 256);
+  ps->tau = reinterpret_cast<unsigned long long*>(q + 512);
+  ps->stats = reinterpret_cast<int64_t*>(q + 512 + 64);
+  q += 768;
+  for (int i = 0; i < 2; ++i) {
+    ps->list[i] = reinterpret_cast<int2*>(q);
+    q += (size_t)C * sizeof(int2);
+  }
+  for (int i = 0; i < 2; ++i) {
+    ps->ldc[i] = prune_ld(C, i);
+    ps->cbuf[i] = reinterpret_cast<double*>(q);
+    q += (size_t)npad * ps->ldc[i] * 8;
+  }
+}
+
 
 // The fused small-n sweep covers npad <= 256, d <= 16 (1..8 outputs) and the fp64 covariance build; the rest takes
 // the K* + trmm path.  An npad = 384 instance (d <= 8, 226 VGPRs, 2 waves/SIMD) measured slower than the K* + trmm path
@@ -660,6 +878,75 @@ size_t sweep_workspace_bytes(int64_t npad, int64_t nrhs, int64_t m) {
 // unfused path (A/B measurements, parity tests of both paths).
 bool sweep_fused_ok(const Context* c, const gpx_kernel_params& p, int npad, int nrhs) {
   return c->sweep_fused && (npad == 128 || npad == 256) && p.d <= 16 && !p.cov_fp32;
+}
+
+bool sweep_prune_ok(const Context* c, const gpx_kernel_params& p, int npad) {
+  if (c->sweep_prune == 0 || sweep_fused_ok(c, p, npad, 1)) return false;
+  return npad >= (c->sweep_prune == 2 ? PRUNE_MIN_NPAD : PRUNE_DEFAULT_NPAD);
+}
+
+// K* and the partial means of one chunk (launch 1 of the file comment)
+static void launch_kstar(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X, int64_t ldx,
+                         const double* alpha, int nrhs, const double* Xs, int64_t ldxs, int64_t m_chunk,
+                         const SweepBuffers& b) {
+  LaunchTimer tm(c, GPX_TIMER_KSTAR);
+  const int64_t C = b.chunk;
+  dim3 g((unsigned)((m_chunk + WG - 1) / WG), npad / NB);
+#define GPX_KSTAR_K(D, F, K)                                                                                     \
+  (nrhs == 1 ? kstar_kernel<D, F, K, true><<<g, WG, 0, c->stream>>>(p, n, X, ldx, alpha, nrhs, Xs, ldxs, m_chunk, C, \
+                                                                    b.kstar, b.mu_part)                            \
+             : kstar_kernel<D, F, K, false><<<g, WG, 0, c->stream>>>(p, n, X, ldx, alpha, nrhs, Xs, ldxs, m_chunk, \
+                                                                     C, b.kstar, b.mu_part))
+#define GPX_KSTAR_F(D, F)                                                                                          \
+  (p.kind == GPX_KERNEL_RBF        ? GPX_KSTAR_K(D, F, GPX_KERNEL_RBF)                                             \
+   : p.kind == GPX_KERNEL_MATERN52 ? GPX_KSTAR_K(D, F, GPX_KERNEL_MATERN52)                                        \
+                                   : GPX_KSTAR_K(D, F, GPX_KERNEL_SCALE_LINEAR_MATERN52))
+#define GPX_KSTAR_M(D, K)                                                                                          \
+  (nrhs == 1 ? kstar_mfma_kernel<D, K, true><<<g, WG, 0, c->stream>>>(p, n, X, ldx, alpha, nrhs, Xs, ldxs, m_chunk, C, \
+                                                                      b.kstar, b.mu_part)                            \
+             : kstar_mfma_kernel<D, K, false><<<g, WG, 0, c->stream>>>(p, n, X, ldx, alpha, nrhs, Xs, ldxs, m_chunk,  \
+                                                                       C, b.kstar, b.mu_part))
+#define GPX_KSTAR_MK(D)                                                                                            \
+  (p.kind == GPX_KERNEL_RBF        ? GPX_KSTAR_M(D, GPX_KERNEL_RBF)                                                \
+   : p.kind == GPX_KERNEL_MATERN52 ? GPX_KSTAR_M(D, GPX_KERNEL_MATERN52)                                           \
+                                   : GPX_KSTAR_M(D, GPX_KERNEL_SCALE_LINEAR_MATERN52))
+#define GPX_KSTAR(D) (p.cov_fp32 ? GPX_KSTAR_F(D, true) : GPX_KSTAR_MK(D))
+  if (p.d <= 4)
+    GPX_KSTAR(4);
+  else if (p.d <= 8)
+    GPX_KSTAR(8);
+  else if (p.d <= 16)
+    GPX_KSTAR(16);
+  else  // d > 16: the difference form (the MFMA kernel's candidate tile would not fit 64 KB of LDS)
+    p.cov_fp32 ? GPX_KSTAR_F(32, true) : GPX_KSTAR_F(32, false);
+#undef GPX_KSTAR_MK
+#undef GPX_KSTAR_M
+#undef GPX_KSTAR
+#undef GPX_KSTAR_F
+#undef GPX_KSTAR_K
+}
+
+// finalize_kernel's arguments of a posterior (a = nullptr: per-output y_mean / y_scale, nullptr = identity) or of an
+// acquisition (a's y_mean / y_scale for the one output)
+static FinalizeArgs finalize_args(const gpx_kernel_params& p, const gpx_acq_params* a, int nrhs, const double* y_mean,
+                                  const double* y_scale) {
+  FinalizeArgs fa;
+  fa.p = p;
+  for (int q = 0; q < GPX_MAX_RHS; ++q) {
+    fa.y_mean[q] = (y_mean && q < nrhs) ? y_mean[q] : 0.0;
+    fa.y_scale[q] = (y_scale && q < nrhs) ? y_scale[q] : 1.0;
+  }
+  fa.acq_kind = a ? a->kind : 0;
+  fa.best_f = a ? a->best_f : 0.0;
+  fa.beta = a ? a->beta : 0.0;
+  if (a) {
+    fa.y_mean[0] = a->y_mean;
+    fa.y_scale[0] = a->y_scale;
+  }
+  fa.weight = 1.0;
+  fa.first = 0;
+  fa.acc_mu = fa.acc_var = nullptr;
+  return fa;
 }
 
 hipError_t launch_sweep_chunk(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X, int64_t ldx,
@@ -693,66 +980,14 @@ hipError_t launch_sweep_chunk(Context* c, const gpx_kernel_params& p, int n, int
 #undef GPX_SMALL_K
     nJB = nI = 1;
   } else {
-    {
-    LaunchTimer tm(c, GPX_TIMER_KSTAR);
-    dim3 g(ncb, nJB);
-#define GPX_KSTAR_K(D, F, K)                                                                                     \
-  (nrhs == 1 ? kstar_kernel<D, F, K, true><<<g, WG, 0, c->stream>>>(p, n, X, ldx, alpha, nrhs, Xs, ldxs, m_chunk, C, \
-                                                                    b.kstar, b.mu_part)                            \
-             : kstar_kernel<D, F, K, false><<<g, WG, 0, c->stream>>>(p, n, X, ldx, alpha, nrhs, Xs, ldxs, m_chunk, \
-                                                                     C, b.kstar, b.mu_part))
-#define GPX_KSTAR_F(D, F)                                                                                          \
-  (p.kind == GPX_KERNEL_RBF        ? GPX_KSTAR_K(D, F, GPX_KERNEL_RBF)                                             \
-   : p.kind == GPX_KERNEL_MATERN52 ? GPX_KSTAR_K(D, F, GPX_KERNEL_MATERN52)                                        \
-                                   : GPX_KSTAR_K(D, F, GPX_KERNEL_SCALE_LINEAR_MATERN52))
-#define GPX_KSTAR_M(D, K)                                                                                          \
-  (nrhs == 1 ? kstar_mfma_kernel<D, K, true><<<g, WG, 0, c->stream>>>(p, n, X, ldx, alpha, nrhs, Xs, ldxs, m_chunk, C, \
-                                                                      b.kstar, b.mu_part)                            \
-             : kstar_mfma_kernel<D, K, false><<<g, WG, 0, c->stream>>>(p, n, X, ldx, alpha, nrhs, Xs, ldxs, m_chunk,  \
-                                                                       C, b.kstar, b.mu_part))
-#define GPX_KSTAR_MK(D)                                                                                            \
-  (p.kind == GPX_KERNEL_RBF        ? GPX_KSTAR_M(D, GPX_KERNEL_RBF)                                                \
-   : p.kind == GPX_KERNEL_MATERN52 ? GPX_KSTAR_M(D, GPX_KERNEL_MATERN52)                                           \
-                                   : GPX_KSTAR_M(D, GPX_KERNEL_SCALE_LINEAR_MATERN52))
-#define GPX_KSTAR(D) (p.cov_fp32 ? GPX_KSTAR_F(D, true) : GPX_KSTAR_MK(D))
-    if (p.d <= 4)
-      GPX_KSTAR(4);
-    else if (p.d <= 8)
-      GPX_KSTAR(8);
-    else if (p.d <= 16)
-      GPX_KSTAR(16);
-    else  // d > 16: the difference form (the MFMA kernel's candidate tile would not fit 64 KB of LDS)
-      p.cov_fp32 ? GPX_KSTAR_F(32, true) : GPX_KSTAR_F(32, false);
-#undef GPX_KSTAR_MK
-#undef GPX_KSTAR_M
-#undef GPX_KSTAR
-#undef GPX_KSTAR_F
-#undef GPX_KSTAR_K
-  }
-  {
+    launch_kstar(c, p, n, npad, X, ldx, alpha, nrhs, Xs, ldxs, m_chunk, b);
     LaunchTimer tm(c, GPX_TIMER_TRMM);
     const int ncbt = (int)((m_chunk + TT - 1) / TT);
     trmm_sumsq_kernel<<<ncbt * nI, WG, 0, c->stream>>>(W, ldw, b.kstar, C, nI, ncbt, b.ss_part, 0);
   }
-  }
   {
     LaunchTimer tm(c, GPX_TIMER_ACQ);
-    FinalizeArgs fa;
-    fa.p = p;
-    for (int q = 0; q < GPX_MAX_RHS; ++q) {
-      fa.y_mean[q] = (y_mean && q < nrhs) ? y_mean[q] : 0.0;
-      fa.y_scale[q] = (y_scale && q < nrhs) ? y_scale[q] : 1.0;
-    }
-    fa.acq_kind = a ? a->kind : 0;
-    fa.best_f = a ? a->best_f : 0.0;
-    fa.beta = a ? a->beta : 0.0;
-    if (a) {
-      fa.y_mean[0] = a->y_mean;
-      fa.y_scale[0] = a->y_scale;
-    }
-    fa.weight = 1.0;
-    fa.first = 0;
-    fa.acc_mu = fa.acc_var = nullptr;
+    FinalizeArgs fa = finalize_args(p, a, nrhs, y_mean, y_scale);
     if (mo) {  // one output of a multi-output objective: accumulate, score later (launch_multi_score)
       mode = 2;
       fa.y_mean[0] = mo->y_mean;
@@ -765,7 +1000,7 @@ hipError_t launch_sweep_chunk(Context* c, const gpx_kernel_params& p, int n, int
     finalize_kernel<<<ncb, WG, 0, c->stream>>>(fa, mode, Xs, ldxs, m_chunk, C, nrhs, nJB, nI, b.mu_part,
                                                    b.ss_part, mean_out, ldmean, var_out, scores_out,
                                                    b.rec_val + rec_offset, b.rec_idx + rec_offset,
-                                                   index_offset);
+                                                   index_offset, PruneSel{});
   }
   return hipGetLastError();
 }
@@ -781,7 +1016,96 @@ hipError_t launch_multi_score(Context* c, const MultiOutput& mo, const gpx_acq_p
   fa.acc_var = mo.acc_var;
   const int ncb = (int)((m_chunk + WG - 1) / WG);
   finalize_kernel<<<ncb, WG, 0, c->stream>>>(fa, 3, nullptr, 0, m_chunk, 0, 1, 0, 0, nullptr, nullptr, nullptr, 0,
-                                             nullptr, scores_out, rec_val, rec_idx, index_offset);
+                                             nullptr, scores_out, rec_val, rec_idx, index_offset, PruneSel{});
+  return hipGetLastError();
+}
+
+// Stage boundaries of the pruned product: R[0] = 0 < 1 < 2 < 4 < 8 < 16 < nI (those below nI), doubling so that a
+// stage costs about three times everything before it: a candidate dropped after stage s has paid R(R+1) / (nI(nI+1)) of
+// its product, R = R[s+1].  Returns the number of stages.
+static int prune_stage_bounds(int nI, int* R) {
+  int S = 0;
+  R[0] = 0;
+  for (int r = 1; r < nI && r <= 16; r *= 2) R[++S] = r;
+  R[++S] = nI;
+  return S;
+}
+
+hipError_t launch_sweep_chunk_pruned(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X,
+                                     int64_t ldx, const double* W, int64_t ldw, const double* alpha, const double* Xs,
+                                     int64_t ldxs, int64_t m_chunk, const SweepBuffers& b, const PruneState& ps,
+                                     const gpx_acq_params* a, int64_t rec_offset, int64_t index_offset, bool first,
+                                     int64_t* host_stats) {
+  const int64_t C = b.chunk;
+  const int nJB = npad / NB, nI = npad / TT;
+  int R[PRUNE_MAX_STAGES];
+  const int S = prune_stage_bounds(nI, R);
+  launch_kstar(c, p, n, npad, X, ldx, alpha, 1, Xs, ldxs, m_chunk, b);
+  const FinalizeArgs fa = finalize_args(p, a, 1, nullptr, nullptr);
+  // The call's first incumbent: its leading PRUNE_SEED candidates through the full product and finalize (a chunk's
+  // later candidates start from the best score of everything scored before them).
+  const int seed = first ? (int)(m_chunk < PRUNE_SEED ? m_chunk : PRUNE_SEED) : 0;
+  const int seed_blocks = (seed + WG - 1) / WG;
+  const int col0 = ((seed + TT - 1) / TT) * TT;  // seed < PRUNE_SEED: the whole chunk, no staged columns
+  const int ncols = m_chunk > seed ? (int)(m_chunk - col0) : 0;
+  const int tiles = (ncols + TT - 1) / TT, blocks = (ncols + WG - 1) / WG;
+  PruneBufs pb;
+  pb.kstar = b.kstar;
+  pb.c1 = ps.cbuf[0];
+  pb.c2 = ps.cbuf[1];
+  pb.ld0 = C;
+  pb.ld1 = ps.ldc[0];
+  pb.ld2 = ps.ldc[1];
+  pb.list0 = ps.list[0];
+  pb.list1 = ps.list[1];
+  {
+    LaunchTimer tm(c, GPX_TIMER_TRMM);
+    prune_init_kernel<<<1, 64, 0, c->stream>>>(ps.desc, ps.count, ps.tau, ps.stats, col0, ncols, R[1], S == 1, first);
+    if (seed) {
+      const int ncbt = (seed + TT - 1) / TT;
+      trmm_sumsq_kernel<<<ncbt * nI, WG, 0, c->stream>>>(W, ldw, b.kstar, C, nI, ncbt, b.ss_part, 0);
+      host_stats[1] += seed;
+      host_stats[2] += (int64_t)ncbt * nI;
+    }
+  }
+  if (seed) {
+    LaunchTimer tm(c, GPX_TIMER_ACQ);
+    PruneSel sel{};
+    sel.tau = ps.tau;
+    finalize_kernel<<<seed_blocks, WG, 0, c->stream>>>(fa, 1, Xs, ldxs, seed, C, 1, nJB, nI, b.mu_part, b.ss_part,
+                                                       nullptr, 0, nullptr, nullptr, b.rec_val + rec_offset,
+                                                       b.rec_idx + rec_offset, index_offset, sel);
+  }
+  if (ncols == 0) return hipGetLastError();
+  PruneSel sel{};
+  sel.list0 = ps.list[0];
+  sel.list1 = ps.list[1];
+  sel.tau = ps.tau;
+  {
+    LaunchTimer tm(c, GPX_TIMER_TRMM);
+    constexpr int ROWS = 32;  // K* rows a compaction workgroup copies
+    const dim3 gc((ncols / 2 + TT + WG - 1) / WG, npad / ROWS);
+    for (int s = 0; s < S; ++s) {
+      const PruneStage st{pb, ps.desc + s, R[s], R[s + 1] - R[s]};
+      trmm_stage_kernel<<<tiles * st.nrows, WG, 0, c->stream>>>(W, ldw, C, nI, b.ss_part, st);
+      if (s == S - 1) break;
+      sel.desc = ps.desc + s;
+      sel.count = ps.count + s;
+      finalize_kernel<<<blocks, WG, 0, c->stream>>>(fa, 4, Xs, ldxs, m_chunk, C, 1, nJB, R[s + 1], b.mu_part,
+                                                    b.ss_part, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
+                                                    index_offset, sel);
+      prune_compact_kernel<<<gc, WG, 0, c->stream>>>(pb, ps.desc + s, ps.desc + s + 1, ps.count + s, ROWS,
+                                                     R[s + 2] - R[s + 1], s + 2 == S, ps.stats);
+    }
+  }
+  {
+    LaunchTimer tm(c, GPX_TIMER_ACQ);
+    sel.desc = ps.desc + S - 1;
+    sel.count = nullptr;
+    finalize_kernel<<<blocks, WG, 0, c->stream>>>(fa, 1, Xs, ldxs, m_chunk, C, 1, nJB, nI, b.mu_part, b.ss_part,
+                                                  nullptr, 0, nullptr, nullptr, b.rec_val + rec_offset + seed_blocks,
+                                                  b.rec_idx + rec_offset + seed_blocks, index_offset, sel);
+  }
   return hipGetLastError();
 }
 

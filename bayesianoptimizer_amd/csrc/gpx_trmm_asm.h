@@ -202,7 +202,10 @@ __device__ __forceinline__ void wait_vm0(Operand<AKM>& A, Operand<BKM>& B) {
 
 // The 128 x 128 tile.  AKM / BKM: A(m, k) / B(k, n) k-major (A(m, k) = Ag[k lda + m], B(k, n) = Bg[k ldb + n]) or
 // row-major (A(m, k) = Ag[m lda + k], B(k, n) = Bg[n ldb + k]).
-template <bool AKM, bool BKM, bool NEG = false>
+// TAG: kernels of one translation unit that each want the k loop inlined instantiate the tile with different tags (the
+// loop's member functions are not forced inline: with one caller each they are inlined, with two they become calls and
+// the tile's registers go to scratch).
+template <bool AKM, bool BKM, bool NEG = false, int TAG = 0>
 struct TileT {
   d4 acc[4][4];  // acc[i][j][r]: row (w >> 1) * 64 + 16 i + (lane >> 4) + 4 r, column (w & 1) * 64 + 16 j + (lane & 15)
   Frag f0, f1;
@@ -399,16 +402,18 @@ struct TileT {
 // The sweep product's tile: both operands k-major; for the triangular W (zero_tail: nk a multiple of 8) the zero 16 x 16
 // blocks of the diagonal 128-block are skipped (run_tri: the waves of rows 0-63 / 64-127 form 10 / 26 of their 32 row-block
 // x k-tile products there, against 16 / 32 when only the zero 64-block was skipped).
-struct Tile : TileT<true, true> {
+template <int TAG>
+struct TileTag : TileT<true, true, false, TAG> {
   __device__ void run(const double* __restrict__ Ag, int64_t lda, const double* __restrict__ Bg, int64_t ldb, int nk,
                       double* smem, bool zero_tail) {
-    zero();
+    this->zero();
     if (zero_tail)
-      TileT<true, true>::run_tri(Ag, lda, Bg, ldb, nk, smem);
+      this->run_tri(Ag, lda, Bg, ldb, nk, smem);
     else
-      TileT<true, true>::run<false, false>(Ag, lda, Bg, ldb, nk, smem);
+      TileT<true, true, false, TAG>::template run<false, false>(Ag, lda, Bg, ldb, nk, smem);
   }
 };
+using Tile = TileTag<0>;
 
 }  // namespace trmm_asm
 }  // namespace gpx

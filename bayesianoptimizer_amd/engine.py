@@ -578,6 +578,13 @@ class GPEngine:
             return best_val, best_idx, scores
         return best_val, best_idx
 
+    def sweep_stats(self):
+        """Work counters of the last `acquire` call (synchronises the stream): (candidates seen, candidates whose
+        variance product was computed to its last row tile, 128x128 product tiles executed, tiles of the full sweep)."""
+        out = (ctypes.c_int64 * 4)()
+        self._check(self.lib.gpx_sweep_stats(self.handle, out))
+        return tuple(int(v) for v in out)
+
     def acquire_multi(self, states: Sequence[GPState], Xs, kind: Union[str, int] = "logei", best_f: float = 0.0,
                       beta: float = 4.0, weights: Optional[Sequence[float]] = None,
                       y_mean: Optional[Sequence[float]] = None, y_scale: Optional[Sequence[float]] = None,

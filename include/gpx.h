@@ -151,7 +151,10 @@ size_t gpx_acq_params_size(void);
  *                          the lookahead schedule (flush every potrf_lazy, default 3 / by size), the rest eager (rounded
  *                          down to the launch after a flush)
  *  GPX_OPT_POTRF_SPLIT     panel row blocks per workgroup: -1 (default) split in 2 where the launch still fits the
- *                          co-resident slots, 1 never split, 3 split only where the split launch fits one workgroup per CU */
+ *                          co-resident slots, 1 never split, 3 split only where the split launch fits one workgroup per CU
+ *  GPX_OPT_SWEEP_PRUNE     gpx_acquire_argmax_f64 without scores_out on the K* + trmm path: 1 (default) the pruned sweep
+ *                          from padded n 384 on, 0 the full sweep, 2 the pruned sweep at every padded n >= 384 (tests).
+ *                          The returned (value, index) pair has the same bits either way. */
 enum {
   GPX_OPT_RESERVED_0 = 0,
   GPX_OPT_SPIN_LIMIT = 1,
@@ -161,7 +164,8 @@ enum {
   GPX_OPT_POTRF_MODE = 5,
   GPX_OPT_POTRF_SWITCH = 6,
   GPX_OPT_POTRF_SPLIT = 7,
-  GPX_OPT_COUNT = 8
+  GPX_OPT_SWEEP_PRUNE = 8,
+  GPX_OPT_COUNT = 9
 };
 gpx_status gpx_set_option(gpx_handle h, int32_t option, int64_t value);
 gpx_status gpx_get_option(gpx_handle h, int32_t option, int64_t* value_host);
@@ -306,12 +310,21 @@ gpx_status gpx_posterior_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n
  * linear objective) and reduce to (best value, lowest index among ties); reported indices are
  * index_offset + local index (candidate shards on several GPUs).  best_val/best_idx are device scalars; scores_out
  * (device, m) is optional (NULL = not written).  Replaces the raw-sample sweep + argmax of optimize_acqf
- * (optimization/Bayesian.py:105-113) and the pool scan + topk of optimization/Bayesian7.py:646-681. */
+ * (optimization/Bayesian.py:105-113) and the pool scan + topk of optimization/Bayesian7.py:646-681.
+ * The returned pair is exact: without scores_out the sweep may stop a candidate's variance product early once an upper
+ * bound of its score (every acquisition here grows with the variance, and the variance only shrinks as the product
+ * proceeds) lies below a score already computed in full; such a candidate cannot be the argmax, and the pair has the
+ * bits of the full sweep (GPX_OPT_SWEEP_PRUNE = 0).  scores_out != NULL forces the full sweep: every score is wanted. */
 gpx_status gpx_acquire_argmax_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X,
                                   int64_t ldx, const double* W, int64_t ldw, const double* alpha,
                                   const double* Xs, int64_t m, int64_t ldxs, const gpx_acq_params* a,
                                   int64_t index_offset, double* best_val, int64_t* best_idx,
                                   double* scores_out, void* ws, size_t ws_bytes);
+/* Work counters of the handle's last gpx_acquire_argmax_f64 call (synchronises the handle's stream; the workspace of
+ * that call must still be allocated): out_host[0] candidates seen, [1] candidates whose last 128-row tile of the
+ * variance product was computed, [2] 128 x 128 product tiles executed, [3] the tiles the full sweep executes (0 / 0 on
+ * the fused small-n path, which has no tiles). */
+gpx_status gpx_sweep_stats(gpx_handle h, int64_t* out_host);
 
 /* Candidate sweep of a LINEAR OBJECTIVE over T independent GPs on the same training inputs X (the outputs of the batched
  * fits above, or of separate fits / appends of the same n): f = sum_t w_t (y_mean[t] + y_scale[t] g_t) with g_t the
