@@ -199,6 +199,9 @@ _PROTOS = {
     "gpx_timing_enable": (c_int32, [_h, c_int32]),
     "gpx_timing_reset": (c_int32, [_h]),
     "gpx_timing_query": (c_int32, [_h, c_int32, POINTER(c_double), POINTER(c_int64)]),
+    "gpx_debug_kstar_workspace_size": (c_int32, [c_int64, c_int64, POINTER(c_size_t)]),
+    "gpx_debug_kstar_f64": (c_int32, [_h, POINTER(KernelParamsC), c_int64, _p, c_int64, _p, c_int64, c_int64, _p, _p,
+                                      _p, c_int64, _p, c_size_t]),
 }
 
 _lib = None
@@ -220,6 +223,10 @@ def load() -> ctypes.CDLL:
     except OSError as e:  # pragma: no cover - depends on the ROCm runtime being present
         raise GPXLibraryError(f"failed to load {LIB_PATH}: {e}") from e
     for name, (res, args) in _PROTOS.items():
+        if name.startswith("gpx_debug_") and "GPX_LIB" in os.environ and not hasattr(lib, name):
+            # A/B tooling against a library older than a debug entry point (no production path calls one)
+            print(f"gpx: {LIB_PATH} has no {name}; left unbound", file=sys.stderr)
+            continue
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -954,8 +954,12 @@ gpx_status gpx_acquire_argmax_f64(gpx_handle h, const gpx_kernel_params* p, int6
   GPX_TRY(carve_sweep(c, npad, 1, m, ws, ws_bytes, &b));
   // scores_out wants every score: the full sweep
   const bool prune = !scores_out && gpx::sweep_prune_ok(c, *p, (int)npad);
+  // the MFMA K* build's configurations take the lazy form (K* in full height for the first tile's survivors only)
+  const bool lazy = prune && gpx::sweep_lazy_ok(*p);
   gpx::PruneState ps;
+  gpx::PruneHead ph;
   if (prune) gpx::sweep_prune_carve(b.rec_idx + (m + 255) / 256 + 1, npad, b.chunk, &ps);
+  if (lazy) gpx::sweep_prune_carve_head(ps, npad, b.chunk, gpx::sweep_super_size(npad, m), m, &ph);
   GPX_USE_DEVICE(c);
   const bool fused = gpx::sweep_fused_ok(c, *p, (int)npad, 1);
   c->sweep_stats[0] = m;
@@ -963,6 +967,23 @@ gpx_status gpx_acquire_argmax_f64(gpx_handle h, const gpx_kernel_params* p, int6
   c->sweep_stats[2] = c->sweep_stats[3] = 0;
   c->sweep_stats_dev = prune ? ps.stats : nullptr;
   int64_t rec = 0;
+  if (lazy) {
+    for (int64_t s = 0; s < m; s += b.chunk)  // [3]: the tiles of the full sweep, with the full path's chunking
+      c->sweep_stats[3] += (((m - s) < b.chunk ? (m - s) : b.chunk) + 127) / 128 * (npad / 128);
+    // the call's first super-chunk is one chunk long: everything after it is bounded against the best of a chunk's
+    // scores instead of the seed block's alone (one super-chunk of 2^20 from the seed on: 23537 product tiles and
+    // 17.6 ms on the bench problem instead of 9121 and 10.2, profiles/r08_variants_probe.jsonl)
+    for (int64_t s = 0, ms = 0; s < m; s += ms) {
+      const int64_t lim = (s == 0 && b.chunk < ph.super) ? b.chunk : ph.super;
+      ms = (m - s) < lim ? (m - s) : lim;
+      GPX_TRY(hip_check(c,
+                        gpx::launch_sweep_super_pruned(c, *p, (int)n, (int)npad, X, ldx, W, ldw, alpha, Xs + s * ldxs,
+                                                       ldxs, ms, b, ps, ph, a, &rec, index_offset + s, s == 0,
+                                                       c->sweep_stats),
+                        "acquire"));
+    }
+    return hip_check(c, gpx::launch_argmax_final(c, ph.rec_val, ph.rec_idx, rec, best_val, best_idx), "argmax");
+  }
   for (int64_t s = 0; s < m; s += b.chunk) {
     const int64_t mc = (m - s) < b.chunk ? (m - s) : b.chunk;
     if (!fused) c->sweep_stats[3] += (mc + 127) / 128 * (npad / 128);
@@ -996,6 +1017,45 @@ gpx_status gpx_sweep_stats(gpx_handle h, int64_t* out) {
     out[2] += dev[1];
   }
   return GPX_OK;
+}
+
+gpx_status gpx_debug_kstar_workspace_size(int64_t n, int64_t ldout, size_t* bytes) {
+  if (!bytes || n < 1 || ldout < 256) return GPX_INVALID_ARG;
+  const int64_t npad = padded(n);
+  *bytes = ((size_t)(npad / gpx::NB) * ldout + npad) * 8 + 256;
+  return GPX_OK;
+}
+
+gpx_status gpx_debug_kstar_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X, int64_t ldx,
+                               const double* Xs, int64_t m, int64_t ldxs, const int32_t* list, const int32_t* count,
+                               double* out, int64_t ldout, void* ws, size_t ws_bytes) {
+  Context* c = reinterpret_cast<Context*>(h);
+  if (!c) return GPX_INVALID_ARG;
+  GPX_TRY(check_params(c, p));
+  GPX_TRY(check_n(c, n));
+  if (m < 1 || m > ((int64_t)1 << 30)) return fail(c, GPX_INVALID_ARG, "m must be in [1, 2^30]");
+  GPX_NONNULL(c, X);
+  GPX_NONNULL(c, Xs);
+  GPX_NONNULL(c, out);
+  const int64_t npad = padded(n);
+  GPX_TRY(check_ld(c, ldx, p->d, "X", false));
+  GPX_TRY(check_ld(c, ldxs, p->d, "Xs", false));
+  if (ldout < (m + 255) / 256 * 256) return fail(c, GPX_INVALID_ARG, "ldout must be >= m rounded up to 256");
+  if (list && !count) return fail(c, GPX_INVALID_ARG, "count is NULL");
+  if (list && !gpx::sweep_lazy_ok(*p))
+    return fail(c, GPX_INVALID_ARG, "the gather build covers the fp64 covariance with d <= 16");
+  double* scratch = nullptr;
+  if (!list) {  // the full build writes its mean partials: scratch for them and a zero alpha
+    size_t need = 0;
+    GPX_TRY(gpx_debug_kstar_workspace_size(n, ldout, &need));
+    if (!ws || ws_bytes < need) return fail(c, GPX_INVALID_ARG, "debug_kstar workspace too small");
+    scratch = align256(ws);
+  }
+  GPX_USE_DEVICE(c);
+  return hip_check(c,
+                   gpx::launch_debug_kstar(c, *p, (int)n, (int)npad, X, ldx, Xs, ldxs, m, list, count, out, ldout,
+                                           scratch),
+                   "debug_kstar");
 }
 
 gpx_status gpx_sweep_multi_workspace_size(int64_t n, int64_t m, size_t* bytes) {

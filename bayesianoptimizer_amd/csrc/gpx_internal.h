@@ -173,7 +173,8 @@ struct PruneDesc {  // the active column set of one stage (written by the launch
   int col0;    // first column in the buffer (buf 0 only: the columns after the seed block)
   int ncols;   // active candidates (slots 0 .. ncols-1)
   int ntiles;  // 128-column tiles covering them
-  int list;    // -1: slot s is chunk column col0 + s; 0 / 1: the index list mapping slots to chunk columns
+  int list;    // -1: slot s is chunk column col0 + s; 0 / 1: the index list mapping slots to chunk columns; 2: the
+               // round's part of the head phase's survivor list (lazy form)
   int pad[3];
 };
 struct PruneState {  // device pointers into the sweep workspace
@@ -197,6 +198,33 @@ hipError_t launch_sweep_chunk_pruned(Context* c, const gpx_kernel_params& p, int
                                      int64_t ldxs, int64_t m_chunk, const SweepBuffers& b, const PruneState& ps,
                                      const gpx_acq_params* a, int64_t rec_offset, int64_t index_offset, bool first,
                                      int64_t* host_stats);
+// The lazy form (launch_sweep_super_pruned): K* in full height only for the survivors of the first row tile.
+constexpr int PRUNE_HEAD_ROWS = 128;  // K* rows the head phase stores: the product's first row tile
+struct PruneHead {    // device pointers into the sweep workspace, after the compact buffers
+  int64_t super;      // candidates per super-chunk (sweep_super_size); the pitch of the three arrays below
+  int2* survivors;    // the head phase's survivor list: {super-chunk column, slot}; super + 128 entries
+  double* head;       // PRUNE_HEAD_ROWS x super
+  double* mu_part;    // (npad/64) x super
+  double* ss_part;    // (npad/128) x super
+  double* rec_val;    // records of the call
+  int64_t* rec_idx;
+};
+int64_t sweep_super_size(int64_t npad, int64_t m);
+void sweep_prune_carve_head(const PruneState& ps, int64_t npad, int64_t C, int64_t MA, int64_t m, PruneHead* ph);
+// the configurations of the MFMA K* build (fp64 covariance, d <= 16); the others keep launch_sweep_chunk_pruned
+bool sweep_lazy_ok(const gpx_kernel_params& p);
+// One super-chunk of gpx_acquire_argmax_f64; first: the call's first (resets the incumbent and the counters, scores the
+// seed block in full).  *recs: the records written so far, advanced.  host_stats as above.
+hipError_t launch_sweep_super_pruned(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X,
+                                     int64_t ldx, const double* W, int64_t ldw, const double* alpha, const double* Xs,
+                                     int64_t ldxs, int64_t m_super, const SweepBuffers& b, const PruneState& ps,
+                                     const PruneHead& ph, const gpx_acq_params* a, int64_t* recs, int64_t index_offset,
+                                     bool first, int64_t* host_stats);
+// K(X, Xs) through the sweep's K* build (gpx_debug_kstar_f64): list = nullptr the full-store build of columns 0 .. m-1,
+// else the gather build of columns list[0 .. *count - 1] (m: the most the list can hold).  out: npad rows of pitch ldout.
+hipError_t launch_debug_kstar(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X, int64_t ldx,
+                              const double* Xs, int64_t ldxs, int64_t m, const int* list, const int* count,
+                              double* out, int64_t ldout, double* mu_scratch);
 hipError_t launch_multi_score(Context* c, const MultiOutput& mo, const gpx_acq_params& a, int64_t m_chunk,
                               double* scores_out, double* rec_val, int64_t* rec_idx, int64_t index_offset);
 hipError_t launch_argmax_final(Context* c, const double* vals, const int64_t* idx, int64_t count, double* best_val,

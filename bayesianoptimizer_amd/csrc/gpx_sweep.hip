@@ -19,7 +19,9 @@
 // the row tiles run in stages (trmm_stage_kernel); after each stage finalize_kernel mode 4 bounds every active
 // candidate's score from the partials it has, drops those that cannot reach the best score computed in full so far,
 // and prune_compact_kernel gathers the surviving K* columns; finalize scores the survivors of the last stage.  The
-// (value, index) pair has the bits of the full sweep.
+// (value, index) pair has the bits of the full sweep.  Where the MFMA K* build applies, the pruned form is lazy
+// (launch_sweep_super_pruned): K* rows 0 .. 127 and the mean partials for every candidate of a super-chunk, the first
+// stage and its bound pass as one launch each, and full-height K* columns rebuilt from the survivor list for the rest.
 #include "gpx_internal.h"
 #include "gpx_device.h"
 #include "gpx_trmm_asm.h"
@@ -185,20 +187,71 @@ __global__ void __launch_bounds__(WG) kstar_kernel(gpx_kernel_params p, int n, c
 // rows by two v_permlane32_swap + two v_permlane16_swap, so every store instruction writes one K* row of 64 consecutive
 // candidates (512 bytes) like the difference-form kernel (an untransposed first version, four 128-byte row segments per
 // instruction, ran at 3.5 vs 4.7 TB/s).  Per element: one fma, a compare and the covariance, no per-dimension VALU work.
-template <int DMAX, int KIND, bool ONE_RHS>
+//
+// MODE (one element arithmetic for all three: a column's K* entries have the same bits whichever mode built them, whatever
+// slot it sits in):
+//  KSTAR_FULL    every row block stores its rows and its mean partials (the full sweep, the seed block).
+//  KSTAR_MU      the pruned sweep's head phase beyond the head rows: row blocks aux.jb0 + blockIdx.y add their mean
+//                partials and store no K* (the head rows themselves, PRUNE_HEAD_ROWS of them, are a KSTAR_FULL launch
+//                over the first row blocks: the rows the first stage of the product reads).
+//  KSTAR_GATHER  the pruned sweep's tail: column s of the output is candidate list[first + s] for s below the round's
+//                column count min(*count - first, cap) (clamped at 0), zero up to the end of the workgroup's 256 columns;
+//                no mean partials; workgroups beyond the count return at once.  Workgroup (0, 0) also writes the round's
+//                first descriptor and resets its survivor counts (read by later launches only).
+constexpr int KSTAR_FULL = 0, KSTAR_MU = 1, KSTAR_GATHER = 2;
+struct KstarAux {
+  int jb0;           // MU: first row block of the launch
+  const int* list;   // GATHER: entry s at list[s * lstride] (the survivor list's int2 .x, or a plain index array)
+  int lstride;
+  const int* count;  // GATHER: entries in the list (device)
+  int first, cap;    // GATHER: this round's entries first .. first + cap - 1
+  int* pad;          // GATHER, optional: the list again, to mark the last tile's padding slots with -1
+  PruneDesc* desc;   // GATHER, optional: the round's first descriptor
+  int* rcount;       // its stages' survivor counts (PRUNE_MAX_STAGES - 1 of them)
+  int64_t* stats;    // the pruned sweep's counters
+  int rows0, last;   // row tiles of the round's first stage; it is also the last
+};
+
+template <int DMAX, int KIND, bool ONE_RHS, int MODE>
 __global__ void __launch_bounds__(WG) kstar_mfma_kernel(gpx_kernel_params p, int n, const double* __restrict__ X,
                                                         int64_t ldx, const double* __restrict__ alpha, int nrhs,
                                                         const double* __restrict__ Xs, int64_t ldxs, int64_t m_chunk,
                                                         int64_t C, double* __restrict__ kstar,
-                                                        double* __restrict__ mu_part) {
+                                                        double* __restrict__ mu_part, KstarAux aux) {
   constexpr bool lin = (KIND == GPX_KERNEL_SCALE_LINEAR_MATERN52);
+  constexpr bool gather = MODE == KSTAR_GATHER;
   constexpr int KS = DMAX / 4;
   constexpr int NRQ = ONE_RHS ? 1 : GPX_MAX_RHS;
   __shared__ double sa[NB][DMAX + 1], sb[WG][DMAX + 1], ra[lin ? NB : 1][DMAX + 1], rb[lin ? WG : 1][DMAX + 1];
   __shared__ double na[NB], nb[WG], cen[DMAX], sal[NB][NRQ];
-  const int jb = blockIdx.y, j0 = jb * NB, d = p.d, t = threadIdx.x;
+  __shared__ int sidx[gather ? WG : 1];
+  const int jb = MODE == KSTAR_MU ? (int)blockIdx.y + aux.jb0 : (int)blockIdx.y, j0 = jb * NB, d = p.d, t = threadIdx.x;
   const int64_t c0 = (int64_t)blockIdx.x * WG;
   const int nv = n - j0 < NB ? n - j0 : NB;  // valid training rows of the block (<= 0: all padding)
+  if constexpr (gather) {
+    const int left = *aux.count - aux.first;
+    const int nr = left < 0 ? 0 : left < aux.cap ? left : aux.cap;
+    const int ntl = (nr + 127) / 128;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && t == 0 && aux.desc) {
+      PruneDesc o;
+      o.buf = 0;
+      o.col0 = 0;
+      o.ncols = nr;
+      o.ntiles = ntl;
+      o.list = 2;
+      o.pad[0] = o.pad[1] = o.pad[2] = 0;
+      *aux.desc = o;
+      for (int s = 0; s < PRUNE_MAX_STAGES - 1; ++s) aux.rcount[s] = 0;
+      aux.stats[1] += (int64_t)ntl * aux.rows0;
+      if (aux.last) aux.stats[0] += nr;
+    }
+    if (c0 >= nr) return;
+    const int slot = (int)c0 + t;
+    sidx[t] = slot < nr ? aux.list[(int64_t)(aux.first + slot) * aux.lstride] : -1;
+    if (aux.pad && blockIdx.y == 0 && slot >= nr && slot < ntl * 128)
+      aux.pad[(int64_t)(aux.first + slot) * aux.lstride] = -1;
+    __syncthreads();
+  }
   for (int e = t; e < NB * DMAX; e += WG) {
     const int r = e / DMAX, k = e % DMAX;
     const double v = (k < d && j0 + r < n) ? X[(int64_t)(j0 + r) * ldx + k] : 0.0;
@@ -207,13 +260,19 @@ __global__ void __launch_bounds__(WG) kstar_mfma_kernel(gpx_kernel_params p, int
   }
   for (int e = t; e < WG * DMAX; e += WG) {
     const int r = e / DMAX, k = e % DMAX;
-    const double v = (k < d && c0 + r < m_chunk) ? Xs[(c0 + r) * ldxs + k] : 0.0;
+    double v;
+    if constexpr (gather)
+      v = (k < d && sidx[r] >= 0) ? Xs[(int64_t)sidx[r] * ldxs + k] : 0.0;
+    else
+      v = (k < d && c0 + r < m_chunk) ? Xs[(c0 + r) * ldxs + k] : 0.0;
     sb[r][k] = (k < d) ? v / p.lengthscale[k] : 0.0;
     if constexpr (lin) rb[r][k] = v;
   }
-  for (int e = t; e < NB * NRQ; e += WG) {
-    const int r = e / NRQ, q = e % NRQ;
-    sal[r][q] = (q < nrhs && j0 + r < n) ? alpha[(int64_t)(j0 + r) * nrhs + q] : 0.0;
+  if constexpr (!gather) {
+    for (int e = t; e < NB * NRQ; e += WG) {
+      const int r = e / NRQ, q = e % NRQ;
+      sal[r][q] = (q < nrhs && j0 + r < n) ? alpha[(int64_t)(j0 + r) * nrhs + q] : 0.0;
+    }
   }
   __syncthreads();
   if (t < DMAX) {
@@ -247,6 +306,11 @@ __global__ void __launch_bounds__(WG) kstar_mfma_kernel(gpx_kernel_params p, int
   double nbc[4];
 #pragma unroll
   for (int cb = 0; cb < 4; ++cb) nbc[cb] = nb[64 * w + 16 * cb + m];
+  bool cok[4] = {true, true, true, true};  // GATHER: the column is a listed candidate (else a zero column)
+  if constexpr (gather) {
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) cok[cb] = sidx[64 * w + 16 * cb + m] >= 0;
+  }
 #pragma unroll 1
   for (int rs = 0; rs < NB; rs += 16) {
     double kv[4][4];  // [r][cb]: row rs + kq + 4 r, candidate 64 w + 16 cb + m
@@ -262,20 +326,28 @@ __global__ void __launch_bounds__(WG) kstar_mfma_kernel(gpx_kernel_params p, int
       for (int r = 0; r < 4; ++r) {
         const int j = rs + kq + 4 * r;
         double v = cov_from_r2(KIND, p.outputscale, sqdist_expanded(na[j], nbc[cb], acc[r]), lin ? lac[r] : 0.0);
-        v = j < nv ? v : 0.0;
+        if constexpr (gather)
+          v = (j < nv && cok[cb]) ? v : 0.0;
+        else
+          v = j < nv ? v : 0.0;
         kv[r][cb] = v;
+        if constexpr (!gather) {
 #pragma unroll
-        for (int q = 0; q < NRQ; ++q) mu[cb][q] = fma(sal[j][q], v, mu[cb][q]);
+          for (int q = 0; q < NRQ; ++q) mu[cb][q] = fma(sal[j][q], v, mu[cb][q]);
+        }
       }
     }
     // after the transpose, register q of 16-lane row g holds row rs + q + 4 r, candidate 64 w + 16 g + m
+    if constexpr (MODE != KSTAR_MU) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      transpose_rows4(kv[r]);
+      for (int r = 0; r < 4; ++r) {
+        transpose_rows4(kv[r]);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) kstar[(int64_t)(j0 + rs + q + 4 * r) * C + c0 + 64 * w + lane] = kv[r][q];
+        for (int q = 0; q < 4; ++q) kstar[(int64_t)(j0 + rs + q + 4 * r) * C + c0 + 64 * w + lane] = kv[r][q];
+      }
     }
   }
+  if constexpr (gather) return;
 #pragma unroll
   for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
@@ -323,6 +395,7 @@ struct PruneBufs {
   int64_t ld0, ld1, ld2;
   int2* list0;
   int2* list1;
+  const int2* list2;  // the round's part of the head phase's survivor list (PruneDesc::list = 2)
 };
 // One stage of the pruned sweep (trmm_stage_kernel).
 struct PruneStage {
@@ -366,7 +439,7 @@ __device__ __forceinline__ void trmm_sumsq_body(const double* __restrict__ W, in
     if ((int)blockIdx.x >= ncb * nrows) return;
     kstar = buf == 0 ? st.pb.kstar : buf == 1 ? st.pb.c1 : st.pb.c2;
     ldb = buf == 0 ? st.pb.ld0 : buf == 1 ? st.pb.ld1 : st.pb.ld2;
-    list = li < 0 ? nullptr : li ? st.pb.list1 : st.pb.list0;
+    list = li < 0 ? nullptr : li == 2 ? st.pb.list2 : li ? st.pb.list1 : st.pb.list0;
   }
   int l, cb;
   trmm_tile_order(blockIdx.x, nrows, ncb, l, cb);
@@ -597,6 +670,7 @@ struct PruneSel {
   int2* list1;
   int* count;
   unsigned long long* tau;
+  const int2* list2;  // read only (PruneDesc::list = 2); its survivors go to list0
 };
 constexpr double PRUNE_EPS = 1e-9;  // margin of the bound test over acq_score's rounding
 
@@ -624,7 +698,7 @@ __global__ void __launch_bounds__(WG) finalize_kernel(FinalizeArgs fa, int mode,
     const PruneDesc d = *ps.desc;
     if (mode == 4 && (int64_t)blockIdx.x * WG >= d.ncols) return;
     valid = t < d.ncols;
-    c = !valid ? 0 : d.list < 0 ? d.col0 + t : (d.list ? ps.list1 : ps.list0)[t].x;
+    c = !valid ? 0 : d.list < 0 ? d.col0 + t : (d.list == 2 ? ps.list2 : d.list ? ps.list1 : ps.list0)[t].x;
     survivors = d.list == 0 ? ps.list1 : ps.list0;
   }
   double score = -INFINITY;
@@ -846,11 +920,36 @@ static int64_t prune_ld(int64_t C, int which) {
   const int64_t cols = which == 0 ? C / 2 : C / 4;
   return ((cols + TT - 1) / TT) * TT;
 }
+// The head phase's super-chunk: as many candidates as a byte budget over its per-candidate arrays holds (PRUNE_HEAD_ROWS
+// rows of K*, the mean partials of every 64-row block, the variance partials of every row tile), at most 2^20 and the
+// call, a multiple of 256.  1.75 GiB is 2^20 candidates at padded n = 4096; the budget bounds the arrays at any n.
+int64_t sweep_super_size(int64_t npad, int64_t m) {
+  const int64_t per = 8 * (PRUNE_HEAD_ROWS + npad / NB + npad / TT);
+  int64_t cap = ((((int64_t)7 << 28) / per) / 256) * 256;
+  if (cap > ((int64_t)1 << 20)) cap = (int64_t)1 << 20;
+  const int64_t C = sweep_chunk_size(npad, m);
+  if (cap < C) cap = C;  // (never at the sizes the library accepts: a column of K* outweighs the per-candidate arrays)
+  int64_t need = ((m + 255) / 256) * 256;
+  if (need < 256) need = 256;
+  return need < cap ? need : cap;
+}
+// Records of the lazy pruned sweep: per super-chunk the seed block's and one 256-candidate block per 256 columns of every
+// tail round it can need.
+static int64_t sweep_lazy_records(int64_t npad, int64_t m) {
+  const int64_t C = sweep_chunk_size(npad, m), MA = sweep_super_size(npad, m);
+  const int64_t supers = (m + MA - 1) / MA + 1, rounds = (MA + C - 1) / C;  // (+ 1: the call's short first one)
+  return PRUNE_SEED / WG + supers * rounds * (C / WG);
+}
 size_t sweep_prune_bytes(int64_t npad, int64_t m) {
   if (npad < PRUNE_MIN_NPAD) return 0;
-  const int64_t C = sweep_chunk_size(npad, m);
+  const int64_t C = sweep_chunk_size(npad, m), MA = sweep_super_size(npad, m);
   static_assert(sizeof(PruneDesc) * PRUNE_MAX_STAGES <= 256 && sizeof(int) * PRUNE_MAX_STAGES <= 256, "header slots");
-  return 256 + 3 * 256 + 2 * (size_t)C * sizeof(int2) + (size_t)npad * (prune_ld(C, 0) + prune_ld(C, 1)) * 8;
+  size_t b = 256 + 3 * 256 + 2 * (size_t)C * sizeof(int2) + (size_t)npad * (prune_ld(C, 0) + prune_ld(C, 1)) * 8;
+  // the head phase (launch_sweep_super_pruned): survivor list (+ one tile of padding slots), head rows, partials, records
+  b += (size_t)(MA + TT) * sizeof(int2);
+  b += (size_t)(PRUNE_HEAD_ROWS + npad / NB + npad / TT) * MA * 8;
+  b += (size_t)sweep_lazy_records(npad, m) * 16;
+  return b;
 }
 void sweep_prune_carve(void* base, int64_t npad, int64_t C, PruneState* ps) {
   char* q = reinterpret_cast<char*>(((uintptr_t)base + 255) & ~(uintptr_t)255);
@@ -868,6 +967,17 @@ void sweep_prune_carve(void* base, int64_t npad, int64_t C, PruneState* ps) {
     ps->cbuf[i] = reinterpret_cast<double*>(q);
     q += (size_t)npad * ps->ldc[i] * 8;
   }
+}
+void sweep_prune_carve_head(const PruneState& ps, int64_t npad, int64_t C, int64_t MA, int64_t m, PruneHead* ph) {
+  char* q = reinterpret_cast<char*>(ps.cbuf[1] + (size_t)npad * ps.ldc[1]);
+  ph->super = MA;
+  ph->survivors = reinterpret_cast<int2*>(q);
+  q += (size_t)(MA + TT) * sizeof(int2);
+  ph->head = reinterpret_cast<double*>(q);
+  ph->mu_part = ph->head + (size_t)PRUNE_HEAD_ROWS * MA;
+  ph->ss_part = ph->mu_part + (size_t)(npad / NB) * MA;
+  ph->rec_val = ph->ss_part + (size_t)(npad / TT) * MA;
+  ph->rec_idx = reinterpret_cast<int64_t*>(ph->rec_val + sweep_lazy_records(npad, m));
 }
 
 
@@ -888,10 +998,13 @@ bool sweep_prune_ok(const Context* c, const gpx_kernel_params& p, int npad) {
 // K* and the partial means of one chunk (launch 1 of the file comment)
 static void launch_kstar(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X, int64_t ldx,
                          const double* alpha, int nrhs, const double* Xs, int64_t ldxs, int64_t m_chunk,
-                         const SweepBuffers& b) {
+                         const SweepBuffers& b, int mode = KSTAR_FULL, const KstarAux& aux = KstarAux{},
+                         int rows = 0) {
+  if (rows == 0) rows = npad;  // (KSTAR_FULL over the leading `rows` rows only: the head phase)
   LaunchTimer tm(c, GPX_TIMER_KSTAR);
   const int64_t C = b.chunk;
-  dim3 g((unsigned)((m_chunk + WG - 1) / WG), npad / NB);
+  // (KSTAR_GATHER: m_chunk is the most columns the round can have; the kernel reads the count itself)
+  dim3 g((unsigned)((m_chunk + WG - 1) / WG), (mode == KSTAR_MU ? npad - PRUNE_HEAD_ROWS : rows) / NB);
 #define GPX_KSTAR_K(D, F, K)                                                                                     \
   (nrhs == 1 ? kstar_kernel<D, F, K, true><<<g, WG, 0, c->stream>>>(p, n, X, ldx, alpha, nrhs, Xs, ldxs, m_chunk, C, \
                                                                     b.kstar, b.mu_part)                            \
@@ -901,11 +1014,14 @@ static void launch_kstar(Context* c, const gpx_kernel_params& p, int n, int npad
   (p.kind == GPX_KERNEL_RBF        ? GPX_KSTAR_K(D, F, GPX_KERNEL_RBF)                                             \
    : p.kind == GPX_KERNEL_MATERN52 ? GPX_KSTAR_K(D, F, GPX_KERNEL_MATERN52)                                        \
                                    : GPX_KSTAR_K(D, F, GPX_KERNEL_SCALE_LINEAR_MATERN52))
+#define GPX_KSTAR_MM(D, K, R, M)                                                                                   \
+  kstar_mfma_kernel<D, K, R, M><<<g, WG, 0, c->stream>>>(p, n, X, ldx, alpha, nrhs, Xs, ldxs, m_chunk, C, b.kstar,    \
+                                                         b.mu_part, aux)
 #define GPX_KSTAR_M(D, K)                                                                                          \
-  (nrhs == 1 ? kstar_mfma_kernel<D, K, true><<<g, WG, 0, c->stream>>>(p, n, X, ldx, alpha, nrhs, Xs, ldxs, m_chunk, C, \
-                                                                      b.kstar, b.mu_part)                            \
-             : kstar_mfma_kernel<D, K, false><<<g, WG, 0, c->stream>>>(p, n, X, ldx, alpha, nrhs, Xs, ldxs, m_chunk,  \
-                                                                       C, b.kstar, b.mu_part))
+  (nrhs != 1               ? GPX_KSTAR_MM(D, K, false, KSTAR_FULL)                                                  \
+   : mode == KSTAR_FULL    ? GPX_KSTAR_MM(D, K, true, KSTAR_FULL)                                                   \
+   : mode == KSTAR_MU      ? GPX_KSTAR_MM(D, K, true, KSTAR_MU)                                                     \
+                           : GPX_KSTAR_MM(D, K, true, KSTAR_GATHER))
 #define GPX_KSTAR_MK(D)                                                                                            \
   (p.kind == GPX_KERNEL_RBF        ? GPX_KSTAR_M(D, GPX_KERNEL_RBF)                                                \
    : p.kind == GPX_KERNEL_MATERN52 ? GPX_KSTAR_M(D, GPX_KERNEL_MATERN52)                                           \
@@ -921,6 +1037,7 @@ static void launch_kstar(Context* c, const gpx_kernel_params& p, int n, int npad
     p.cov_fp32 ? GPX_KSTAR_F(32, true) : GPX_KSTAR_F(32, false);
 #undef GPX_KSTAR_MK
 #undef GPX_KSTAR_M
+#undef GPX_KSTAR_MM
 #undef GPX_KSTAR
 #undef GPX_KSTAR_F
 #undef GPX_KSTAR_K
@@ -1058,6 +1175,7 @@ hipError_t launch_sweep_chunk_pruned(Context* c, const gpx_kernel_params& p, int
   pb.ld2 = ps.ldc[1];
   pb.list0 = ps.list[0];
   pb.list1 = ps.list[1];
+  pb.list2 = nullptr;
   {
     LaunchTimer tm(c, GPX_TIMER_TRMM);
     prune_init_kernel<<<1, 64, 0, c->stream>>>(ps.desc, ps.count, ps.tau, ps.stats, col0, ncols, R[1], S == 1, first);
@@ -1105,6 +1223,176 @@ hipError_t launch_sweep_chunk_pruned(Context* c, const gpx_kernel_params& p, int
     finalize_kernel<<<blocks, WG, 0, c->stream>>>(fa, 1, Xs, ldxs, m_chunk, C, 1, nJB, nI, b.mu_part, b.ss_part,
                                                   nullptr, 0, nullptr, nullptr, b.rec_val + rec_offset + seed_blocks,
                                                   b.rec_idx + rec_offset + seed_blocks, index_offset, sel);
+  }
+  return hipGetLastError();
+}
+
+// The lazy form of the pruned sweep, for the configurations of kstar_mfma_kernel: K* is built in full only
+// for the candidates that survive the first row tile.  Per super-chunk of ph.super candidates:
+//  seed   (first super-chunk of a call) the leading PRUNE_SEED candidates through the full path: the first incumbent.
+//  head   KSTAR_FULL over the head rows and KSTAR_MU over the rest (every mean partial, K* rows 0 .. 127 only), the first
+//         stage of the product and its bound pass as one launch each; the survivors land in ph.survivors.
+//  tail   rounds of at most C survivors: KSTAR_GATHER rebuilds their full-height columns into the chunk buffer (the bits
+//         of the full build), then the staged pipeline of launch_sweep_chunk_pruned from row tile 1 on, the partials
+//         going to the columns' own places in ph.ss_part.  The host cannot know the survivor count, so the worst-case
+//         number of rounds is enqueued and the workgroups of an empty round return at once; the rounds after the first
+//         therefore take fewer, coarser stages (the stage grouping does not change a column's partials).
+// *recs: records used so far (in ph.rec_val / ph.rec_idx).
+bool sweep_lazy_ok(const gpx_kernel_params& p) { return !p.cov_fp32 && p.d <= 16; }
+
+hipError_t launch_sweep_super_pruned(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X,
+                                     int64_t ldx, const double* W, int64_t ldw, const double* alpha, const double* Xs,
+                                     int64_t ldxs, int64_t m_super, const SweepBuffers& b, const PruneState& ps,
+                                     const PruneHead& ph, const gpx_acq_params* a, int64_t* recs, int64_t index_offset,
+                                     bool first, int64_t* host_stats) {
+  const int64_t C = b.chunk, MA = ph.super;
+  const int nJB = npad / NB, nI = npad / TT;
+  int R[PRUNE_MAX_STAGES];
+  const int S = prune_stage_bounds(nI, R);  // (nI >= 3: S >= 3, R[1] = 1 = the head's row tile)
+  static_assert(PRUNE_HEAD_ROWS == TT, "the head phase is the product's first row tile");
+  const FinalizeArgs fa = finalize_args(p, a, 1, nullptr, nullptr);
+  int seed = first ? (int)(m_super < PRUNE_SEED ? m_super : PRUNE_SEED) : 0;
+  if (seed > C) seed = (int)C;
+  const int seed_blocks = (seed + WG - 1) / WG;
+  const int col0 = ((seed + TT - 1) / TT) * TT;
+  const int ncols = m_super > col0 ? (int)(m_super - col0) : 0;
+  const int tiles = (ncols + TT - 1) / TT, blocks = (ncols + WG - 1) / WG;
+  {
+    LaunchTimer tm(c, GPX_TIMER_TRMM);
+    prune_init_kernel<<<1, 64, 0, c->stream>>>(ps.desc, ps.count, ps.tau, ps.stats, col0, ncols, R[1], 0, first);
+  }
+  if (seed) {
+    launch_kstar(c, p, n, npad, X, ldx, alpha, 1, Xs, ldxs, seed, b);
+    {
+      LaunchTimer tm(c, GPX_TIMER_TRMM);
+      const int ncbt = (seed + TT - 1) / TT;
+      trmm_sumsq_kernel<<<ncbt * nI, WG, 0, c->stream>>>(W, ldw, b.kstar, C, nI, ncbt, b.ss_part, 0);
+      host_stats[1] += seed;
+      host_stats[2] += (int64_t)ncbt * nI;
+    }
+    LaunchTimer tm(c, GPX_TIMER_ACQ);
+    PruneSel sel{};
+    sel.tau = ps.tau;
+    finalize_kernel<<<seed_blocks, WG, 0, c->stream>>>(fa, 1, Xs, ldxs, seed, C, 1, nJB, nI, b.mu_part, b.ss_part,
+                                                       nullptr, 0, nullptr, nullptr, ph.rec_val + *recs,
+                                                       ph.rec_idx + *recs, index_offset, sel);
+    *recs += seed_blocks;
+  }
+  if (ncols == 0) return hipGetLastError();
+  // head: the columns of the whole super-chunk (the seed block's again: the head kernel has no column offset)
+  {
+    SweepBuffers hb = b;
+    hb.kstar = ph.head;
+    hb.mu_part = ph.mu_part;
+    hb.chunk = MA;
+    KstarAux aux{};
+    aux.jb0 = PRUNE_HEAD_ROWS / NB;
+    launch_kstar(c, p, n, npad, X, ldx, alpha, 1, Xs, ldxs, m_super, hb, KSTAR_FULL, KstarAux{}, PRUNE_HEAD_ROWS);
+    launch_kstar(c, p, n, npad, X, ldx, alpha, 1, Xs, ldxs, m_super, hb, KSTAR_MU, aux);
+  }
+  PruneBufs pb;
+  pb.kstar = ph.head;
+  pb.c1 = ps.cbuf[0];
+  pb.c2 = ps.cbuf[1];
+  pb.ld0 = MA;
+  pb.ld1 = ps.ldc[0];
+  pb.ld2 = ps.ldc[1];
+  pb.list0 = ps.list[0];
+  pb.list1 = ps.list[1];
+  pb.list2 = nullptr;
+  PruneSel sel{};
+  sel.tau = ps.tau;
+  {
+    LaunchTimer tm(c, GPX_TIMER_TRMM);
+    const PruneStage st{pb, ps.desc, 0, R[1]};
+    trmm_stage_kernel<<<tiles * st.nrows, WG, 0, c->stream>>>(W, ldw, MA, nI, ph.ss_part, st);
+    sel.desc = ps.desc;
+    sel.count = ps.count;
+    sel.list0 = ph.survivors;  // (the descriptor's list is -1: the survivors go to list0)
+    sel.list1 = nullptr;
+    finalize_kernel<<<blocks, WG, 0, c->stream>>>(fa, 4, Xs, ldxs, m_super, MA, 1, nJB, R[1], ph.mu_part, ph.ss_part,
+                                                  nullptr, 0, nullptr, nullptr, nullptr, nullptr, index_offset, sel);
+  }
+  // tail
+  pb.kstar = b.kstar;
+  pb.ld0 = C;
+  sel.list0 = ps.list[0];
+  sel.list1 = ps.list[1];
+  constexpr int ROWS = 32;  // K* rows a compaction workgroup copies
+  for (int64_t r0 = 0; r0 < ncols; r0 += C) {
+    const int cap = (int)(ncols - r0 < C ? ncols - r0 : C);  // the most columns this round can have
+    // stage boundaries Rr[0] = 1 < .. < Rr[ns] = nI: round 0 the doubling ones, later rounds 1 < 4 < nI
+    int Rr[PRUNE_MAX_STAGES], ns = 0;
+    if (r0 == 0) {
+      for (int s = 1; s <= S; ++s) Rr[s - 1] = R[s];
+      ns = S - 1;
+    } else {
+      Rr[0] = 1;
+      if (nI > 4) Rr[++ns] = 4;
+      Rr[++ns] = nI;
+    }
+    KstarAux aux{};
+    aux.list = reinterpret_cast<const int*>(ph.survivors);
+    aux.lstride = 2;
+    aux.count = ps.count;
+    aux.first = (int)r0;
+    aux.cap = cap;
+    aux.pad = reinterpret_cast<int*>(ph.survivors);
+    aux.desc = ps.desc + 1;
+    aux.rcount = ps.count + 1;
+    aux.stats = ps.stats;
+    aux.rows0 = Rr[1] - Rr[0];
+    aux.last = ns == 1;
+    launch_kstar(c, p, n, npad, X, ldx, alpha, 1, Xs, ldxs, cap, b, KSTAR_GATHER, aux);
+    pb.list2 = sel.list2 = ph.survivors + r0;
+    const int rtiles = (cap + TT - 1) / TT, rblocks = (cap + WG - 1) / WG;
+    {
+      LaunchTimer tm(c, GPX_TIMER_TRMM);
+      const dim3 gc((cap / 2 + TT + WG - 1) / WG, npad / ROWS);
+      for (int s = 0; s < ns; ++s) {
+        const PruneStage st{pb, ps.desc + 1 + s, Rr[s], Rr[s + 1] - Rr[s]};
+        trmm_stage_kernel<<<rtiles * st.nrows, WG, 0, c->stream>>>(W, ldw, MA, nI, ph.ss_part, st);
+        if (s == ns - 1) break;
+        sel.desc = ps.desc + 1 + s;
+        sel.count = ps.count + 1 + s;
+        finalize_kernel<<<rblocks, WG, 0, c->stream>>>(fa, 4, Xs, ldxs, m_super, MA, 1, nJB, Rr[s + 1], ph.mu_part,
+                                                       ph.ss_part, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
+                                                       index_offset, sel);
+        prune_compact_kernel<<<gc, WG, 0, c->stream>>>(pb, ps.desc + 1 + s, ps.desc + 2 + s, ps.count + 1 + s, ROWS,
+                                                       Rr[s + 2] - Rr[s + 1], s + 2 == ns, ps.stats);
+      }
+    }
+    LaunchTimer tm(c, GPX_TIMER_ACQ);
+    sel.desc = ps.desc + ns;
+    sel.count = nullptr;
+    finalize_kernel<<<rblocks, WG, 0, c->stream>>>(fa, 1, Xs, ldxs, m_super, MA, 1, nJB, nI, ph.mu_part, ph.ss_part,
+                                                   nullptr, 0, nullptr, nullptr, ph.rec_val + *recs,
+                                                   ph.rec_idx + *recs, index_offset, sel);
+    *recs += rblocks;
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_debug_kstar(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X, int64_t ldx,
+                              const double* Xs, int64_t ldxs, int64_t m, const int* list, const int* count,
+                              double* out, int64_t ldout, double* mu_scratch) {
+  SweepBuffers b{};
+  b.kstar = out;
+  b.chunk = ldout;
+  b.mu_part = mu_scratch;  // (npad/64) x ldout mean partials of a zero alpha, then the zero alpha
+  if (!list) {
+    double* alpha = mu_scratch + (size_t)(npad / NB) * ldout;
+    hipError_t e = hipMemsetAsync(alpha, 0, (size_t)npad * 8, c->stream);
+    if (e != hipSuccess) return e;
+    launch_kstar(c, p, n, npad, X, ldx, alpha, 1, Xs, ldxs, m, b);
+  } else {
+    KstarAux aux{};
+    aux.list = list;
+    aux.lstride = 1;
+    aux.count = count;
+    aux.first = 0;
+    aux.cap = (int)m;
+    launch_kstar(c, p, n, npad, X, ldx, nullptr, 1, Xs, ldxs, m, b, KSTAR_GATHER, aux);  // (no mean: alpha unread)
   }
   return hipGetLastError();
 }

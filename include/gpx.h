@@ -456,6 +456,18 @@ gpx_status gpx_timing_enable(gpx_handle h, int32_t mask);
 gpx_status gpx_timing_reset(gpx_handle h);
 gpx_status gpx_timing_query(gpx_handle h, int32_t timer, double* total_ms_host, int64_t* launches_host);
 
+/* K(X, X*) through the candidate sweep's own K* build, for bit checks (no production path uses it): out (device,
+ * padded_n rows of pitch ldout >= m rounded up to 256) gets column c = K(X, Xs[c]) for c < m, rows >= n zero.  With
+ * list = NULL the full-store build (the full sweep's launch; ws of gpx_debug_kstar_workspace_size bytes for its mean
+ * partials).  With a device index list and a device count (at most m) the gather build of the pruned sweep's tail:
+ * column s = K(X, Xs[list[s]]) for s < *count, zero for a negative entry and up to the end of the last written
+ * 256-column group; columns beyond are not written; ws is not used.  The gather build covers the fp64 covariance with
+ * d <= 16.  A column has the same bits from either build.  Asynchronous on the handle's stream, no allocation. */
+gpx_status gpx_debug_kstar_workspace_size(int64_t n, int64_t ldout, size_t* bytes);
+gpx_status gpx_debug_kstar_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X, int64_t ldx,
+                               const double* Xs, int64_t m, int64_t ldxs, const int32_t* list, const int32_t* count,
+                               double* out, int64_t ldout, void* ws, size_t ws_bytes);
+
 #ifdef __cplusplus
 }
 #endif
