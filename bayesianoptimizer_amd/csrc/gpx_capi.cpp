@@ -205,7 +205,7 @@ static gpx_status set_option(Context* c, int32_t option, int64_t v) {
       c->potrf_split = (int)v;
       return GPX_OK;
     case GPX_OPT_SWEEP_PRUNE:
-      if (v < 0 || v > 2) return fail(c, GPX_INVALID_ARG, "sweep_prune must be 0, 1 or 2");
+      if (v != -2 && (v < 0 || v > 2)) return fail(c, GPX_INVALID_ARG, "sweep_prune must be 0, 1, 2 or -2");
       c->sweep_prune = (int)v;
       return GPX_OK;
     default:
@@ -1056,6 +1056,67 @@ gpx_status gpx_debug_kstar_f64(gpx_handle h, const gpx_kernel_params* p, int64_t
                    gpx::launch_debug_kstar(c, *p, (int)n, (int)npad, X, ldx, Xs, ldxs, m, list, count, out, ldout,
                                            scratch),
                    "debug_kstar");
+}
+
+gpx_status gpx_debug_kstar_mu_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X, int64_t ldx,
+                                  const double* alpha, const double* Xs, int64_t m, int64_t ldxs, const int32_t* list,
+                                  const int32_t* count, double* out, int64_t ldout, double* mu_part, int64_t ldmu) {
+  Context* c = reinterpret_cast<Context*>(h);
+  if (!c) return GPX_INVALID_ARG;
+  GPX_TRY(check_params(c, p));
+  GPX_TRY(check_n(c, n));
+  if (m < 1 || m > ((int64_t)1 << 30)) return fail(c, GPX_INVALID_ARG, "m must be in [1, 2^30]");
+  GPX_NONNULL(c, X);
+  GPX_NONNULL(c, alpha);
+  GPX_NONNULL(c, Xs);
+  GPX_NONNULL(c, out);
+  GPX_NONNULL(c, mu_part);
+  const int64_t npad = padded(n);
+  GPX_TRY(check_ld(c, ldx, p->d, "X", false));
+  GPX_TRY(check_ld(c, ldxs, p->d, "Xs", false));
+  if (ldout < (m + 255) / 256 * 256) return fail(c, GPX_INVALID_ARG, "ldout must be >= m rounded up to 256");
+  if (list && !count) return fail(c, GPX_INVALID_ARG, "count is NULL");
+  if (list && ldmu < 1) return fail(c, GPX_INVALID_ARG, "ldmu must be >= 1");
+  if (!gpx::sweep_lazy_ok(*p)) return fail(c, GPX_INVALID_ARG, "the MFMA K* build covers the fp64 covariance with d <= 16");
+  GPX_USE_DEVICE(c);
+  return hip_check(c,
+                   gpx::launch_debug_kstar(c, *p, (int)n, (int)npad, X, ldx, Xs, ldxs, m, list, count, out, ldout,
+                                           nullptr, alpha, mu_part, ldmu),
+                   "debug_kstar_mu");
+}
+
+gpx_status gpx_debug_mu_bound_workspace_size(int64_t n, size_t* bytes) {
+  if (!bytes || n < 1) return GPX_INVALID_ARG;
+  *bytes = gpx::mu_prep_doubles(padded(n), 16) * 8 + 256;
+  return GPX_OK;
+}
+
+gpx_status gpx_debug_mu_bound_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X, int64_t ldx,
+                                  const double* alpha, const double* Xs, int64_t m, int64_t ldxs, double* mu_approx,
+                                  double* mu_slack, void* ws, size_t ws_bytes) {
+  Context* c = reinterpret_cast<Context*>(h);
+  if (!c) return GPX_INVALID_ARG;
+  GPX_TRY(check_params(c, p));
+  GPX_TRY(check_n(c, n));
+  if (m < 1 || m > ((int64_t)1 << 30)) return fail(c, GPX_INVALID_ARG, "m must be in [1, 2^30]");
+  GPX_NONNULL(c, X);
+  GPX_NONNULL(c, alpha);
+  GPX_NONNULL(c, Xs);
+  GPX_NONNULL(c, mu_approx);
+  GPX_NONNULL(c, mu_slack);
+  const int64_t npad = padded(n);
+  GPX_TRY(check_ld(c, ldx, p->d, "X", false));
+  GPX_TRY(check_ld(c, ldxs, p->d, "Xs", false));
+  if (!gpx::sweep_mu_bound_ok(*p))
+    return fail(c, GPX_INVALID_ARG, "the mean bound covers the RBF kernel, the fp64 covariance and d <= 16");
+  size_t need = 0;
+  GPX_TRY(gpx_debug_mu_bound_workspace_size(n, &need));
+  if (!ws || ws_bytes < need) return fail(c, GPX_INVALID_ARG, "debug_mu_bound workspace too small");
+  GPX_USE_DEVICE(c);
+  return hip_check(c,
+                   gpx::launch_mu_bound(c, *p, (int)n, (int)npad, X, ldx, alpha, Xs, ldxs, m, align256(ws), mu_approx,
+                                        mu_slack),
+                   "debug_mu_bound");
 }
 
 gpx_status gpx_sweep_multi_workspace_size(int64_t n, int64_t m, size_t* bytes) {

@@ -40,7 +40,8 @@ struct Context {
   int potrf_mode = -1;     // multi-launch panel mode, -1 by size
   int potrf_switch = -1;   // launch at which a single fit switches schedule (gpx_potrf.hip potrf_switch), -1 by size
   int potrf_split = -1;    // panel split policy (gpx_potrf.hip step_plan): -1 fits the slots, 1 never, 3 one per CU
-  int sweep_prune = 1;     // pruned acquisition sweep: 1 where it pays, 0 never, 2 at every padded n >= 384
+  int sweep_prune = 1;     // pruned acquisition sweep: 1 where it pays, 0 never, 2 at every padded n >= 384, -2 as 2
+                           // with the lazy head's exact means instead of their bound
   // gpx_sweep_stats of the last acquire call: the host-known parts, plus the device counters of the pruned path
   // ({candidates computed to the last row tile, product tiles executed}; they live in that call's workspace)
   int64_t sweep_stats[4] = {0, 0, 0, 0};
@@ -224,7 +225,17 @@ hipError_t launch_sweep_super_pruned(Context* c, const gpx_kernel_params& p, int
 // else the gather build of columns list[0 .. *count - 1] (m: the most the list can hold).  out: npad rows of pitch ldout.
 hipError_t launch_debug_kstar(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X, int64_t ldx,
                               const double* Xs, int64_t ldxs, int64_t m, const int* list, const int* count,
-                              double* out, int64_t ldout, double* mu_scratch);
+                              double* out, int64_t ldout, double* mu_scratch, const double* alpha = nullptr,
+                              double* mu_part = nullptr, int64_t ldmu = 0);
+// (alpha != nullptr, gpx_debug_kstar_mu_f64: the build's mean partials too.  Full build: mu_part[jb * ldout + c], no
+// scratch; gather build: mu_part[jb * ldmu + list[s]], the partials KSTAR_FULL gives that candidate, other entries kept.)
+// The lazy pruned sweep's bound of the posterior mean (gpx_sweep.hip 1b; RBF, fp64 covariance, d <= 16):
+// mu_approx[c] +- mu_slack[c] holds the exact path's mean of candidate c.  prep: mu_prep_doubles(npad, d) doubles.
+bool sweep_mu_bound_ok(const gpx_kernel_params& p);
+size_t mu_prep_doubles(int64_t npad, int d);
+hipError_t launch_mu_bound(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X, int64_t ldx,
+                           const double* alpha, const double* Xs, int64_t ldxs, int64_t m_chunk, double* prep,
+                           double* mu_approx, double* mu_slack);
 hipError_t launch_multi_score(Context* c, const MultiOutput& mo, const gpx_acq_params& a, int64_t m_chunk,
                               double* scores_out, double* rec_val, int64_t* rec_idx, int64_t index_offset);
 hipError_t launch_argmax_final(Context* c, const double* vals, const int64_t* idx, int64_t count, double* best_val,

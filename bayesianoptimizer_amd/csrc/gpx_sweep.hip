@@ -196,7 +196,8 @@ __global__ void __launch_bounds__(WG) kstar_kernel(gpx_kernel_params p, int n, c
 //                over the first row blocks: the rows the first stage of the product reads).
 //  KSTAR_GATHER  the pruned sweep's tail: column s of the output is candidate list[first + s] for s below the round's
 //                column count min(*count - first, cap) (clamped at 0), zero up to the end of the workgroup's 256 columns;
-//                no mean partials; workgroups beyond the count return at once.  Workgroup (0, 0) also writes the round's
+//                mean partials only on request (aux.mu_out: KSTAR_FULL's bits, stored at the listed candidate's own
+//                place); workgroups beyond the count return at once.  Workgroup (0, 0) also writes the round's
 //                first descriptor and resets its survivor counts (read by later launches only).
 constexpr int KSTAR_FULL = 0, KSTAR_MU = 1, KSTAR_GATHER = 2;
 struct KstarAux {
@@ -210,6 +211,8 @@ struct KstarAux {
   int* rcount;       // its stages' survivor counts (PRUNE_MAX_STAGES - 1 of them)
   int64_t* stats;    // the pruned sweep's counters
   int rows0, last;   // row tiles of the round's first stage; it is also the last
+  double* mu_out;    // GATHER, optional: the listed candidates' mean partials (KSTAR_FULL's bits) go to
+  int64_t ldmu;      //   mu_out[jb * ldmu + candidate]; alpha is read only then
 };
 
 template <int DMAX, int KIND, bool ONE_RHS, int MODE>
@@ -273,6 +276,8 @@ __global__ void __launch_bounds__(WG) kstar_mfma_kernel(gpx_kernel_params p, int
       const int r = e / NRQ, q = e % NRQ;
       sal[r][q] = (q < nrhs && j0 + r < n) ? alpha[(int64_t)(j0 + r) * nrhs + q] : 0.0;
     }
+  } else {
+    if (t < NB) sal[t][0] = (aux.mu_out && j0 + t < n) ? alpha[j0 + t] : 0.0;
   }
   __syncthreads();
   if (t < DMAX) {
@@ -331,10 +336,8 @@ __global__ void __launch_bounds__(WG) kstar_mfma_kernel(gpx_kernel_params p, int
         else
           v = j < nv ? v : 0.0;
         kv[r][cb] = v;
-        if constexpr (!gather) {
 #pragma unroll
-          for (int q = 0; q < NRQ; ++q) mu[cb][q] = fma(sal[j][q], v, mu[cb][q]);
-        }
+        for (int q = 0; q < NRQ; ++q) mu[cb][q] = fma(sal[j][q], v, mu[cb][q]);
       }
     }
     // after the transpose, register q of 16-lane row g holds row rs + q + 4 r, candidate 64 w + 16 g + m
@@ -347,7 +350,19 @@ __global__ void __launch_bounds__(WG) kstar_mfma_kernel(gpx_kernel_params p, int
       }
     }
   }
-  if constexpr (gather) return;
+  if constexpr (gather) {
+    // the survivors' exact mean partials, at the candidates' own places (the head bounded their means only)
+    if (!aux.mu_out) return;
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) {
+      double v = mu[cb][0];
+      v += __shfl_xor(v, 16);
+      v += __shfl_xor(v, 32);
+      const int sc = sidx[64 * w + 16 * cb + m];
+      if (kq == 0 && sc >= 0) aux.mu_out[(int64_t)jb * aux.ldmu + sc] = v;
+    }
+    return;
+  }
 #pragma unroll
   for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
@@ -357,6 +372,187 @@ __global__ void __launch_bounds__(WG) kstar_mfma_kernel(gpx_kernel_params p, int
       v += __shfl_xor(v, 32);
       if (kq == 0 && q < nrhs) mu_part[((int64_t)jb * nrhs + q) * C + c0 + 64 * w + 16 * cb + m] = v;
     }
+}
+
+// ---- 1b. the head phase's bound of the posterior mean (RBF, fp64, d <= 16, one right-hand side) --------
+// The pruned sweep's head needs the mean of every candidate only to bound its score from above, and every acquisition of
+// the ABI is non-decreasing in the mean.  mu_bound_kernel gives, per candidate, mu_approx and mu_slack with
+//     mu_approx - mu_slack <= mu <= mu_approx + mu_slack,
+// mu being the value the exact path computes (sum_partials over the mean partials of KSTAR_FULL), at about a third of
+// the exact build's instructions per entry: the exponential is v_exp_f32 with a first-order correction.
+//
+// Proof.  r2_j has the bits of the exact build's: same v / lengthscale, same centring by the mean of the row block's
+// valid rows (mu_prep_kernel runs kstar_mfma_kernel's prologue once per row block), same MFMA sequence, same
+// sqdist_expanded.  So with E_j = the exact path's exp(-r2_j / 2) and k_j = fl(outputscale * E_j) its K* entry,
+// the two means differ by the exponential and by the summation only.
+//  (a) exponential.  y = fl(r2 * (-log2(e) / 2)), yf = the fp32 nearest y, e = v_exp_f32(yf), rem = y - yf (exact in
+//      fp64), e~ = fl(e + fl(e * rem) * ln 2).  2^y = 2^yf * 2^rem and 2^rem = 1 + rem ln 2 + O(rem^2) with |rem| <=
+//      2^-24 |y| <= 2^-13.9 over the range where 2^y is not flushed (|y| < 127), so the second-order term is below 2^-29;
+//      the roundings of y (|y| 2^-53 ln 2 relative), of the constant, of the two fp64 operations and the error of E_j
+//      itself (1 ulp of fp64) are below 2^-40 together.  What is left is the instruction's error, documented as 1 ulp
+//      (2^-23 relative), and its flush of results below 2^-126 to zero.  Hence
+//          |e~ - E| <= eps1 e~ + eps2,    eps1 = MUB_EPS1 = 2^-20,  eps2 = MUB_EPS2 = 2^-120,
+//      each constant at least 4 x the largest error measured over 2^22 arguments in [-760, 0] and every fp32 argument of
+//      three binades (tests/test_gpu_sweep_mubound.py: at most 0.089 of eps1 e~ + eps2, 2^-23.5 relative).
+//      NaN r2 gives NaN; r2 = +inf gives y = yf = -inf, e = 0, rem = NaN replaced by 1 (fmin), e~ = 0.
+//  (b) sums.  The kernel forms S = sum_j alpha_j e~_j and A = sum_j |alpha_j| e~_j by fp64 FMAs, every term passing at
+//      most npad / 4 + 2 additions: |S - sum alpha e~| <= (npad / 4 + 2) u A' with u = 2^-53 and A' = sum |alpha| e~ (exact),
+//      A >= A' (1 - (npad / 4 + 2) u).  The exact path: |mu - sum alpha k| <= (npad / 64 + 18) u sum |alpha| k (16 FMAs and
+//      two shuffles per partial, then sum_partials), and |k - outputscale E| <= u outputscale E.
+//  (c) together, with mu_approx = fl(outputscale S):
+//          |mu_approx - mu| <= outputscale (eps1 A' + eps2 |alpha|_1) + (npad / 4 + npad / 64 + 23) u outputscale (1 + eps1) A'
+//                              + (npad / 64 + 19) u outputscale eps2 |alpha|_1
+//      which lies below mu_slack = (eps1 A~ + eps2 outputscale |alpha|_1 + (n + 64) 2^-52 A~) (1 + 2^-30), A~ =
+//      fl(outputscale A): (n + 64) 2^-52 = 2 (n + 64) u is more than twice the factor in front of u above (npad < n +
+//      128), and the factor 1 + 2^-30 covers A~ against outputscale A', the last line's term ((npad / 64 + 19) u < 2^-30)
+//      and the roundings of the slack's own operations.  Padded rows have alpha = 0: their terms are exact zeros (e~ is finite for a finite candidate).  With
+//      alpha = 0 everywhere S = A = 0 and the slack is exactly 0.
+//  (d) the head's bound pass scores mu_approx + mu_slack.  The rounded sum can fall below the real one by u |sum|; since
+//      mu_slack >= eps1 |mu_approx|, the 2^-30 in (c) covers that too.  The y transform is monotone under rounding, and
+//      acq_score's own rounding is what PRUNE_EPS is for, as with the variance bound.
+constexpr double MUB_EPS1 = 0x1p-20, MUB_EPS2 = 0x1p-120;
+
+__device__ __forceinline__ double exp_half_neg_fast(double r2) {  // ~ exp(-r2 / 2), r2 >= 0 (or NaN)
+  const double y = r2 * -0.72134752044448170367996234050095;  // -log2(e) / 2
+  const float yf = (float)y;
+  const double e = (double)__builtin_amdgcn_exp2f(yf);
+  const double rem = fmin(y - (double)yf, 1.0);  // (y = -inf: NaN -> 1 with e = 0)
+  return fma(e * rem, 0.69314718055994530941723212145818, e);
+}
+
+// Per row block of 64 training rows: kstar_mfma_kernel's prologue (scaled rows, centre = mean of the valid rows, centred
+// rows, their norms), alpha with zeros for the padded rows, and sum |alpha| of the block.  Layout of a block's record:
+template <int DMAX>
+struct MuPrep {
+  static constexpr int ROWS = 0, NA = NB * DMAX, AL = NA + NB, CEN = AL + NB, L1 = CEN + DMAX, STRIDE = L1 + 2;
+};
+size_t mu_prep_doubles(int64_t npad, int d) {
+  const int D = d <= 4 ? 4 : d <= 8 ? 8 : 16;
+  return (size_t)(npad / NB) * (NB * D + 2 * NB + D + 2);
+}
+
+template <int DMAX>
+__global__ void __launch_bounds__(WG) mu_prep_kernel(gpx_kernel_params p, int n, const double* __restrict__ X,
+                                                     int64_t ldx, const double* __restrict__ alpha,
+                                                     double* __restrict__ prep) {
+  using P = MuPrep<DMAX>;
+  __shared__ double sa[NB][DMAX + 1], cen[DMAX];
+  const int jb = blockIdx.x, j0 = jb * NB, d = p.d, t = threadIdx.x;
+  const int nv = n - j0 < NB ? n - j0 : NB;
+  double* out = prep + (int64_t)jb * P::STRIDE;
+  for (int e = t; e < NB * DMAX; e += WG) {
+    const int r = e / DMAX, k = e % DMAX;
+    const double v = (k < d && j0 + r < n) ? X[(int64_t)(j0 + r) * ldx + k] : 0.0;
+    sa[r][k] = (k < d) ? v / p.lengthscale[k] : 0.0;
+  }
+  __syncthreads();
+  if (t < DMAX) {
+    double s = 0.0;
+    for (int r = 0; r < nv; ++r) s += sa[r][t];
+    cen[t] = nv > 0 ? s / nv : 0.0;
+  }
+  __syncthreads();
+  for (int e = t; e < NB * DMAX; e += WG) sa[e / DMAX][e % DMAX] -= cen[e % DMAX];
+  __syncthreads();
+  for (int e = t; e < NB * DMAX; e += WG) out[P::ROWS + e] = sa[e / DMAX][e % DMAX];
+  if (t < NB) {
+    double u = 0.0;
+#pragma unroll
+    for (int k = 0; k < DMAX; ++k) u = fma(sa[t][k], sa[t][k], u);
+    out[P::NA + t] = u;
+    out[P::AL + t] = j0 + t < n ? alpha[j0 + t] : 0.0;
+  }
+  if (t < DMAX) out[P::CEN + t] = cen[t];
+  if (t == 0) {
+    double s = 0.0;
+    for (int r = 0; r < nv; ++r) s += fabs(alpha[j0 + r]);
+    out[P::L1] = s;
+  }
+}
+
+// Workgroup x: candidates 256 x .. 256 x + 255 against every row block.  The candidate tile is loaded and divided once
+// (a thread keeps its own candidate's scaled coordinates in registers); per row block it is centred and its norms are
+// taken (the bits of kstar_mfma_kernel's), then kstar_mfma_kernel's MFMA sequence and the fast exponential.
+template <int DMAX>
+__global__ void __launch_bounds__(WG) mu_bound_kernel(gpx_kernel_params p, int n, const double* __restrict__ prep,
+                                                      const double* __restrict__ Xs, int64_t ldxs, int64_t m_chunk,
+                                                      double* __restrict__ mu_approx, double* __restrict__ mu_slack) {
+  using P = MuPrep<DMAX>;
+  constexpr int KS = DMAX / 4;
+  __shared__ double sa[NB][DMAX + 1], sb[WG][DMAX + 1], na[NB], nb[WG], sal[NB];
+  const int d = p.d, t = threadIdx.x;
+  const int64_t c0 = (int64_t)blockIdx.x * WG;
+  const int nblk = (n + NB - 1) / NB;  // row blocks with a valid row
+  double xb[DMAX];
+#pragma unroll
+  for (int k = 0; k < DMAX; ++k) {
+    const double v = (k < d && c0 + t < m_chunk) ? Xs[(c0 + t) * ldxs + k] : 0.0;
+    xb[k] = (k < d) ? v / p.lengthscale[k] : 0.0;
+  }
+  const int lane = t & 63, w = t >> 6, m = lane & 15, kq = lane >> 4;
+  double S[4] = {0.0, 0.0, 0.0, 0.0}, A[4] = {0.0, 0.0, 0.0, 0.0}, l1 = 0.0;
+#pragma unroll 1
+  for (int jb = 0; jb < nblk; ++jb) {
+    const double* __restrict__ in = prep + (int64_t)jb * P::STRIDE;
+    __syncthreads();  // (the previous block's reads)
+    for (int e = t; e < NB * DMAX; e += WG) sa[e / DMAX][e % DMAX] = in[P::ROWS + e];
+    if (t < NB) {
+      na[t] = in[P::NA + t];
+      sal[t] = in[P::AL + t];
+    }
+    l1 += in[P::L1];
+    {
+      double v = 0.0;
+#pragma unroll
+      for (int k = 0; k < DMAX; ++k) {
+        const double s = xb[k] - in[P::CEN + k];
+        sb[t][k] = s;
+        v = fma(s, s, v);
+      }
+      nb[t] = v;
+    }
+    __syncthreads();
+    double nbc[4];
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) nbc[cb] = nb[64 * w + 16 * cb + m];
+#pragma unroll 1
+    for (int rs = 0; rs < NB; rs += 16) {
+      d4 acc[4];
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb) {
+        acc[cb] = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int k = 0; k < KS; ++k)
+          acc[cb] = mfma16x16x4(sa[rs + m][4 * k + kq], sb[64 * w + 16 * cb + m][4 * k + kq], acc[cb]);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int j = rs + kq + 4 * r;
+        const double naj = na[j], al = sal[j];
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb) {
+          const double e = exp_half_neg_fast(sqdist_expanded(naj, nbc[cb], acc[cb][r]));
+          S[cb] = fma(al, e, S[cb]);
+          A[cb] = fma(fabs(al), e, A[cb]);
+        }
+      }
+    }
+  }
+  const double os = fabs(p.outputscale);
+#pragma unroll
+  for (int cb = 0; cb < 4; ++cb) {
+    double s = S[cb], a = A[cb];
+    s += __shfl_xor(s, 16);
+    s += __shfl_xor(s, 32);
+    a += __shfl_xor(a, 16);
+    a += __shfl_xor(a, 32);
+    const int64_t c = c0 + 64 * w + 16 * cb + m;
+    if (kq == 0 && c < m_chunk) {
+      const double at = os * a;
+      mu_approx[c] = p.outputscale * s;
+      mu_slack[c] = (MUB_EPS1 * at + MUB_EPS2 * os * l1 + ((double)(n + 64) * 0x1p-52) * at) * (1.0 + 0x1p-30);
+    }
+  }
 }
 
 // ---- 2. triangular product + column sums of squares ------------------------------------------------------
@@ -671,6 +867,8 @@ struct PruneSel {
   int* count;
   unsigned long long* tau;
   const int2* list2;  // read only (PruneDesc::list = 2); its survivors go to list0
+  const double* mu_bound;  // mode 4, the lazy head's pass: mu_approx at [c], mu_slack at [C + c] (mu_bound_kernel) stand
+                           // in for the mean partials
 };
 constexpr double PRUNE_EPS = 1e-9;  // margin of the bound test over acq_score's rounding
 
@@ -729,7 +927,8 @@ __global__ void __launch_bounds__(WG) finalize_kernel(FinalizeArgs fa, int mode,
         var_out[c] = fmax(var * (fa.y_scale[0] * fa.y_scale[0]), 1e-12);  // BoTorch min_var [upstream]
         return;
       }
-      mu = sum_partials(mu_part + c, nJB, C);
+      // (mode 4 with a mean bound: the score is non-decreasing in the mean too, so its upper end bounds the score)
+      mu = (mode == 4 && ps.mu_bound) ? ps.mu_bound[c] + ps.mu_bound[C + c] : sum_partials(mu_part + c, nJB, C);
       mu = fa.y_mean[0] + fa.y_scale[0] * (mu + p.const_mean);
       var = var * (fa.y_scale[0] * fa.y_scale[0]);
       if (mode == 2) {
@@ -992,7 +1191,7 @@ bool sweep_fused_ok(const Context* c, const gpx_kernel_params& p, int npad, int 
 
 bool sweep_prune_ok(const Context* c, const gpx_kernel_params& p, int npad) {
   if (c->sweep_prune == 0 || sweep_fused_ok(c, p, npad, 1)) return false;
-  return npad >= (c->sweep_prune == 2 ? PRUNE_MIN_NPAD : PRUNE_DEFAULT_NPAD);
+  return npad >= (c->sweep_prune != 1 ? PRUNE_MIN_NPAD : PRUNE_DEFAULT_NPAD);  // (-2: forced, exact head means)
 }
 
 // K* and the partial means of one chunk (launch 1 of the file comment)
@@ -1041,6 +1240,28 @@ static void launch_kstar(Context* c, const gpx_kernel_params& p, int n, int npad
 #undef GPX_KSTAR
 #undef GPX_KSTAR_F
 #undef GPX_KSTAR_K
+}
+
+// The head phase's mean bound of m_chunk candidates (mu_prep_kernel + mu_bound_kernel); prep: mu_prep_doubles(npad, d)
+// doubles of scratch.
+bool sweep_mu_bound_ok(const gpx_kernel_params& p) { return p.kind == GPX_KERNEL_RBF && !p.cov_fp32 && p.d <= 16; }
+
+hipError_t launch_mu_bound(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X, int64_t ldx,
+                           const double* alpha, const double* Xs, int64_t ldxs, int64_t m_chunk, double* prep,
+                           double* mu_approx, double* mu_slack) {
+  LaunchTimer tm(c, GPX_TIMER_KSTAR);
+  const unsigned nwg = (unsigned)((m_chunk + WG - 1) / WG);
+#define GPX_MU_BOUND(D)                                                                                            \
+  (mu_prep_kernel<D><<<npad / NB, WG, 0, c->stream>>>(p, n, X, ldx, alpha, prep),                                   \
+   mu_bound_kernel<D><<<nwg, WG, 0, c->stream>>>(p, n, prep, Xs, ldxs, m_chunk, mu_approx, mu_slack))
+  if (p.d <= 4)
+    GPX_MU_BOUND(4);
+  else if (p.d <= 8)
+    GPX_MU_BOUND(8);
+  else
+    GPX_MU_BOUND(16);
+#undef GPX_MU_BOUND
+  return hipGetLastError();
 }
 
 // finalize_kernel's arguments of a posterior (a = nullptr: per-output y_mean / y_scale, nullptr = identity) or of an
@@ -1230,10 +1451,12 @@ hipError_t launch_sweep_chunk_pruned(Context* c, const gpx_kernel_params& p, int
 // The lazy form of the pruned sweep, for the configurations of kstar_mfma_kernel: K* is built in full only
 // for the candidates that survive the first row tile.  Per super-chunk of ph.super candidates:
 //  seed   (first super-chunk of a call) the leading PRUNE_SEED candidates through the full path: the first incumbent.
-//  head   KSTAR_FULL over the head rows and KSTAR_MU over the rest (every mean partial, K* rows 0 .. 127 only), the first
-//         stage of the product and its bound pass as one launch each; the survivors land in ph.survivors.
+//  head   KSTAR_FULL over the head rows (K* rows 0 .. 127), then the mean of every candidate: for the RBF kernel its bound
+//         (mu_bound_kernel, 1b; the bound pass scores its upper end), else or with sweep_prune = -2 KSTAR_MU over the other
+//         row blocks (every mean partial); the first stage of the product and its bound pass as one launch each; the
+//         survivors land in ph.survivors.
 //  tail   rounds of at most C survivors: KSTAR_GATHER rebuilds their full-height columns into the chunk buffer (the bits
-//         of the full build), then the staged pipeline of launch_sweep_chunk_pruned from row tile 1 on, the partials
+//         of the full build) and, after a mean bound, their exact mean partials into ph.mu_part, then the staged pipeline of launch_sweep_chunk_pruned from row tile 1 on, the partials
 //         going to the columns' own places in ph.ss_part.  The host cannot know the survivor count, so the worst-case
 //         number of rounds is enqueued and the workgroups of an empty round return at once; the rounds after the first
 //         therefore take fewer, coarser stages (the stage grouping does not change a column's partials).
@@ -1245,6 +1468,7 @@ hipError_t launch_sweep_super_pruned(Context* c, const gpx_kernel_params& p, int
                                      int64_t ldxs, int64_t m_super, const SweepBuffers& b, const PruneState& ps,
                                      const PruneHead& ph, const gpx_acq_params* a, int64_t* recs, int64_t index_offset,
                                      bool first, int64_t* host_stats) {
+  const bool mu_bound = c->sweep_prune != -2 && sweep_mu_bound_ok(p);
   const int64_t C = b.chunk, MA = ph.super;
   const int nJB = npad / NB, nI = npad / TT;
   int R[PRUNE_MAX_STAGES];
@@ -1288,7 +1512,17 @@ hipError_t launch_sweep_super_pruned(Context* c, const gpx_kernel_params& p, int
     KstarAux aux{};
     aux.jb0 = PRUNE_HEAD_ROWS / NB;
     launch_kstar(c, p, n, npad, X, ldx, alpha, 1, Xs, ldxs, m_super, hb, KSTAR_FULL, KstarAux{}, PRUNE_HEAD_ROWS);
-    launch_kstar(c, p, n, npad, X, ldx, alpha, 1, Xs, ldxs, m_super, hb, KSTAR_MU, aux);
+    if (mu_bound) {
+      // the mean's bound instead of the mean.  Its two values per candidate go to the mean partials' rows of blocks 2
+      // and 3 (the head rows' launch wrote blocks 0 and 1; nothing writes the others before the gather), the row
+      // blocks' records to the chunk's K* buffer, idle between the seed block's scoring and the first gather
+      // (mu_prep_doubles <= 19 npad doubles, the buffer holds npad x C >= 256 npad).
+      static_assert(PRUNE_MIN_NPAD / NB >= 4, "mean partial rows 2 and 3 exist");
+      (void)launch_mu_bound(c, p, n, npad, X, ldx, alpha, Xs, ldxs, m_super, b.kstar, ph.mu_part + 2 * MA,
+                            ph.mu_part + 3 * MA);  // (the launch error is read at the end)
+    } else {
+      launch_kstar(c, p, n, npad, X, ldx, alpha, 1, Xs, ldxs, m_super, hb, KSTAR_MU, aux);
+    }
   }
   PruneBufs pb;
   pb.kstar = ph.head;
@@ -1310,8 +1544,10 @@ hipError_t launch_sweep_super_pruned(Context* c, const gpx_kernel_params& p, int
     sel.count = ps.count;
     sel.list0 = ph.survivors;  // (the descriptor's list is -1: the survivors go to list0)
     sel.list1 = nullptr;
+    sel.mu_bound = mu_bound ? ph.mu_part + 2 * MA : nullptr;
     finalize_kernel<<<blocks, WG, 0, c->stream>>>(fa, 4, Xs, ldxs, m_super, MA, 1, nJB, R[1], ph.mu_part, ph.ss_part,
                                                   nullptr, 0, nullptr, nullptr, nullptr, nullptr, index_offset, sel);
+    sel.mu_bound = nullptr;  // (the tail's passes read the survivors' exact partials, written by their gather)
   }
   // tail
   pb.kstar = b.kstar;
@@ -1343,6 +1579,8 @@ hipError_t launch_sweep_super_pruned(Context* c, const gpx_kernel_params& p, int
     aux.stats = ps.stats;
     aux.rows0 = Rr[1] - Rr[0];
     aux.last = ns == 1;
+    aux.mu_out = mu_bound ? ph.mu_part : nullptr;
+    aux.ldmu = MA;
     launch_kstar(c, p, n, npad, X, ldx, alpha, 1, Xs, ldxs, cap, b, KSTAR_GATHER, aux);
     pb.list2 = sel.list2 = ph.survivors + r0;
     const int rtiles = (cap + TT - 1) / TT, rblocks = (cap + WG - 1) / WG;
@@ -1375,16 +1613,30 @@ hipError_t launch_sweep_super_pruned(Context* c, const gpx_kernel_params& p, int
 
 hipError_t launch_debug_kstar(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X, int64_t ldx,
                               const double* Xs, int64_t ldxs, int64_t m, const int* list, const int* count,
-                              double* out, int64_t ldout, double* mu_scratch) {
+                              double* out, int64_t ldout, double* mu_scratch, const double* alpha_in,
+                              double* mu_part, int64_t ldmu) {
   SweepBuffers b{};
   b.kstar = out;
   b.chunk = ldout;
   b.mu_part = mu_scratch;  // (npad/64) x ldout mean partials of a zero alpha, then the zero alpha
-  if (!list) {
+  if (!list && alpha_in) {  // the full build's own mean partials (pitch ldout)
+    b.mu_part = mu_part;
+    launch_kstar(c, p, n, npad, X, ldx, alpha_in, 1, Xs, ldxs, m, b);
+  } else if (!list) {
     double* alpha = mu_scratch + (size_t)(npad / NB) * ldout;
     hipError_t e = hipMemsetAsync(alpha, 0, (size_t)npad * 8, c->stream);
     if (e != hipSuccess) return e;
     launch_kstar(c, p, n, npad, X, ldx, alpha, 1, Xs, ldxs, m, b);
+  } else if (alpha_in) {  // the gather build scatters the listed candidates' partials to mu_part[jb * ldmu + list[s]]
+    KstarAux aux{};
+    aux.list = list;
+    aux.lstride = 1;
+    aux.count = count;
+    aux.first = 0;
+    aux.cap = (int)m;
+    aux.mu_out = mu_part;
+    aux.ldmu = ldmu;
+    launch_kstar(c, p, n, npad, X, ldx, alpha_in, 1, Xs, ldxs, m, b, KSTAR_GATHER, aux);
   } else {
     KstarAux aux{};
     aux.list = list;

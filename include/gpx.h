@@ -153,7 +153,9 @@ size_t gpx_acq_params_size(void);
  *  GPX_OPT_POTRF_SPLIT     panel row blocks per workgroup: -1 (default) split in 2 where the launch still fits the
  *                          co-resident slots, 1 never split, 3 split only where the split launch fits one workgroup per CU
  *  GPX_OPT_SWEEP_PRUNE     gpx_acquire_argmax_f64 without scores_out on the K* + trmm path: 1 (default) the pruned sweep
- *                          from padded n 384 on, 0 the full sweep, 2 the pruned sweep at every padded n >= 384 (tests).
+ *                          from padded n 384 on, 0 the full sweep, 2 the pruned sweep at every padded n >= 384 (tests),
+ *                          -2 as 2 but the lazy form's head phase computes every candidate's exact mean instead of the
+ *                          bound of it that 1 and 2 take for the RBF kernel (A/B measurements, tests; 3 is not a value).
  *                          The returned (value, index) pair has the same bits either way. */
 enum {
   GPX_OPT_RESERVED_0 = 0,
@@ -467,6 +469,20 @@ gpx_status gpx_debug_kstar_workspace_size(int64_t n, int64_t ldout, size_t* byte
 gpx_status gpx_debug_kstar_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X, int64_t ldx,
                                const double* Xs, int64_t m, int64_t ldxs, const int32_t* list, const int32_t* count,
                                double* out, int64_t ldout, void* ws, size_t ws_bytes);
+/* The same builds with a device alpha (n values), returning their mean partials too (fp64 covariance, d <= 16).  Full
+ * build (list = NULL): mu_part[jb * ldout + c] = sum over the 64 rows of block jb of alpha_j K(x_j, Xs[c]); the sweep's
+ * mean is their sum over jb in ascending order.  Gather build: the partials of the listed candidates go to
+ * mu_part[jb * ldmu + list[s]] (ldmu > every list entry) with the bits of the full build's; no other entry is written. */
+gpx_status gpx_debug_kstar_mu_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X, int64_t ldx,
+                                  const double* alpha, const double* Xs, int64_t m, int64_t ldxs, const int32_t* list,
+                                  const int32_t* count, double* out, int64_t ldout, double* mu_part, int64_t ldmu);
+/* The pruned sweep's bound of the posterior mean, through the production kernel (RBF, fp64 covariance, d <= 16; DESIGN
+ * §3): mu_approx[c] - mu_slack[c] <= mu_c <= mu_approx[c] + mu_slack[c] for c < m, mu_c being the mean the full build's
+ * partials sum to (without the constant mean).  ws: gpx_debug_mu_bound_workspace_size bytes. */
+gpx_status gpx_debug_mu_bound_workspace_size(int64_t n, size_t* bytes);
+gpx_status gpx_debug_mu_bound_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X, int64_t ldx,
+                                  const double* alpha, const double* Xs, int64_t m, int64_t ldxs, double* mu_approx,
+                                  double* mu_slack, void* ws, size_t ws_bytes);
 
 #ifdef __cplusplus
 }
