@@ -230,7 +230,8 @@ hipError_t launch_debug_kstar(Context* c, const gpx_kernel_params& p, int n, int
 // (alpha != nullptr, gpx_debug_kstar_mu_f64: the build's mean partials too.  Full build: mu_part[jb * ldout + c], no
 // scratch; gather build: mu_part[jb * ldmu + list[s]], the partials KSTAR_FULL gives that candidate, other entries kept.)
 // The lazy pruned sweep's bound of the posterior mean (gpx_sweep.hip 1b; RBF, fp64 covariance, d <= 16):
-// mu_approx[c] +- mu_slack[c] holds the exact path's mean of candidate c.  prep: mu_prep_doubles(npad, d) doubles.
+// mu_approx[c] +- mu_slack[c] holds the exact path's mean of candidate c.  prep: mu_prep_doubles(npad, d) doubles,
+// 256-byte aligned; its first int64 ends up as the count of 256-candidate workgroups on the unfactorised path.
 bool sweep_mu_bound_ok(const gpx_kernel_params& p);
 size_t mu_prep_doubles(int64_t npad, int d);
 hipError_t launch_mu_bound(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X, int64_t ldx,

@@ -420,26 +420,209 @@ __device__ __forceinline__ double exp_half_neg_fast(double r2) {  // ~ exp(-r2 /
   return fma(e * rem, 0.69314718055994530941723212145818, e);
 }
 
+// The factorised form (mu_fact_kernel).  With one centre c for every row block (the mean of the valid scaled
+// rows), a_j = x_j / l - c and b = x* / l - c,
+//     exp(-r2_j / 2) = exp(-|a_j|^2 / 2) exp(-|b|^2 / 2) exp(a_j . b):
+// the row factor goes into alpha once per row (alpha'_j = alpha_j exp(-|a_j|^2 / 2), fp64, mu_prep_kernel), the candidate
+// factor G = exp(-|b|^2 / 2) is applied once per candidate, and an entry costs v_cvt_f32_f64, v_exp_f32 and two v_fma_f32:
+// the rows' fragments carry log2(e), so the MFMA sequence gives y = log2(e) a_j . b, e = v_exp_f32(fl32(y)),
+// S += alpha"_j e, A += |alpha"_j| e in fp32 over the 16 rows a lane holds of a row block, the runs added in fp64.
+// alpha" = fl32(alpha' / 2^k), 2^k >= max |alpha'| (exact scaling; |alpha"| <= 1, a run stays below 2^20).
+//     mu_approx = outputscale 2^k S G,   A~ = |outputscale| 2^k A G.
+// A workgroup takes this form only if every candidate c of it has
+//     Y_c = log2(e) sqrt(M2 |b|^2) (1 + 2^-40) <= MUF_Y_LIMIT  and  Q_c = M2 + |b|^2 <= MUF_Q_LIMIT,  M2 = max_j |a_j|^2
+// (written so that NaN fails); otherwise it flags itself (mu_slack = -1 for its candidates) and mu_bound_kernel, launched
+// behind, runs it as before; mu_bound_kernel's other workgroups return at once.  |y| <= Y_c (Cauchy-Schwarz on the
+// computed fragments, M2 being the maximum of the very values |a_j|^2 the row factors use).
+//
+// Proof of |mu_approx - mu| <= mu_slack on this path.  r2 no longer shares bits with the exact build, so both sides are
+// compared with the real value R_j = outputscale alpha_j exp(-|s_j - s*|^2 / 2) of the fp64 scaled points s = x / l;
+// u = 2^-53, v = 2^-24, D = DMAX.
+//  (e) the exact path against R.  Its centred points carry u relative per coordinate, the norms D u, the MFMA dot
+//      D u |a'||b'|, the two operations of sqdist_expanded u each: |r2 - real| <= 2 (D + 4) u (|a'|^2 + |b'|^2), the clamp
+//      only helping; its block centre lies within sqrt(M2) of c, so |a'|^2 + |b'|^2 <= 6 Q_c.  With exp's and the
+//      outputscale's ulp: |k_j - R_j / alpha_j| <= (6 (D + 4) Q_c + 4) u k_j <= (120 Q_c + 4) u k_j.
+//  (f) this path against R, fp64 part.  |a - b|^2 = |a|^2 + |b|^2 - 2 a.b exactly for the rounded a, b, and differs from
+//      the real r2 by <= 4 u Q_c; the two norms carry D u each (exponent error <= D u Q_c / 2), the fragments' scaling 2 u
+//      and the MFMA D u (|y - log2(e) a.b| <= (D + 2) u Y_c <= 288 u), exp / products of alpha', G and the final
+//      scalings <= 8 u: relative (12 Q_c + 210) u.
+//      (e) + (f) + the sums of (b) (here npad / 64 + 6 fp64 additions per term) lie below
+//          eps64 = (256 Q_c + 512 + 2 (n + 64)) u  <=  2^-29 + (n + 320) 2^-52.
+//  (g) fp32 part, relative to |alpha"_j| e_j: rounding of y to fp32 <= v Y_c ln 2 (on 2^y), the instruction 2 v (1 ulp,
+//      no flush: |y| <= 16), alpha"'s rounding v, the run of 16 FMAs 16 v: (19 + 0.6932 Y_c) v.  Second-order terms and
+//      A against the true sum (A >= |S|: the two runs round monotonically in the same order) take the factor 1 + 2^-8:
+//          eps1(c) = ((19 + 0.6932 Y_c) 2^-24 + eps64) (1 + 2^-8)  <=  2^-19.08 + 2^-28 < 2^-18  for Y_c <= 16.
+//  (h) flushes.  alpha" below 2^-126 may flush (<= 2^-126 e <= 2^-110 each), so may an FMA's result (2^-126): less than
+//      n 2^-109 2^k <= 2^-84 |alpha|_1 in all for n < 2^24 (2^k <= 2 max |alpha'| <= 2 |alpha|_1); alpha' or G below the
+//      fp64 normal range lose at most 2^-1074 2^16 per term, which MUF_EPS2 |alpha|_1 covers because mu_prep_kernel sends
+//      every workgroup to the other path when 0 < max |alpha'| < 2^-800 (or when it is not finite).  MUF_EPS2 = 2^-80.
+//      mu_slack = (eps1(c) A~ + MUF_EPS2 |outputscale| |alpha|_1) (1 + 2^-30).
+//  Zero alpha: alpha" = 0, S = A = 0, G finite: both values are exact zeros.  Padded rows have alpha" = 0 and zero
+//  fragments (e = 1): exact zeros.  A NaN or infinite candidate fails the eligibility test and keeps the other path's
+//  result (NaN stays NaN).  (d) holds as before: mu_slack >= eps1 |mu_approx|.
+constexpr double MUF_Y_LIMIT = 16.0, MUF_Q_LIMIT = 65536.0, MUF_EPS2 = 0x1p-80;
+constexpr double MUF_LOG2E = 1.44269504088896340735992468100189;
+
+// The buffer's head: MUF_HEAD doubles of call-wide values, then the row blocks' records (MuPrep), the factorised form's
+// records (MuFact) and the row blocks' sums and maxima (MuStat).
+constexpr int MUF_FALLBACK = 0;  // int64: workgroups of the last call that took mu_bound_kernel's path
+constexpr int MUF_M2 = 1, MUF_SCALE = 2, MUF_L1 = 3, MUF_CEN = 4, MUF_HEAD = 32;
+
 // Per row block of 64 training rows: kstar_mfma_kernel's prologue (scaled rows, centre = mean of the valid rows, centred
 // rows, their norms), alpha with zeros for the padded rows, and sum |alpha| of the block.  Layout of a block's record:
 template <int DMAX>
 struct MuPrep {
   static constexpr int ROWS = 0, NA = NB * DMAX, AL = NA + NB, CEN = AL + NB, L1 = CEN + DMAX, STRIDE = L1 + 2;
 };
+// The factorised form's record of a row block: the fragments log2(e) a in the MFMA's own order (double FRAG + ((s KS +
+// k) 64 + lane) = row 16 s + (lane & 15), coordinate 4 k + (lane >> 4)), then alpha" as 64 floats, row 16 s + kq + 4 r at
+// float 16 kq + 4 s + r (the 16 rows of a lane in a row).
+template <int DMAX>
+struct MuFact {
+  static constexpr int FRAG = 0, AL = NB * DMAX, STRIDE = AL + NB / 2;
+};
+// A row block's column sums of the scaled rows, then max |a|^2, max |alpha'| and sum |alpha| over its valid rows.
+template <int DMAX>
+struct MuStat {
+  static constexpr int SUM = 0, M2 = DMAX, AM = DMAX + 1, L1 = DMAX + 2, STRIDE = DMAX + 4;
+};
 size_t mu_prep_doubles(int64_t npad, int d) {
   const int D = d <= 4 ? 4 : d <= 8 ? 8 : 16;
-  return (size_t)(npad / NB) * (NB * D + 2 * NB + D + 2);
+  return MUF_HEAD + (size_t)(npad / NB) * ((NB * D + 2 * NB + D + 2) + (NB * D + NB / 2) + (D + 4));
+}
+template <int DMAX>
+__device__ __forceinline__ double* mu_stat(double* prep, int npad, int jb) {
+  return prep + MUF_HEAD + (int64_t)(npad / NB) * (MuPrep<DMAX>::STRIDE + MuFact<DMAX>::STRIDE) +
+         (int64_t)jb * MuStat<DMAX>::STRIDE;
+}
+
+// |a|^2 of row j for the centre cen: the value the row factor, M2 and (through M2) the eligibility test all use.
+template <int DMAX>
+__device__ __forceinline__ double mu_row_norm(const gpx_kernel_params& p, const double* __restrict__ X, int64_t ldx,
+                                              int j, const double* cen) {
+  double u = 0.0;
+#pragma unroll
+  for (int k = 0; k < DMAX; ++k) {
+    const double a = k < p.d ? X[(int64_t)j * ldx + k] / p.lengthscale[k] - cen[k] : 0.0;
+    u = fma(a, a, u);
+  }
+  return u;
+}
+__device__ __forceinline__ double max_nan(double a, double b) { return (a > b || a != a) ? a : b; }  // a NaN stays
+
+// The call-wide values of the factorised form (centre, M2, 2^k, |alpha|_1) in three small launches of one workgroup per
+// row block, every sum and maximum in a fixed order: the blocks' column sums; from them the centre (every workgroup the
+// same bits) and the blocks' maxima; from those M2 and 2^k in mu_prep_kernel.
+template <int DMAX>
+__global__ void __launch_bounds__(WG) mu_colsum_kernel(gpx_kernel_params p, int n, int npad,
+                                                       const double* __restrict__ X, int64_t ldx,
+                                                       double* __restrict__ prep) {
+  __shared__ double red[WG];
+  const int jb = blockIdx.x, j0 = jb * NB, d = p.d, t = threadIdx.x, k = t % DMAX;
+  double s = 0.0;
+  if (k < d)
+    for (int r = t / DMAX; r < NB && j0 + r < n; r += WG / DMAX) s += X[(int64_t)(j0 + r) * ldx + k] / p.lengthscale[k];
+  red[t] = s;
+  __syncthreads();
+  if (t < DMAX) {
+    double v = 0.0;
+    for (int i = t; i < WG; i += DMAX) v += red[i];
+    mu_stat<DMAX>(prep, npad, jb)[MuStat<DMAX>::SUM + t] = v;
+  }
 }
 
 template <int DMAX>
-__global__ void __launch_bounds__(WG) mu_prep_kernel(gpx_kernel_params p, int n, const double* __restrict__ X,
+__global__ void __launch_bounds__(NB) mu_rowstat_kernel(gpx_kernel_params p, int n, int npad,
+                                                        const double* __restrict__ X, int64_t ldx,
+                                                        const double* __restrict__ alpha, double* __restrict__ prep) {
+  using T = MuStat<DMAX>;
+  __shared__ double cen[DMAX];
+  const int jb = blockIdx.x, j = jb * NB + (int)threadIdx.x, t = threadIdx.x;
+  if (t < DMAX) {
+    double s = 0.0;
+    for (int b = 0; b < npad / NB; ++b) s += mu_stat<DMAX>(prep, npad, b)[T::SUM + t];
+    cen[t] = s / n;
+    if (jb == 0) prep[MUF_CEN + t] = cen[t];
+  }
+  __syncthreads();
+  double m2 = 0.0, am = 0.0, l1 = 0.0;
+  if (j < n) {
+    m2 = mu_row_norm<DMAX>(p, X, ldx, j, cen);
+    am = fabs(alpha[j] * exp(-0.5 * m2));
+    l1 = fabs(alpha[j]);
+  }
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    m2 = max_nan(m2, __shfl_xor(m2, o));
+    am = max_nan(am, __shfl_xor(am, o));
+    l1 += __shfl_xor(l1, o);
+  }
+  if (t == 0) {
+    double* st = mu_stat<DMAX>(prep, npad, jb);
+    st[T::M2] = m2, st[T::AM] = am, st[T::L1] = l1;
+  }
+}
+
+template <int DMAX>
+__global__ void __launch_bounds__(WG) mu_prep_kernel(gpx_kernel_params p, int n, int npad, const double* __restrict__ X,
                                                      int64_t ldx, const double* __restrict__ alpha,
                                                      double* __restrict__ prep) {
   using P = MuPrep<DMAX>;
-  __shared__ double sa[NB][DMAX + 1], cen[DMAX];
+  using F = MuFact<DMAX>;
+  using T = MuStat<DMAX>;
+  constexpr int KS = DMAX / 4;
+  __shared__ double sa[NB][DMAX + 1], cen[DMAX], inv_scale;
   const int jb = blockIdx.x, j0 = jb * NB, d = p.d, t = threadIdx.x;
   const int nv = n - j0 < NB ? n - j0 : NB;
-  double* out = prep + (int64_t)jb * P::STRIDE;
+  if (t < 64) {  // M2, 2^k and |alpha|_1 from the blocks' values (every workgroup the same bits; block 0 writes the head)
+    double m2 = 0.0, am = 0.0, l1 = 0.0;
+    for (int b = t; b < npad / NB; b += 64) {
+      const double* st = mu_stat<DMAX>(prep, npad, b);
+      m2 = max_nan(m2, st[T::M2]);
+      am = max_nan(am, st[T::AM]);
+      l1 += st[T::L1];
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      m2 = max_nan(m2, __shfl_xor(m2, o));
+      am = max_nan(am, __shfl_xor(am, o));
+      l1 += __shfl_xor(l1, o);
+    }
+    if (t == 0) {
+      double scale = 1.0;
+      if (am > 0.0) {
+        int e;
+        (void)frexp(am, &e);
+        scale = ldexp(1.0, e);  // am in [scale / 2, scale)
+      }
+      if (!(am <= 0x1p1000) || (am > 0.0 && am < 0x1p-800)) m2 = __builtin_nan("");  // every workgroup to the other path
+      inv_scale = 1.0 / scale;
+      if (jb == 0) {
+        reinterpret_cast<unsigned long long*>(prep)[MUF_FALLBACK] = 0ull;
+        prep[MUF_M2] = m2;
+        prep[MUF_SCALE] = scale;
+        prep[MUF_L1] = l1;
+      }
+    }
+  }
+  __syncthreads();
+  {  // the factorised form's record (the centre is in the head: mu_rowstat_kernel)
+    double* fo = prep + MUF_HEAD + (int64_t)(npad / NB) * P::STRIDE + (int64_t)jb * F::STRIDE;
+    const double* gc = prep + MUF_CEN;
+    for (int e = t; e < NB * DMAX; e += WG) {
+      const int lane = e & 63, k = (e >> 6) % KS, s = (e >> 6) / KS;
+      const int j = j0 + 16 * s + (lane & 15), col = 4 * k + (lane >> 4);
+      const double a = (col < d && j < n) ? X[(int64_t)j * ldx + col] / p.lengthscale[col] - gc[col] : 0.0;
+      fo[F::FRAG + e] = a * MUF_LOG2E;
+    }
+    if (t < NB) {
+      const int kq = t >> 4, s = (t >> 2) & 3, r = t & 3, j = j0 + 16 * s + kq + 4 * r;
+      double ap = 0.0;
+      if (j < n) ap = alpha[j] * exp(-0.5 * mu_row_norm<DMAX>(p, X, ldx, j, gc)) * inv_scale;
+      reinterpret_cast<float*>(fo + F::AL)[t] = (float)ap;
+    }
+  }
+  double* out = prep + MUF_HEAD + (int64_t)jb * P::STRIDE;
   for (int e = t; e < NB * DMAX; e += WG) {
     const int r = e / DMAX, k = e % DMAX;
     const double v = (k < d && j0 + r < n) ? X[(int64_t)(j0 + r) * ldx + k] : 0.0;
@@ -482,6 +665,8 @@ __global__ void __launch_bounds__(WG) mu_bound_kernel(gpx_kernel_params p, int n
   __shared__ double sa[NB][DMAX + 1], sb[WG][DMAX + 1], na[NB], nb[WG], sal[NB];
   const int d = p.d, t = threadIdx.x;
   const int64_t c0 = (int64_t)blockIdx.x * WG;
+  if (mu_slack[c0] != -1.0) return;  // mu_fact_kernel did this workgroup's candidates
+  prep += MUF_HEAD;
   const int nblk = (n + NB - 1) / NB;  // row blocks with a valid row
   double xb[DMAX];
 #pragma unroll
@@ -552,6 +737,130 @@ __global__ void __launch_bounds__(WG) mu_bound_kernel(gpx_kernel_params p, int n
       mu_approx[c] = p.outputscale * s;
       mu_slack[c] = (MUB_EPS1 * at + MUB_EPS2 * os * l1 + ((double)(n + 64) * 0x1p-52) * at) * (1.0 + 0x1p-30);
     }
+  }
+}
+
+// The factorised form.  Workgroup x: candidates 256 x .. 256 x + 255 against every row block, no LDS: a lane keeps the
+// fragments of its wave's 64 candidates in registers for the whole kernel (the centre is the same for every row block)
+// and reads the row blocks' fragments and alpha" from their records (every wave reads the same lines; the next block's
+// are loaded before the current block's work).  The MFMAs of a row step are issued before the exponentials of the step
+// before it.  Thread t ends up with the sums of its own candidate c0 + t (16-lane row kq holds candidate block cb = kq).
+template <int DMAX>
+__global__ void __launch_bounds__(WG) mu_fact_kernel(gpx_kernel_params p, int n, int npad,
+                                                     const double* __restrict__ prep, const double* __restrict__ Xs,
+                                                     int64_t ldxs, int64_t m_chunk, double* __restrict__ mu_approx,
+                                                     double* __restrict__ mu_slack,
+                                                     unsigned long long* __restrict__ fallback) {
+  using F = MuFact<DMAX>;
+  constexpr int KS = DMAX / 4;
+  const int d = p.d, t = threadIdx.x;
+  const int64_t c0 = (int64_t)blockIdx.x * WG, c = c0 + t;
+  const int nblk = (n + NB - 1) / NB;  // row blocks with a valid row
+  const double* __restrict__ gc = prep + MUF_CEN;
+  const double m2 = prep[MUF_M2];
+  double nbq = 0.0;
+#pragma unroll
+  for (int k = 0; k < DMAX; ++k) {
+    const double v = (k < d && c < m_chunk) ? Xs[c * ldxs + k] : 0.0;
+    const double b = k < d ? v / p.lengthscale[k] - gc[k] : 0.0;
+    nbq = fma(b, b, nbq);
+  }
+  const double yc = MUF_LOG2E * sqrt(m2 * nbq) * (1.0 + 0x1p-40), q = m2 + nbq;
+  const bool ok = c >= m_chunk || (yc <= MUF_Y_LIMIT && q <= MUF_Q_LIMIT);  // (NaN fails)
+  if (!__syncthreads_and(ok)) {
+    if (c < m_chunk) mu_slack[c] = -1.0;
+    if (t == 0) atomicAdd(fallback, 1ull);
+    return;
+  }
+  const int lane = t & 63, w = t >> 6, m = lane & 15, kq = lane >> 4;
+  double bf[4][KS];
+#pragma unroll
+  for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+    for (int k = 0; k < KS; ++k) {
+      const int64_t cc = c0 + 64 * w + 16 * cb + m;
+      const int col = 4 * k + kq;
+      const double v = (col < d && cc < m_chunk) ? Xs[cc * ldxs + col] : 0.0;
+      bf[cb][k] = col < d ? v / p.lengthscale[col] - gc[col] : 0.0;
+    }
+  const double* __restrict__ rec = prep + MUF_HEAD + (int64_t)(npad / NB) * MuPrep<DMAX>::STRIDE;
+  double af[4][KS], afn[4][KS];
+  float4 al[4], aln[4];
+  auto load = [&](int jb, double(&a)[4][KS], float4(&l)[4]) {
+    const double* __restrict__ in = rec + (int64_t)jb * F::STRIDE;
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int k = 0; k < KS; ++k) a[s][k] = in[F::FRAG + (s * KS + k) * 64 + lane];
+    const float4* __restrict__ ap = reinterpret_cast<const float4*>(in + F::AL) + 4 * kq;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) l[s] = ap[s];
+  };
+  auto mm = [&](const double(&a)[KS], d4(&acc)[4]) {
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) {
+      acc[cb] = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int k = 0; k < KS; ++k) acc[cb] = mfma16x16x4(a[k], bf[cb][k], acc[cb]);
+    }
+  };
+  float Sf[4], Af[4];
+  auto entries = [&](const d4(&acc)[4], const float4 l) {  // rows kq + 4 r of the step, alpha" in l
+    const float lr[4] = {l.x, l.y, l.z, l.w};
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb) {
+        const float e = __builtin_amdgcn_exp2f((float)acc[cb][r]);
+        Sf[cb] = fmaf(lr[r], e, Sf[cb]);
+        Af[cb] = fmaf(fabsf(lr[r]), e, Af[cb]);
+      }
+  };
+  double S[4] = {0.0, 0.0, 0.0, 0.0}, A[4] = {0.0, 0.0, 0.0, 0.0};
+  d4 acc0[4], acc1[4];
+  load(0, af, al);
+  mm(af[0], acc0);
+#pragma unroll 1
+  for (int jb = 0; jb < nblk; ++jb) {
+    load(jb + 1 < nblk ? jb + 1 : jb, afn, aln);
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) Sf[cb] = Af[cb] = 0.0f;
+    mm(af[1], acc1);
+    entries(acc0, al[0]);
+    mm(af[2], acc0);
+    entries(acc1, al[1]);
+    mm(af[3], acc1);
+    entries(acc0, al[2]);
+    mm(afn[0], acc0);  // (the last block's again after the last: unused)
+    entries(acc1, al[3]);
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) {
+      S[cb] += (double)Sf[cb];
+      A[cb] += (double)Af[cb];
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      al[s] = aln[s];
+#pragma unroll
+      for (int k = 0; k < KS; ++k) af[s][k] = afn[s][k];
+    }
+  }
+#pragma unroll
+  for (int cb = 0; cb < 4; ++cb) {
+    S[cb] += __shfl_xor(S[cb], 16);
+    S[cb] += __shfl_xor(S[cb], 32);
+    A[cb] += __shfl_xor(A[cb], 16);
+    A[cb] += __shfl_xor(A[cb], 32);
+  }
+  if (c < m_chunk) {
+    const double s = kq == 0 ? S[0] : kq == 1 ? S[1] : kq == 2 ? S[2] : S[3];
+    const double a = kq == 0 ? A[0] : kq == 1 ? A[1] : kq == 2 ? A[2] : A[3];
+    const double g = exp(-0.5 * nbq), scale = prep[MUF_SCALE], os = fabs(p.outputscale);
+    const double at = (os * (scale * a)) * g;
+    const double eps1 =
+        ((19.0 + 0.6932 * yc) * 0x1p-24 + (256.0 * q + 512.0 + 2.0 * (double)(n + 64)) * 0x1p-53) * (1.0 + 0x1p-8);
+    mu_approx[c] = (p.outputscale * (scale * s)) * g;
+    mu_slack[c] = (eps1 * at + MUF_EPS2 * os * prep[MUF_L1]) * (1.0 + 0x1p-30);
   }
 }
 
@@ -1242,8 +1551,8 @@ static void launch_kstar(Context* c, const gpx_kernel_params& p, int n, int npad
 #undef GPX_KSTAR_K
 }
 
-// The head phase's mean bound of m_chunk candidates (mu_prep_kernel + mu_bound_kernel); prep: mu_prep_doubles(npad, d)
-// doubles of scratch.
+// The head phase's mean bound of m_chunk candidates (mu_colsum_kernel, mu_rowstat_kernel and mu_prep_kernel, then mu_fact_kernel for the
+// eligible workgroups and mu_bound_kernel for the others); prep: mu_prep_doubles(npad, d) doubles of scratch.
 bool sweep_mu_bound_ok(const gpx_kernel_params& p) { return p.kind == GPX_KERNEL_RBF && !p.cov_fp32 && p.d <= 16; }
 
 hipError_t launch_mu_bound(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X, int64_t ldx,
@@ -1251,8 +1560,12 @@ hipError_t launch_mu_bound(Context* c, const gpx_kernel_params& p, int n, int np
                            double* mu_approx, double* mu_slack) {
   LaunchTimer tm(c, GPX_TIMER_KSTAR);
   const unsigned nwg = (unsigned)((m_chunk + WG - 1) / WG);
+  unsigned long long* fallback = reinterpret_cast<unsigned long long*>(prep) + MUF_FALLBACK;
 #define GPX_MU_BOUND(D)                                                                                            \
-  (mu_prep_kernel<D><<<npad / NB, WG, 0, c->stream>>>(p, n, X, ldx, alpha, prep),                                   \
+  (mu_colsum_kernel<D><<<npad / NB, WG, 0, c->stream>>>(p, n, npad, X, ldx, prep),                                  \
+   mu_rowstat_kernel<D><<<npad / NB, NB, 0, c->stream>>>(p, n, npad, X, ldx, alpha, prep),                          \
+   mu_prep_kernel<D><<<npad / NB, WG, 0, c->stream>>>(p, n, npad, X, ldx, alpha, prep),                             \
+   mu_fact_kernel<D><<<nwg, WG, 0, c->stream>>>(p, n, npad, prep, Xs, ldxs, m_chunk, mu_approx, mu_slack, fallback), \
    mu_bound_kernel<D><<<nwg, WG, 0, c->stream>>>(p, n, prep, Xs, ldxs, m_chunk, mu_approx, mu_slack))
   if (p.d <= 4)
     GPX_MU_BOUND(4);
@@ -1516,7 +1829,7 @@ hipError_t launch_sweep_super_pruned(Context* c, const gpx_kernel_params& p, int
       // the mean's bound instead of the mean.  Its two values per candidate go to the mean partials' rows of blocks 2
       // and 3 (the head rows' launch wrote blocks 0 and 1; nothing writes the others before the gather), the row
       // blocks' records to the chunk's K* buffer, idle between the seed block's scoring and the first gather
-      // (mu_prep_doubles <= 19 npad doubles, the buffer holds npad x C >= 256 npad).
+      // (mu_prep_doubles <= 38 npad + 32 doubles, the buffer holds npad x C >= 256 npad).
       static_assert(PRUNE_MIN_NPAD / NB >= 4, "mean partial rows 2 and 3 exist");
       (void)launch_mu_bound(c, p, n, npad, X, ldx, alpha, Xs, ldxs, m_super, b.kstar, ph.mu_part + 2 * MA,
                             ph.mu_part + 3 * MA);  // (the launch error is read at the end)
