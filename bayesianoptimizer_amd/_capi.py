@@ -36,6 +36,7 @@ GPX_OPT_COUNT = len(OPTIONS) + len(GPX_OPT_RESERVED)
 
 KERNEL_RBF, KERNEL_MATERN52, KERNEL_SCALE_LINEAR_MATERN52 = 0, 1, 2
 ACQ_EI, ACQ_LOGEI, ACQ_UCB, ACQ_VARIANCE = 0, 1, 2, 3
+MCACQ_QLOGEI, MCACQ_QPSD = 0, 1
 TIMERS = {"gram": 0, "potrf": 1, "trtri": 2, "alpha": 3, "kstar": 4, "trmm": 5, "acq": 6, "mll": 7}
 
 # gpx_mll_grad_f64 output layout (include/gpx.h)
@@ -109,6 +110,18 @@ class AcqParamsC(ctypes.Structure):
     ]
 
 
+class McAcqParamsC(ctypes.Structure):
+    _fields_ = [
+        ("kind", c_int32),
+        ("fat_relu", c_int32),
+        ("fat_max", c_int32),
+        ("reserved", c_int32),
+        ("best_f", c_double),
+        ("tau_relu", c_double),
+        ("tau_max", c_double),
+    ]
+
+
 _h = c_void_p
 _p = c_void_p  # device pointers
 _PROTOS = {
@@ -161,6 +174,10 @@ _PROTOS = {
     "gpx_moments_grad_workspace_size": (c_int32, [c_int64, c_int64, POINTER(c_size_t)]),
     "gpx_moments_grad_f64": (c_int32, [_h, POINTER(KernelParamsC), c_int64, _p, c_int64, _p, c_int64, _p, _p, c_int64,
                                        c_int64, c_int64, _p, _p, _p, _p, _p, c_size_t]),
+    "gpx_mcacq_params_size": (c_size_t, []),
+    "gpx_mc_acq_workspace_size": (c_int32, [c_int64, c_int64, c_int64, POINTER(c_size_t)]),
+    "gpx_mc_acq_f64": (c_int32, [_h, POINTER(McAcqParamsC), c_int64, c_int64, c_int64, _p, _p, _p, _p, _p, _p, _p, _p,
+                                 c_size_t]),
     "gpx_sweep_workspace_size": (c_int32, [c_int64, c_int64, c_int64, POINTER(c_size_t)]),
     "gpx_posterior_f64": (c_int32, [_h, POINTER(KernelParamsC), c_int64, _p, c_int64, _p, c_int64, _p, c_int64,
                                     _p, c_int64, c_int64, POINTER(c_double), POINTER(c_double), _p, c_int64, _p,
@@ -237,7 +254,8 @@ def load() -> ctypes.CDLL:
         fn.argtypes = args
     # the struct definitions above must match the ones compiled into the library (a truncated struct would make the
     # library read past the caller's object, include/gpx.h)
-    for cls, fn in ((KernelParamsC, lib.gpx_kernel_params_size), (AcqParamsC, lib.gpx_acq_params_size)):
+    for cls, fn in ((KernelParamsC, lib.gpx_kernel_params_size), (AcqParamsC, lib.gpx_acq_params_size),
+                    (McAcqParamsC, lib.gpx_mcacq_params_size)):
         if ctypes.sizeof(cls) != fn():
             raise GPXLibraryError(f"{cls.__name__} is {ctypes.sizeof(cls)} bytes, libgpx expects {fn()}")
     _lib = lib

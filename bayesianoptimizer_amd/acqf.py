@@ -16,9 +16,14 @@ outputs, 256 base samples, num_restarts 8, raw_samples 256).  This module mirror
 Parity definition (parity unpinned: BoTorch is not installed and has no fixtures here): qLogEI follows
 BoTorch's log-space form — log-improvement with the fat-tailed softplus (softplus + 0.1 * Cauchy, tau_relu = 1e-6) or
 the plain log-softplus (``fat=False``), q-reduction by the smooth max tau_max * logsumexp(x / tau_max) (tau_max =
-1e-2; BoTorch's fat q-reduction tail is not restated — identical for q = 1), sample reduction logmeanexp.  Base
-samples are scrambled Sobol points (``torch.quasirandom.SobolEngine``) mapped through the inverse normal cdf.
-oracle/gp_oracle.py restates the same definitions in NumPy for the tests.
+1e-2) or, with ``fat_max=True``, by BoTorch's fat-tailed ``fatmax`` (identical for q = 1), sample reduction
+logmeanexp.  Base samples are scrambled Sobol points (``torch.quasirandom.SobolEngine``) mapped through the inverse
+normal cdf.  oracle/gp_oracle.py restates the logsumexp definitions in NumPy for the tests.
+
+The Monte-Carlo part after the moments runs either in torch (the default qLogEI: batched Cholesky, einsum, softplus and
+logsumexp chains, differentiated by autograd) or in one libgpx call, ``gpx_mc_acq_f64`` (``fused=True``, ``fat_max=True``
+and ``qPosteriorStandardDeviation``, the exact-mode acquisition of ``optimization/Bayesian6.py:113-130, 896-919``): value
+and the gradients w.r.t. the moments from one kernel, chained to ``gpx_moments_grad_f64``'s derivatives by ``_Moments``.
 """
 from __future__ import annotations
 
@@ -162,6 +167,15 @@ def smooth_amax(x, tau: float, dim: int = -1):
     return tau * torch.logsumexp(x / tau, dim=dim)
 
 
+def fatmax(x, tau: float, alpha: float = 2.0, dim: int = -1):
+    """BoTorch's fat-tailed smooth maximum (safe_math.fatmax [upstream, unverified: restated from memory]): with
+    M = max x, M + tau log sum_i (1 + (M - x_i) / (alpha tau))^-alpha.  An entry far below the maximum keeps a gradient
+    that decays like a power of its distance, where logsumexp's decays exponentially."""
+    M = x.amax(dim=dim, keepdim=True)
+    t = 1.0 + (M - x) / (alpha * tau)
+    return M.squeeze(dim) + tau * torch.log(t.pow(-alpha).sum(dim=dim))
+
+
 def logmeanexp(x, dim: int = 0):
     return torch.logsumexp(x, dim=dim) - math.log(x.shape[dim])
 
@@ -209,6 +223,27 @@ def psd_safe_cholesky(S: torch.Tensor, max_tries: int = 3) -> torch.Tensor:
             return L
         jitter *= 10.0
     raise torch.linalg.LinAlgError("q-batch posterior covariance not positive definite after jitter")
+
+
+class _McAcq(torch.autograd.Function):
+    """value (B) of gpx_mc_acq_f64 from (mean (B, q), cov (B, q, q)); backward scales the kernel's gmean / gcov by the
+    incoming gradient.  Without a gradient to give (scoring under no_grad) the call is value-only.  Raises LinAlgError
+    when a batch's covariance did not factor after the jitter retries; reading that word is the only synchronisation."""
+
+    @staticmethod
+    def forward(ctx, mean, cov, engine, z, kind, opts):
+        need_grad = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
+        value, gmean, gcov, info = engine.mc_acq(mean.detach(), cov.detach(), z, kind, need_grad=need_grad, **opts)
+        if bool((info < 0).any()):
+            raise torch.linalg.LinAlgError("q-batch posterior covariance not positive definite after jitter")
+        if need_grad:
+            ctx.save_for_backward(gmean, gcov)
+        return value
+
+    @staticmethod
+    def backward(ctx, gvalue):
+        gmean, gcov = ctx.saved_tensors
+        return gvalue.unsqueeze(-1) * gmean, gvalue.view(-1, 1, 1) * gcov, None, None, None, None
 
 
 # ---- acquisition functions (differentiable in X of shape B x q x d) -----------------------------------------
@@ -263,11 +298,13 @@ class PosteriorVariance(AnalyticAcquisition):
 class qLogExpectedImprovement:
     """MC q-batch log expected improvement (the acquisition of Bayesian.py:100-101 and Bayesian2.py:226-231):
     samples f = mu + L z of the objective's joint q-batch posterior, log-improvement log_fatplus(f - best_f, tau_relu)
-    (or log_softplus with fat=False), smooth max over q (tau_max), logmeanexp over the samples."""
+    (or log_softplus with fat=False), smooth max over q (tau_max), logmeanexp over the samples.  ``fat_max=True``:
+    BoTorch's default q-reduction ``fatmax`` instead of tau_max * logsumexp.  ``fused=True`` or ``fat_max=True``: the
+    Monte-Carlo part runs in gpx_mc_acq_f64; with both off it is the torch chain of qlogei_from_moments."""
 
     def __init__(self, model, best_f: float, sampler: Optional[SobolQMCNormalSampler] = None,
                  objective: Optional[LinearMCObjective] = None, fat: bool = True, tau_max: float = TAU_MAX,
-                 tau_relu: float = TAU_RELU, output: int = 0):
+                 tau_relu: float = TAU_RELU, output: int = 0, fat_max: bool = False, fused: bool = False):
         self.model = model
         self.best_f = float(best_f)
         self.sampler = sampler or SobolQMCNormalSampler(torch.Size([512]))
@@ -275,6 +312,8 @@ class qLogExpectedImprovement:
         self.fat = fat
         self.tau_max = float(tau_max)
         self.tau_relu = float(tau_relu)
+        self.fat_max = bool(fat_max)
+        self.fused = bool(fused) or self.fat_max
 
     def __call__(self, X: torch.Tensor) -> torch.Tensor:
         if X.dim() == 2:
@@ -282,7 +321,29 @@ class qLogExpectedImprovement:
         q = X.shape[1]
         mu, cov = posterior_moments(self.model, X, self.objective)
         z = self.sampler.base_samples(q, X.device)
+        if self.fused:
+            opts = {"best_f": self.best_f, "fat_relu": self.fat, "fat_max": self.fat_max, "tau_max": self.tau_max,
+                    "tau_relu": self.tau_relu}
+            return _McAcq.apply(mu, cov, self.model.engine, z, "qlogei", opts)
         return qlogei_from_moments(mu, cov, z, self.best_f, self.fat, self.tau_max, self.tau_relu)
+
+
+class qPosteriorStandardDeviation:
+    """MC q-batch posterior standard deviation of one output (optimization/Bayesian6.py:113-130: the sum over the q
+    points of the standard deviation over the samples of ``samples[..., output]``), on gpx_mc_acq_f64.  The default
+    sampler draws 256 base samples (Bayesian6.py:896-919)."""
+
+    def __init__(self, model, sampler: Optional[SobolQMCNormalSampler] = None, output: int = 0):
+        self.model = model
+        self.sampler = sampler or SobolQMCNormalSampler(torch.Size([256]))
+        self.objective = _Objective(model, None, output)
+
+    def __call__(self, X: torch.Tensor) -> torch.Tensor:
+        if X.dim() == 2:
+            X = X.unsqueeze(0)
+        mu, cov = posterior_moments(self.model, X, self.objective)
+        z = self.sampler.base_samples(X.shape[1], X.device)
+        return _McAcq.apply(mu, cov, self.model.engine, z, "qpsd", {})
 
 
 def qlogei_from_moments(mu: torch.Tensor, cov: torch.Tensor, z: torch.Tensor, best_f: float, fat: bool = True,
@@ -321,14 +382,50 @@ def initialize_q_batch(X: torch.Tensor, Y: torch.Tensor, n: int, eta: float = 1.
     return X[idcs.to(X.device)]
 
 
+def initialize_q_batch_nonneg(X: torch.Tensor, Y: torch.Tensor, n: int, eta: float = 1.0, alpha: float = 1e-4,
+                              generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """n restart points from raw samples X (N x q x d) with non-negative acquisition values Y (N) (BoTorch
+    initialize_q_batch_nonneg [upstream, from the public algorithm]): only points with Y >= alpha max(Y) qualify (alpha
+    divided by 10 until n do), drawn with weights exp(eta (Y / max(Y) - 1)), the best point always kept.  Fewer than
+    n positive values: all of them plus a random fill; none: a random choice."""
+    N = X.shape[0]
+    if n > N:
+        raise ValueError(f"n ({n}) cannot exceed the number of raw samples ({N})")
+    if n == N:
+        return X
+    Yc = Y.detach().cpu()
+    max_idx = int(torch.argmax(Yc))
+    max_val = Yc[max_idx]
+    if not bool(max_val > 0):
+        return X[torch.randperm(N, generator=generator)[:n].to(X.device)]
+    pos = Yc > 0
+    num_pos = int(pos.sum())
+    if num_pos < n:
+        rest = (~pos).nonzero().view(-1)
+        fill = rest[torch.randperm(rest.numel(), generator=generator)[:n - num_pos]]
+        pos[fill] = True
+        return X[pos.nonzero().view(-1).to(X.device)]
+    ok = Yc >= alpha * max_val
+    while int(ok.sum()) < n:
+        alpha = 0.1 * alpha
+        ok = Yc >= alpha * max_val
+    ok_idcs = ok.nonzero().view(-1)
+    weights = torch.exp(eta * (Yc[ok] / max_val - 1.0))
+    idcs = ok_idcs[torch.multinomial(weights, n, replacement=False, generator=generator)]
+    if max_idx not in idcs.tolist():
+        idcs[-1] = max_idx
+    return X[idcs.to(X.device)]
+
+
 def _eval_batched(acq, X: torch.Tensor, chunk: int) -> torch.Tensor:
     with torch.no_grad():
         return torch.cat([acq(X[s:s + chunk]) for s in range(0, X.shape[0], chunk)])
 
 
 def gen_batch_initial_conditions(acq, bounds: torch.Tensor, q: int, num_restarts: int, raw_samples: int,
-                                 seed: Optional[int] = None, eta: float = 1.0) -> torch.Tensor:
-    """raw_samples scrambled-Sobol q-batches in the bounds, scored on the GPU posterior, then initialize_q_batch."""
+                                 seed: Optional[int] = None, eta: float = 1.0, nonnegative: bool = False) -> torch.Tensor:
+    """raw_samples scrambled-Sobol q-batches in the bounds, scored on the GPU posterior, then initialize_q_batch
+    (``nonnegative``: initialize_q_batch_nonneg, for acquisition values that cannot be negative)."""
     d = bounds.shape[1]
     seed = int(seed) if seed is not None else int(torch.randint(0, 1_000_000, (1,)).item())
     u = torch.quasirandom.SobolEngine(dimension=q * d, scramble=True, seed=seed).draw(raw_samples, dtype=torch.float64)
@@ -337,7 +434,8 @@ def gen_batch_initial_conditions(acq, bounds: torch.Tensor, q: int, num_restarts
     max_m = _capi.GPX_MAX_GRAD_CANDIDATES // q
     Y = _eval_batched(acq, X, max(1, min(max_m, 2048 // q if q <= 2048 else 1)))
     g = torch.Generator().manual_seed(seed)
-    return initialize_q_batch(X, Y, num_restarts, eta=eta, generator=g)
+    init = initialize_q_batch_nonneg if nonnegative else initialize_q_batch
+    return init(X, Y, num_restarts, eta=eta, generator=g)
 
 
 def gen_candidates_scipy(X0: torch.Tensor, acq, lower: torch.Tensor, upper: torch.Tensor, maxiter: int = 200):
@@ -378,7 +476,8 @@ def gen_candidates_scipy(X0: torch.Tensor, acq, lower: torch.Tensor, upper: torc
 def optimize_acqf(acq_function, bounds, q: int, num_restarts: int, raw_samples: int, options: Optional[dict] = None,
                   return_best_only: bool = True, seed: Optional[int] = None):
     """BoTorch-shaped optimize_acqf (Bayesian.py:105-112, Bayesian2.py:240-245): raw-sample initialisation, restarts
-    in batches of ``batch_limit`` refined with L-BFGS-B (``maxiter``), best restart returned as (q x d, value)."""
+    in batches of ``batch_limit`` refined with L-BFGS-B (``maxiter``), best restart returned as (q x d, value).
+    ``options["nonnegative"]``: initialise with initialize_q_batch_nonneg (Bayesian6.py:896-919)."""
     options = dict(options or {})
     dev = acq_function.model.engine.device
     bounds = torch.as_tensor(bounds, dtype=torch.float64, device=dev)
@@ -387,7 +486,8 @@ def optimize_acqf(acq_function, bounds, q: int, num_restarts: int, raw_samples: 
     if q < 1 or q > _capi.GPX_MAX_Q:
         raise ValueError(f"q must be in [1, {_capi.GPX_MAX_Q}]")
     X0 = gen_batch_initial_conditions(acq_function, bounds, q, num_restarts, raw_samples, seed=seed,
-                                      eta=float(options.get("eta", 1.0)))
+                                      eta=float(options.get("eta", 1.0)),
+                                      nonnegative=bool(options.get("nonnegative", False)))
     batch_limit = int(options.get("batch_limit", num_restarts))
     maxiter = int(options.get("maxiter", 200))
     Xs, vs = [], []

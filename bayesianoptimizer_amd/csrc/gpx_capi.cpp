@@ -868,6 +868,50 @@ gpx_status gpx_moments_grad_f64(gpx_handle h, const gpx_kernel_params* p, int64_
                    "moments_grad");
 }
 
+size_t gpx_mcacq_params_size(void) { return sizeof(gpx_mcacq_params); }
+
+gpx_status gpx_mc_acq_workspace_size(int64_t B, int64_t q, int64_t S, size_t* bytes) {
+  if (!bytes || q < 1 || q > GPX_MAX_Q || B < 1 || B * q > GPX_MAX_GRAD_CANDIDATES || S < 1 || S > (int64_t)1 << 20)
+    return GPX_INVALID_ARG;
+  *bytes = gpx::mc_acq_ws_doubles(B, q, S) * sizeof(double) + 256;
+  return GPX_OK;
+}
+
+gpx_status gpx_mc_acq_f64(gpx_handle h, const gpx_mcacq_params* a, int64_t B, int64_t q, int64_t S, const double* mean,
+                          const double* cov, const double* z, double* value, double* gmean, double* gcov,
+                          int32_t* info, void* ws, size_t ws_bytes) {
+  Context* c = reinterpret_cast<Context*>(h);
+  if (!c) return GPX_INVALID_ARG;
+  GPX_NONNULL(c, a);
+  if (a->kind != GPX_MCACQ_QLOGEI && a->kind != GPX_MCACQ_QPSD)
+    return fail(c, GPX_INVALID_ARG, "unknown MC acquisition kind " + std::to_string(a->kind));
+  if ((a->fat_relu != 0 && a->fat_relu != 1) || (a->fat_max != 0 && a->fat_max != 1))
+    return fail(c, GPX_INVALID_ARG, "gpx_mcacq_params.fat_relu / fat_max must be 0 or 1");
+  if (a->reserved != 0) return fail(c, GPX_INVALID_ARG, "gpx_mcacq_params.reserved must be 0");
+  if (!(a->tau_relu > 0.0) || !(a->tau_max > 0.0) || !std::isfinite(a->tau_relu) || !std::isfinite(a->tau_max))
+    return fail(c, GPX_INVALID_ARG, "tau_relu and tau_max must be positive and finite");
+  if (q < 1 || q > GPX_MAX_Q) return fail(c, GPX_INVALID_ARG, "q must be in [1, GPX_MAX_Q]");
+  if (B < 1 || B * q > GPX_MAX_GRAD_CANDIDATES)
+    return fail(c, GPX_INVALID_ARG, "B must be at least 1 and B * q at most GPX_MAX_GRAD_CANDIDATES");
+  if (S < (a->kind == GPX_MCACQ_QPSD ? 2 : 1) || S > (int64_t)1 << 20)
+    return fail(c, GPX_INVALID_ARG, "S must be in [1, 2^20], and at least 2 for GPX_MCACQ_QPSD");
+  if ((gmean == nullptr) != (gcov == nullptr))
+    return fail(c, GPX_INVALID_ARG, "gmean and gcov must be both NULL or both set");
+  GPX_NONNULL(c, mean);
+  GPX_NONNULL(c, cov);
+  GPX_NONNULL(c, z);
+  GPX_NONNULL(c, value);
+  GPX_NONNULL(c, info);
+  GPX_NONNULL(c, ws);
+  size_t need = 0;
+  GPX_TRY(gpx_mc_acq_workspace_size(B, q, S, &need));
+  if (ws_bytes < need) return fail(c, GPX_INVALID_ARG, "mc_acq workspace too small");
+  GPX_USE_DEVICE(c);
+  return hip_check(c, gpx::launch_mc_acq(c, *a, (int)B, (int)q, (int)S, mean, cov, z, value, gmean, gcov, info,
+                                         align256(ws)),
+                   "mc_acq");
+}
+
 gpx_status gpx_sweep_workspace_size(int64_t n, int64_t nrhs, int64_t m, size_t* bytes) {
   if (!bytes || n < 1 || m < 1 || nrhs < 1 || nrhs > GPX_MAX_RHS) return GPX_INVALID_ARG;
   *bytes = gpx::sweep_workspace_bytes(padded(n), nrhs, m);

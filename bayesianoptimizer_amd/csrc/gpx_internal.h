@@ -275,6 +275,12 @@ hipError_t launch_moments_grad(Context* c, const gpx_kernel_params& p, int n, in
                                const double* W, int64_t ldw, const double* alpha, const double* Xs, int64_t ldxs,
                                int m, int q, double* mean, double* dmean, double* cov, double* dcov, double* ws);
 
+// MC q-batch acquisition from the moments (gpx_mcacq.hip); gmean / gcov both null: value only
+size_t mc_acq_ws_doubles(int64_t B, int64_t q, int64_t S);
+hipError_t launch_mc_acq(Context* c, const gpx_mcacq_params& a, int B, int q, int S, const double* mean,
+                         const double* cov, const double* z, double* value, double* gmean, double* gcov, int32_t* info,
+                         double* ws);
+
 size_t mll_workspace_bytes(int64_t npad);
 hipError_t launch_mll(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X, int64_t ldx,
                       const double* Y, int64_t ldy, int nrhs, const double* L, int64_t ldl, const double* W,

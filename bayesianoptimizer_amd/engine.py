@@ -669,6 +669,40 @@ class GPEngine:
             ws.numel()))
         return mean, dmean, cov, dcov
 
+    def mc_acq(self, mean, cov, z, kind: str = "qlogei", best_f: float = 0.0, fat_relu: bool = True,
+               fat_max: bool = False, tau_max: float = 1e-2, tau_relu: float = 1e-6, need_grad: bool = True):
+        """Monte-Carlo acquisition value of B q-batches from their moments (gpx_mc_acq_f64): mean (B x q), cov
+        (B x q x q), base samples z (S x q); ``kind`` "qlogei" or "qpsd".  Returns device tensors (value (B), gmean
+        (B x q), gcov (B x q x q), info (B)); gmean and gcov are None with ``need_grad=False``.  info: 0 factored, 1..3
+        factored at that jitter retry, -1 not positive definite (value and gradients of that batch are NaN).
+        Asynchronous: the caller reads ``info``."""
+        kinds = {"qlogei": _capi.MCACQ_QLOGEI, "qpsd": _capi.MCACQ_QPSD}
+        if kind not in kinds:
+            raise ValueError(f"unknown MC acquisition '{kind}'")
+        dev = self.device
+        mean = mean.to(device=dev, dtype=torch.float64).contiguous()
+        cov = cov.to(device=dev, dtype=torch.float64).contiguous()
+        z = z.to(device=dev, dtype=torch.float64).contiguous()
+        if mean.dim() != 2 or cov.shape != (mean.shape[0], mean.shape[1], mean.shape[1]):
+            raise ValueError(f"mean must be B x q and cov B x q x q, got {tuple(mean.shape)} and {tuple(cov.shape)}")
+        B, q = mean.shape
+        if z.dim() != 2 or z.shape[1] != q:
+            raise ValueError(f"z must be S x {q}, got {tuple(z.shape)}")
+        S = z.shape[0]
+        value = torch.empty((B,), dtype=torch.float64, device=dev)
+        gmean = torch.empty((B, q), dtype=torch.float64, device=dev) if need_grad else None
+        gcov = torch.empty((B, q, q), dtype=torch.float64, device=dev) if need_grad else None
+        info = torch.empty((B,), dtype=torch.int32, device=dev)
+        ap = _capi.McAcqParamsC(kinds[kind], int(bool(fat_relu)), int(bool(fat_max)), 0, float(best_f), float(tau_relu),
+                                float(tau_max))
+        nbytes = ctypes.c_size_t()
+        self._check(self.lib.gpx_mc_acq_workspace_size(B, q, S, ctypes.byref(nbytes)))
+        ws = self.workspace("mc_acq", nbytes.value)
+        self._bind_stream()
+        self._check(self.lib.gpx_mc_acq_f64(self.handle, ctypes.byref(ap), B, q, S, _ptr(mean), _ptr(cov), _ptr(z),
+                                            _ptr(value), _ptr(gmean), _ptr(gcov), _ptr(info), _ptr(ws), ws.numel()))
+        return value, gmean, gcov, info
+
     def argmax_combine(self, vals: torch.Tensor, idx: torch.Tensor):
         """Deterministic (max value, lowest index) over device records (after the cross-rank gather)."""
         vals = vals.to(device=self.device, dtype=torch.float64).contiguous().reshape(-1)

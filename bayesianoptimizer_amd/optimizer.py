@@ -23,7 +23,10 @@ hyperparameters are tied), in which case new observations are folded in by the b
   scrambled-Sobol grid scored on the device, best k by ``gpx_topk_f64``;
 * ``"qlogei"`` (``Bayesian.py:100-112``): ``optimize_acqf`` on MC qLogEI; batches larger than the engine's joint
   q-batch limit (``GPX_MAX_Q``) are built greedily in chunks, each chunk conditioned on the ones before it with their
-  posterior means as fantasy observations (kriging believer).
+  posterior means as fantasy observations (kriging believer); ``GPConfig.qlogei_fat_max`` selects BoTorch's default
+  fat-tailed q-reduction;
+* ``"qpsd"`` (Bayesian6's exact mode, ``Bayesian6.py:896-919``): per output one ``optimize_acqf`` on the MC posterior
+  standard deviation of that output (``acqf.qPosteriorStandardDeviation``), the batch split evenly over the outputs.
 
 The scalar objective the improvement modes maximise is the one ``optimize()`` reports (``_scalar_objective``,
 ``Bayesian7.py:597-609``): the weighted sum (``objective_weights``), one output (``objective_index``) or the sum of
@@ -95,6 +98,8 @@ class GPConfig:
     acqf_raw_samples: int = 1024
     batch_limit: int = 5
     maxiter: int = 200
+    # acquisition="qlogei": BoTorch's default q-reduction (fatmax) instead of tau_max * logsumexp (acqf.fatmax)
+    qlogei_fat_max: bool = False
 
 
 # ---- persistence -----------------------------------------------------------------------------------------------
@@ -154,6 +159,16 @@ class _ResultsTable:
         return table[self.inputs].to_numpy(np.float64), table[self.outputs].to_numpy(np.float64)
 
 
+class _UnitCube:
+    """optimize_acqf searches the unit cube; the GP sees transformed inputs."""
+
+    def __init__(self, inner, model, x_tf):
+        self.inner, self.model, self.x_tf = inner, model, x_tf
+
+    def __call__(self, X):
+        return self.inner(self.x_tf(X.reshape(-1, X.shape[-1])).reshape(X.shape))
+
+
 # ---- optimizer --------------------------------------------------------------------------------------------------
 class BayesianOptimizer:
     def __init__(
@@ -190,7 +205,7 @@ class BayesianOptimizer:
         self.objective_index = kwargs.get("objective_index", None)
         self.objective_weights = kwargs.get("objective_weights", None)
         self.acquisition = str(kwargs.get("acquisition", "variance")).lower()
-        if self.acquisition not in ("variance", "logei", "ei", "ucb", "qlogei"):
+        if self.acquisition not in ("variance", "logei", "ei", "ucb", "qlogei", "qpsd"):
             raise ValueError(f"unknown acquisition '{self.acquisition}'")
         self.seed = kwargs.get("seed", None)
         self._rng = np.random.default_rng(self.seed)
@@ -443,6 +458,8 @@ class BayesianOptimizer:
             return self._pool_scan(k)
         if self.acquisition == "qlogei":
             return self._acquire_qlogei(k)
+        if self.acquisition == "qpsd":
+            return self._acquire_qpsd(k)
         return self._analytic_sweep(k)
 
     def _pool_scan(self, k: int) -> torch.Tensor:
@@ -495,16 +512,9 @@ class BayesianOptimizer:
             q = min(remaining, _capi.GPX_MAX_Q)
             seed = int(self._rng.integers(0, 1 << 30))
             acq = qLogExpectedImprovement(model, best_f=best_f, objective=objective,
-                                          sampler=SobolQMCNormalSampler(torch.Size([cfg.mc_samples]), seed))
-
-            class _UnitCube:  # optimize_acqf searches the unit cube; the GP sees transformed inputs
-                def __init__(self, inner, m):
-                    self.inner, self.model = inner, m
-
-                def __call__(self, X):
-                    return self.inner(x_tf(X.reshape(-1, X.shape[-1])).reshape(X.shape))
-
-            cand, _ = optimize_acqf(_UnitCube(acq, model), unit_box, q=q, num_restarts=cfg.num_restarts,
+                                          sampler=SobolQMCNormalSampler(torch.Size([cfg.mc_samples]), seed),
+                                          fat_max=cfg.qlogei_fat_max)
+            cand, _ = optimize_acqf(_UnitCube(acq, model, x_tf), unit_box, q=q, num_restarts=cfg.num_restarts,
                                     raw_samples=cfg.acqf_raw_samples,
                                     options={"batch_limit": cfg.batch_limit, "maxiter": cfg.maxiter}, seed=seed)
             cand = cand.detach().reshape(q, self.dim)
@@ -515,6 +525,34 @@ class BayesianOptimizer:
                 fantasy = model.posterior(Xf).mean
                 model = ExactGP(torch.cat([model.train_X, Xf]), torch.cat([model.train_Y, fantasy]), model.params,
                                 engine=self.engine, jitter_schedule=model.jitter_schedule).fit()
+        return torch.cat(picked)
+
+    def _acquire_qpsd(self, k: int) -> torch.Tensor:
+        """Bayesian6's exact-mode acquisition (Bayesian6.py:896-919): per output one optimize_acqf on the MC posterior
+        standard deviation of that output (256 Sobol base samples, batch_limit 5, maxiter 100, non-negative
+        initialisation), with the configured restarts and raw samples.  The k points are split over the outputs as
+        evenly as possible, the first k mod T outputs taking one more (the reference's quota heuristic,
+        Bayesian6.py:771-788, is not restated), in chunks of at most GPX_MAX_Q.  Points picked for earlier outputs
+        do not enter later ones: the reference sets them as X_pending, which its custom forward never reads
+        [upstream, unverified]."""
+        from .acqf import SobolQMCNormalSampler, optimize_acqf, qPosteriorStandardDeviation
+
+        cfg = self.config
+        T = self.num_outputs
+        unit_box = torch.stack([torch.zeros(self.dim), torch.ones(self.dim)]).to(self.dtype)
+        picked: List[torch.Tensor] = []
+        for out in range(T):
+            remaining = k // T + (1 if out < k % T else 0)
+            while remaining > 0:
+                q = min(remaining, _capi.GPX_MAX_Q)
+                seed = int(self._rng.integers(0, 1 << 30))
+                acq = qPosteriorStandardDeviation(self.gp_model, SobolQMCNormalSampler(torch.Size([256]), seed),
+                                                  output=out)
+                cand, _ = optimize_acqf(_UnitCube(acq, self.gp_model, self.x_tf), unit_box, q=q,
+                                        num_restarts=cfg.num_restarts, raw_samples=cfg.acqf_raw_samples,
+                                        options={"batch_limit": 5, "maxiter": 100, "nonnegative": True}, seed=seed)
+                picked.append(cand.detach().reshape(q, self.dim))
+                remaining -= q
         return torch.cat(picked)
 
     def optimize_acquisition_function(self, gp=None) -> torch.Tensor:

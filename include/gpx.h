@@ -370,6 +370,46 @@ gpx_status gpx_moments_grad_f64(gpx_handle h, const gpx_kernel_params* p, int64_
                                 int64_t q, int64_t ldxs, double* mean, double* dmean, double* cov, double* dcov,
                                 void* ws, size_t ws_bytes);
 
+/* Monte-Carlo acquisition value of B q-batches from their joint moments (mean B x q, cov B x q x q, as
+ * gpx_moments_grad_f64 gives them after the caller's scaling) and S x q base samples z, with the gradients w.r.t. the
+ * moments: the q x q part of optimize_acqf that follows the moments call.  QLOGEI is qLogExpectedImprovement with
+ * q = batch_size (optimization/Bayesian.py:100-112, optimization/Bayesian2.py:226-245); QPSD is
+ * qPosteriorStandardDeviation of one output (optimization/Bayesian6.py:113-130, 896-919).  Per q-batch b:
+ *   A = (cov + cov^T) / 2 = L L^T; a pivot <= 0 or NaN retries that batch with A + j I, j = 1e-8, 1e-7, 1e-6
+ *   (GPyTorch psd_safe_cholesky for fp64 [upstream, unverified]); info[b] = 0 clean, k = 1..3 factored at retry k,
+ *   -1 not factored: value[b] and the gradients of b are NaN then, the other batches are unaffected.
+ *   f_s = mean + L z_s, y = (f - best_f) / tau_relu
+ *   QLOGEI  li = log tau_relu + log(softplus(y) + 0.1 / (1 + y^2))   (fat_relu = 1; 0: log tau_relu + log softplus(y),
+ *           = y below y <= -37)
+ *           r_s = tau_max logsumexp_i(li / tau_max)                  (fat_max = 0), or with M = max_i li, alpha = 2,
+ *           t_i = 1 + (M - li_i) / (alpha tau_max): r_s = M + tau_max log sum_i t_i^-alpha  (fat_max = 1: BoTorch
+ *           safe_math.fatmax [upstream, unverified])
+ *           value = logsumexp_s r_s - log S
+ *   QPSD    value = sum_i std_s(f_si), the unbiased standard deviation over the samples (S >= 2), in the closed form
+ *           sqrt(l_i C l_i^T) with l_i row i of L and C the unbiased sample covariance of the rows of z; gmean = 0.
+ * gmean = d value / d mean and gcov = d value / d cov, the latter through the symmetrised factorisation (symmetric:
+ * what torch gives for cholesky((cov + cov^T) / 2)).  gmean and gcov are both NULL (value only: raw-sample scoring) or
+ * both set; the value has the same bits either way.  Limits: 1 <= q <= GPX_MAX_Q, B q <= GPX_MAX_GRAD_CANDIDATES,
+ * 1 <= S <= 2^20 (QPSD: S >= 2).  reserved != 0, a flag outside {0, 1}, a tau that is not positive or an unknown kind
+ * is GPX_INVALID_ARG, and nothing is launched.  Device pointers, contiguous fp64; asynchronous on the handle's stream,
+ * no allocation; every sum runs in a fixed order, so two calls give the same bits. */
+enum { GPX_MCACQ_QLOGEI = 0, GPX_MCACQ_QPSD = 1 };
+typedef struct {
+  int32_t kind;     /* GPX_MCACQ_* */
+  int32_t fat_relu; /* QLOGEI: 1 log_fatplus, 0 log_softplus */
+  int32_t fat_max;  /* QLOGEI: 1 fatmax (alpha = 2), 0 tau_max * logsumexp */
+  int32_t reserved; /* must be 0 */
+  double best_f, tau_relu, tau_max;
+} gpx_mcacq_params;
+/* sizeof(gpx_mcacq_params) (40) as compiled into the library, for a binding's load-time check */
+size_t gpx_mcacq_params_size(void);
+gpx_status gpx_mc_acq_workspace_size(int64_t B, int64_t q, int64_t S, size_t* bytes);
+gpx_status gpx_mc_acq_f64(gpx_handle h, const gpx_mcacq_params* a, int64_t B, int64_t q, int64_t S,
+                          const double* mean /* B x q */, const double* cov /* B x q x q */,
+                          const double* z /* S x q base samples */, double* value /* B */,
+                          double* gmean /* B x q or NULL */, double* gcov /* B x q x q or NULL */,
+                          int32_t* info /* B */, void* ws, size_t ws_bytes);
+
 /* ---- cross-GPU selection exchange (SURVEY §8b gpx_allreduce_argmax, §8e) ------------------------------------------ */
 /* One process per GPU.  Rank 0 creates the communicator id (gpx_comm_unique_id), the host side broadcasts its
  * GPX_COMM_ID_BYTES bytes (e.g. over torch.distributed), every rank calls gpx_comm_init (collective).
