@@ -9,8 +9,8 @@ scratch is reported, not fatal.  Compiler warnings in the remarks file are echoe
 import re
 import sys
 
-ASM_TILE_KERNELS = ("trmm_sumsq_kernel", "potrf_step_kernel", "mll_grad_kernel", "svgp_w2_kernel", "trtri_t_kernel",
-                    "trtri_w_kernel")
+ASM_TILE_KERNELS = ("trmm_sumsq_kernel", "trmm_stage_kernel", "trmm_stage_dual_kernel", "potrf_step_kernel",
+                    "mll_grad_kernel", "svgp_w2_kernel", "trtri_t_kernel", "trtri_w_kernel")
 
 
 def main(path: str) -> int:

@@ -1129,6 +1129,43 @@ gpx_status gpx_debug_kstar_mu_f64(gpx_handle h, const gpx_kernel_params* p, int6
                    "debug_kstar_mu");
 }
 
+gpx_status gpx_debug_stage_product_workspace_size(int64_t ncols, size_t* bytes) {
+  if (!bytes || ncols < 1 || ncols > ((int64_t)1 << 20)) return GPX_INVALID_ARG;
+  *bytes = gpx::debug_stage_product_bytes(ncols) + 256;
+  return GPX_OK;
+}
+
+gpx_status gpx_debug_stage_product_f64(gpx_handle h, int64_t n, const double* W, int64_t ldw, const double* kstar,
+                                       int64_t ldk, int64_t ncols, const int32_t* list, int32_t I0, int32_t nrows,
+                                       int32_t shape, double* ss, int64_t ldss, void* ws, size_t ws_bytes) {
+  Context* c = reinterpret_cast<Context*>(h);
+  if (!c) return GPX_INVALID_ARG;
+  GPX_TRY(check_n(c, n));
+  GPX_NONNULL(c, W);
+  GPX_NONNULL(c, kstar);
+  GPX_NONNULL(c, ss);
+  GPX_NONNULL(c, ws);
+  const int64_t npad = padded(n), nI = npad / gpx::TILE;
+  if (ncols < 1 || ncols > ((int64_t)1 << 20)) return fail(c, GPX_INVALID_ARG, "ncols must be in [1, 2^20]");
+  if (I0 < 0 || nrows < 1 || (int64_t)I0 + nrows > nI)
+    return fail(c, GPX_INVALID_ARG, "the stage's row tiles must be I0 >= 0, nrows >= 1, I0 + nrows <= padded n / 128");
+  if (shape != 0 && shape != 1) return fail(c, GPX_INVALID_ARG, "shape must be 0 (wide) or 1 (narrow)");
+  const int64_t cpad = (ncols + gpx::TILE - 1) / gpx::TILE * gpx::TILE;
+  if (ldw < npad || (ldw & 1) || (reinterpret_cast<uintptr_t>(W) & 15))
+    return fail(c, GPX_INVALID_ARG, "W must be 16-byte aligned with an even pitch >= padded n");
+  if (ldk < cpad || (ldk & 1) || (reinterpret_cast<uintptr_t>(kstar) & 15))
+    return fail(c, GPX_INVALID_ARG, "kstar must be 16-byte aligned with an even pitch >= ncols rounded up to 128");
+  if (ldss < cpad) return fail(c, GPX_INVALID_ARG, "ldss must be >= ncols rounded up to 128");
+  size_t need = 0;
+  GPX_TRY(gpx_debug_stage_product_workspace_size(ncols, &need));
+  if (ws_bytes < need) return fail(c, GPX_INVALID_ARG, "debug_stage_product workspace too small");
+  GPX_USE_DEVICE(c);
+  return hip_check(c,
+                   gpx::launch_debug_stage_product(c, (int)npad, W, ldw, kstar, ldk, (int)ncols, list, I0, nrows, shape,
+                                                   ss, ldss, align256(ws)),
+                   "debug_stage_product");
+}
+
 gpx_status gpx_debug_mu_bound_workspace_size(int64_t n, size_t* bytes) {
   if (!bytes || n < 1) return GPX_INVALID_ARG;
   *bytes = gpx::mu_prep_doubles(padded(n), 16) * 8 + 256;

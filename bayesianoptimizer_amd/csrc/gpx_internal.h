@@ -229,6 +229,13 @@ hipError_t launch_debug_kstar(Context* c, const gpx_kernel_params& p, int n, int
                               double* mu_part = nullptr, int64_t ldmu = 0);
 // (alpha != nullptr, gpx_debug_kstar_mu_f64: the build's mean partials too.  Full build: mu_part[jb * ldout + c], no
 // scratch; gather build: mu_part[jb * ldmu + list[s]], the partials KSTAR_FULL gives that candidate, other entries kept.)
+// One stage of the staged product in a named tile shape (gpx_debug_stage_product_f64): row tiles I0 .. I0 + nrows - 1
+// over slots 0 .. ncols - 1 of kstar (pitch ldk), shape 0 wide / 1 narrow, list (device, ncols entries, optional) the
+// slots' output columns; ss[I * ldss + c].  ws: debug_stage_product_bytes(ncols), 256-byte aligned.
+size_t debug_stage_product_bytes(int64_t ncols);
+hipError_t launch_debug_stage_product(Context* c, int npad, const double* W, int64_t ldw, const double* kstar,
+                                      int64_t ldk, int ncols, const int* list, int I0, int nrows, int shape, double* ss,
+                                      int64_t ldss, void* ws);
 // The lazy pruned sweep's bound of the posterior mean (gpx_sweep.hip 1b; RBF, fp64 covariance, d <= 16):
 // mu_approx[c] +- mu_slack[c] holds the exact path's mean of candidate c.  prep: mu_prep_doubles(npad, d) doubles,
 // 256-byte aligned; its first int64 ends up as the count of 256-candidate workgroups on the unfactorised path.

@@ -16,7 +16,8 @@
 // launch_argmax_final reduces the records of the whole sweep in one workgroup.
 //
 // gpx_acquire_argmax_f64 without scores_out takes the PRUNED form of launch 2 (launch_sweep_chunk_pruned):
-// the row tiles run in stages (trmm_stage_kernel); after each stage finalize_kernel mode 4 bounds every active
+// the row tiles run in stages (trmm_stage_kernel; after the first trmm_stage_dual_kernel, whose workgroups take a
+// 128 x 32 tile when the stage has fewer 128 x 128 tiles than the device has CUs); after each stage finalize_kernel mode 4 bounds every active
 // candidate's score from the partials it has, drops those that cannot reach the best score computed in full so far,
 // and prune_compact_kernel gathers the surviving K* columns; finalize scores the survivors of the last stage.  The
 // (value, index) pair has the bits of the full sweep.  Where the MFMA K* build applies, the pruned form is lazy
@@ -902,24 +903,175 @@ struct PruneBufs {
   int2* list1;
   const int2* list2;  // the round's part of the head phase's survivor list (PruneDesc::list = 2)
 };
-// One stage of the pruned sweep (trmm_stage_kernel).
+// One stage of the pruned sweep (trmm_stage_kernel / trmm_stage_dual_kernel).
 struct PruneStage {
   PruneBufs pb;
   const PruneDesc* desc;  // the active columns, written by an earlier launch
   int I0, nrows;          // the stage's row tiles I0 .. I0 + nrows - 1
+  int narrow_below;       // dual kernel: the narrow shape runs when desc->ntiles * nrows is below this (0: never)
 };
+
+// The NARROW shape of the product's tile: 128 rows x 32 columns, a quarter of the wide tile's columns with the same four
+// waves in 2 x 2 (MfmaTile<128, 32, ..>: WM = 4 row blocks, WN = 1, the wide tile's row_of).  A stage that has fewer
+// wide tiles than the device has CUs lasts as long as its deepest tile, one workgroup walking (I + 1) k-ranges of 64
+// MFMAs per wave and k-tile while the other CUs idle; four narrow workgroups compute the same 128 columns with 16 MFMAs
+// per wave and k-tile each.  Bits: a 16 x 16 accumulator block's MFMA chain (k ascending in steps of 4 from 0, lane
+// (kr, m) supplying W[k0 + kr][I*128 + m] and K*[k0 + kr][c]) does not depend on the blocks that share its workgroup,
+// the diagonal 128-block skips the zero row blocks by run_tri's rule, and the column sums are trmm_colsum_store's for
+// both shapes, so a column's partial is the wide tile's.
+// No LDS staging: with 16 MFMAs (~1000 cycles) per k-tile a workgroup cannot cover a load round trip behind one staged
+// tile, and a combined kernel must keep the wide shape's 73,728 B of LDS (two workgroups per CU).  Every wave
+// loads its own fragments straight into registers (each 16-lane row a contiguous 128 bytes of one k-row; the A
+// fragments are read by the two waves of a row half, the B fragment by the two of a column half: L1 / L2 hits) in
+// blocks of one k-tile (16 fragment loads A + 4 B), four blocks in registers: three k-tiles (~3000 cycles of MFMAs)
+// between a block's loads and its use, against ~550 / ~900 cycles of Infinity Cache / HBM latency.  The kernels of this
+// shape are held to 256 registers (__launch_bounds__(WG, 2)): two waves per SIMD, as the wide shape has.  Measured
+// (DESIGN §5): 5.4 us per k-range of 128 against the wide tile's 13.6; the 80 fragment loads per CU and k-tile, not the
+// MFMAs (3.4 us), set the pace.
+constexpr int TNW = 32;
+using NarrowTile = MfmaTile<TT, TNW, 16, true, true>;  // (layout only: row_of / col_of)
+static_assert(NarrowTile::WM == TrmmTile::WM && NarrowTile::WN == 1, "the wide tile's row blocks, one column block");
+struct TrmmNarrow {
+  struct Blk {  // the fragments of one k-tile of 16: substep s, row block i
+    double a[4][4], b[4];
+  };
+  d4 acc[4][1];
+  const double* pa;  // W[kr][I*128 + wm0 + cl], advanced by k-tile
+  const double* pb;  // K*[kr][column wn0 + cl]
+  int64_t lda, ldb;
+
+  // (sched_barrier: hipcc's scheduler otherwise gathers the four blocks' loads at the top of a loop trip and waits for
+  // them there, which exposes a load round trip per trip)
+  __device__ __forceinline__ void load(Blk& f, int kt) const {
+    __builtin_amdgcn_sched_barrier(0);
+    const double* a = pa + (int64_t)kt * 16 * lda;
+    const double* b = pb + (int64_t)kt * 16 * ldb;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) f.a[s][i] = a[(int64_t)(4 * s) * lda + 16 * i];
+      f.b[s] = b[(int64_t)(4 * s) * ldb];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  // SKIP (0 .. 4): the wave's first SKIP row blocks are zero in this k-tile of W (TileT::ktile's rule)
+  template <int SKIP>
+  __device__ __forceinline__ void mm(const Blk& f) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int i = SKIP; i < 4; ++i) acc[i][0] = mfma16x16x4(f.a[s][i], f.b[s], acc[i][0]);
+  }
+  // local k-tile J of the diagonal 128-block: the waves of rows 0-63 (lo = 0) skip their row blocks i < J, the waves of
+  // rows 64-127 (lo = 4) their row blocks i < J - 4 (run_tri's rule)
+  template <int J>
+  __device__ __forceinline__ void mm_diag(const Blk& f, int lo) {
+    if (lo == 0)
+      mm<(J < 4 ? J : 4)>(f);
+    else
+      mm<(J > 4 ? J - 4 : 0)>(f);
+  }
+  // acc = A B over nk k-tiles of 16 (nk a multiple of 8) for an upper-triangular block row A whose last 8 k-tiles are
+  // the diagonal 128-block
+  __device__ __forceinline__ void run(const double* __restrict__ Ag, int64_t lda_, const double* __restrict__ Bg,
+                                      int64_t ldb_, int nk) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, kr = lane >> 4, cl = lane & 15;
+    lda = lda_;
+    ldb = ldb_;
+    pa = Ag + (int64_t)kr * lda + (w >> 1) * (TT / 2) + cl;
+    pb = Bg + (int64_t)kr * ldb + (w & 1) * (TNW / 2) + cl;
+    const int lo = __builtin_amdgcn_readfirstlane(w >> 1) == 0 ? 0 : 4;
+    const int kd = nk - 8;  // first k-tile of the diagonal block
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[i][0] = (d4){0.0, 0.0, 0.0, 0.0};
+    Blk f0, f1, f2, f3;
+    load(f0, 0);
+    load(f1, 1);
+    load(f2, 2);
+    load(f3, 3);
+    for (int kt = 0; kt < kd; kt += 4) {
+      mm<0>(f0);
+      load(f0, kt + 4);
+      mm<0>(f1);
+      load(f1, kt + 5);
+      mm<0>(f2);
+      load(f2, kt + 6);
+      mm<0>(f3);
+      load(f3, kt + 7);
+    }
+    mm_diag<0>(f0, lo);
+    load(f0, kd + 4);
+    mm_diag<1>(f1, lo);
+    load(f1, kd + 5);
+    mm_diag<2>(f2, lo);
+    load(f2, kd + 6);
+    mm_diag<3>(f3, lo);
+    load(f3, kd + 7);
+    mm_diag<4>(f0, lo);
+    mm_diag<5>(f1, lo);
+    mm_diag<6>(f2, lo);
+    mm_diag<7>(f3, lo);
+  }
+};
+
+// Column sums of squares of a 128 x TN tile's accumulators (MfmaTile<128, TN> layout, WN = TN / 32 column blocks per
+// wave) and their store: over the wave's rows (lane-sequential over i, r), then over the lanes holding the same column,
+// then the two waves of each column half through LDS.  One code for both shapes: a column's partial does not depend on
+// the tile's width.  slot0: the tile's first slot; STAGED: slot -> chunk column through list / col0, padding skipped.
+template <int TN, bool STAGED>
+__device__ __forceinline__ void trmm_colsum_store(const d4 (&acc)[4][TN / 32], int I, int64_t C, int64_t slot0,
+                                                  const int2* list, int col0, double* __restrict__ ss_part,
+                                                  double* red) {
+  using L = MfmaTile<TT, TN, 16, true, true>;
+  static_assert(L::WM == 4, "128 rows");
+  double s[L::WN];
+#pragma unroll
+  for (int j = 0; j < L::WN; ++j) {
+    double v = 0.0;
+#pragma unroll
+    for (int i = 0; i < L::WM; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) v += acc[i][j][r] * acc[i][j][r];
+    v += __shfl_xor(v, 16);
+    v += __shfl_xor(v, 32);
+    s[j] = v;
+  }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if ((w >> 1) == 1 && lane < 16) {
+#pragma unroll
+    for (int j = 0; j < L::WN; ++j) red[L::col_of(j)] = s[j];
+  }
+  __syncthreads();
+  if ((w >> 1) == 0 && lane < 16) {
+#pragma unroll
+    for (int j = 0; j < L::WN; ++j) {
+      const int col = L::col_of(j);
+      if constexpr (STAGED) {
+        const int slot = (int)slot0 + col;
+        const int c = list ? list[slot].x : col0 + slot;  // -1: a padding column of the last compact tile
+        if (c >= 0) ss_part[(int64_t)I * C + c] = s[j] + red[col];
+      } else {
+        ss_part[(int64_t)I * C + slot0 + col] = s[j] + red[col];
+      }
+    }
+  }
+}
 
 // kfull = 0: W upper triangular (k < (I+1)*128); kfull = 1: W is a full npad x npad matrix (the SVGP's
 // W2 = L^{-T} S term, gpx_svgp.hip), k over all nI row tiles.
 // With W2 (the SVGP's second product, grid.y = 2): blockIdx.y = 0 runs W2 with kfull = 1 into ss2 (the heavier,
 // full-k tiles dispatched first), blockIdx.y = 1 the product given by (W, ss_part, kfull): both products of a chunk in
 // one launch share its K* and one launch tail (two launches before).
-// STAGED (trmm_stage_kernel, a stage of the pruned sweep): row tiles st.I0 .. st.I0 + st.nrows - 1 of the columns active in
+// STAGED (a stage of the pruned sweep): row tiles st.I0 .. st.I0 + st.nrows - 1 of the columns active in
 // *st.desc.  The grid covers every candidate tile the chunk could still have; workgroups beyond the active tiles
 // return at once.  Same tile, same order (heaviest row tile first, XCD-aware) and, for a column, the same MFMA chain
 // whatever slot of whatever buffer it sits in; its sums go to ss_part at the column's place in the chunk, so the
 // partials of a candidate are the ones the plain product writes.
-template <bool STAGED>
+// SHAPE: TRMM_WIDE the hand-placed 128 x 128 tile; TRMM_NARROW the narrow one over 4 ncb column tiles (ncb counts wide
+// tiles in every shape); TRMM_DUAL (staged) the workgroups read the stage's tile count and take the narrow shape when
+// the wide one would leave CUs without a tile (ncb * nrows < st.narrow_below), each tile as four workgroups.
+enum { TRMM_WIDE = 0, TRMM_NARROW = 1, TRMM_DUAL = 2 };
+template <bool STAGED, int SHAPE>
 __device__ __forceinline__ void trmm_sumsq_body(const double* __restrict__ W, int64_t ldw,
                                                 const double* __restrict__ kstar, int64_t C, int nI, int ncb,
                                                 double* __restrict__ ss_part, int kfull,
@@ -933,6 +1085,7 @@ __device__ __forceinline__ void trmm_sumsq_body(const double* __restrict__ W, in
   int I0 = 0, nrows = nI, col0 = 0;
   int64_t ldb = C;
   const int2* list = nullptr;
+  bool narrow = SHAPE == TRMM_NARROW;
   if constexpr (STAGED) {
     // (the tile's buffer descriptors want base and pitch in scalar registers: make the uniformity explicit)
     const int buf = __builtin_amdgcn_readfirstlane(st.desc->buf);
@@ -941,54 +1094,33 @@ __device__ __forceinline__ void trmm_sumsq_body(const double* __restrict__ W, in
     ncb = __builtin_amdgcn_readfirstlane(st.desc->ntiles);
     I0 = st.I0;
     nrows = st.nrows;
-    if ((int)blockIdx.x >= ncb * nrows) return;
+    if constexpr (SHAPE == TRMM_DUAL) narrow = ncb * nrows < st.narrow_below;
+    if ((int)blockIdx.x >= (narrow ? 4 : 1) * ncb * nrows) return;
     kstar = buf == 0 ? st.pb.kstar : buf == 1 ? st.pb.c1 : st.pb.c2;
     ldb = buf == 0 ? st.pb.ld0 : buf == 1 ? st.pb.ld1 : st.pb.ld2;
     list = li < 0 ? nullptr : li == 2 ? st.pb.list2 : li ? st.pb.list1 : st.pb.list0;
   }
   int l, cb;
-  trmm_tile_order(blockIdx.x, nrows, ncb, l, cb);
-  const int I = I0 + nrows - 1 - l;
-  const double* Ab = W + (int64_t)I * TT;               // A(m=i,k) = W[k][I*128 + i]
-  const double* Bb = kstar + col0 + (int64_t)cb * TT;   // B(k,n=c) = K*[k][col0 + cb*128 + c]
-  // the k loop with a hand-placed instruction stream (gpx_trmm_asm.h; same MFMA sequence per accumulator as
-  // MfmaTile::run, so the same bits); for the triangular W every wave skips the zero 16 x 16 blocks of the diagonal
-  // 128-tile (trmm_asm::TileT::run_tri)
-  trmm_asm::TileTag<STAGED ? 1 : 0> tile;  // (a tag per kernel: gpx_trmm_asm.h TileT)
-  tile.run(Ab, ldw, Bb, ldb, (kfull ? nI : I + 1) * (TT / 16), smem, !kfull);
-  // column sums of squares over this wave's rows, then over the lanes holding the same column
-  double s[TrmmTile::WN];
-#pragma unroll
-  for (int j = 0; j < TrmmTile::WN; ++j) {
-    double v = 0.0;
-#pragma unroll
-    for (int i = 0; i < TrmmTile::WM; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v += tile.acc[i][j][r] * tile.acc[i][j][r];
-    v += __shfl_xor(v, 16);
-    v += __shfl_xor(v, 32);
-    s[j] = v;
+  if (SHAPE != TRMM_WIDE && narrow) {
+    trmm_tile_order(blockIdx.x, nrows, 4 * ncb, l, cb);
+    const int I = I0 + nrows - 1 - l;
+    TrmmNarrow tile;
+    tile.run(W + (int64_t)I * TT, ldw, kstar + col0 + (int64_t)cb * TNW, ldb, (I + 1) * (TT / 16));  // (kfull = 0 only)
+    trmm_colsum_store<TNW, STAGED>(tile.acc, I, C, (int64_t)cb * TNW, list, col0, ss_part, smem);
+    return;
   }
-  // the two waves of each column half (w>>1 = 0, 1) combine through LDS (smem is free after run())
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  double* red = smem;
-  if ((w >> 1) == 1 && lane < 16) {
-#pragma unroll
-    for (int j = 0; j < TrmmTile::WN; ++j) red[TrmmTile::col_of(j)] = s[j];
-  }
-  __syncthreads();
-  if ((w >> 1) == 0 && lane < 16) {
-#pragma unroll
-    for (int j = 0; j < TrmmTile::WN; ++j) {
-      const int col = TrmmTile::col_of(j);
-      if constexpr (STAGED) {
-        const int slot = cb * TT + col;
-        const int c = list ? list[slot].x : col0 + slot;  // -1: a padding column of the last compact tile
-        if (c >= 0) ss_part[(int64_t)I * C + c] = s[j] + red[col];
-      } else {
-        ss_part[(int64_t)I * C + (int64_t)cb * TT + col] = s[j] + red[col];
-      }
-    }
+  if constexpr (SHAPE != TRMM_NARROW) {
+    trmm_tile_order(blockIdx.x, nrows, ncb, l, cb);
+    const int I = I0 + nrows - 1 - l;
+    const double* Ab = W + (int64_t)I * TT;               // A(m=i,k) = W[k][I*128 + i]
+    const double* Bb = kstar + col0 + (int64_t)cb * TT;   // B(k,n=c) = K*[k][col0 + cb*128 + c]
+    // the k loop with a hand-placed instruction stream (gpx_trmm_asm.h; same MFMA sequence per accumulator as
+    // MfmaTile::run, so the same bits); for the triangular W every wave skips the zero 16 x 16 blocks of the diagonal
+    // 128-tile (trmm_asm::TileT::run_tri)
+    trmm_asm::TileTag<SHAPE == TRMM_DUAL ? 2 : STAGED ? 1 : 0> tile;  // (a tag per kernel: gpx_trmm_asm.h TileT)
+    tile.run(Ab, ldw, Bb, ldb, (kfull ? nI : I + 1) * (TT / 16), smem, !kfull);
+    // (smem is free after run())
+    trmm_colsum_store<TT, STAGED>(tile.acc, I, C, (int64_t)cb * TT, list, col0, ss_part, smem);
   }
 }
 
@@ -997,13 +1129,36 @@ trmm_sumsq_kernel(const double* __restrict__ W, int64_t ldw, const double* __res
                   int ncb, double* __restrict__ ss_part, int kfull, const double* __restrict__ W2 = nullptr,
                   double* __restrict__ ss2 = nullptr) {
   __shared__ __attribute__((aligned(16))) double smem[TrmmTile::LDS_DOUBLES];
-  trmm_sumsq_body<false>(W, ldw, kstar, C, nI, ncb, ss_part, kfull, W2, ss2, PruneStage{}, smem);
+  trmm_sumsq_body<false, TRMM_WIDE>(W, ldw, kstar, C, nI, ncb, ss_part, kfull, W2, ss2, PruneStage{}, smem);
 }
+// the plain product on narrow tiles (4 ncb * nI workgroups): the seed block, whose 8 wide column tiles leave the launch
+// as long as its deepest row tile
+__global__ void __launch_bounds__(WG, 2)
+trmm_sumsq_narrow_kernel(const double* __restrict__ W, int64_t ldw, const double* __restrict__ kstar, int64_t C, int nI,
+                         int ncb, double* __restrict__ ss_part) {
+  __shared__ double red[TNW];
+  trmm_sumsq_body<false, TRMM_NARROW>(W, ldw, kstar, C, nI, ncb, ss_part, 0, nullptr, nullptr, PruneStage{}, red);
+}
+// a stage on wide tiles: the first stage of a chunk or super-chunk, never sparse
 __global__ void __launch_bounds__(WG)
 trmm_stage_kernel(const double* __restrict__ W, int64_t ldw, int64_t C, int nI, double* __restrict__ ss_part,
                   PruneStage st) {
   __shared__ __attribute__((aligned(16))) double smem[TrmmTile::LDS_DOUBLES];
-  trmm_sumsq_body<true>(W, ldw, nullptr, C, nI, 0, ss_part, 0, nullptr, nullptr, st, smem);
+  trmm_sumsq_body<true, TRMM_WIDE>(W, ldw, nullptr, C, nI, 0, ss_part, 0, nullptr, nullptr, st, smem);
+}
+// a later stage: either shape, chosen by its workgroups from the stage's tile count (launch_tail_stage)
+__global__ void __launch_bounds__(WG, 2)
+trmm_stage_dual_kernel(const double* __restrict__ W, int64_t ldw, int64_t C, int nI, double* __restrict__ ss_part,
+                       PruneStage st) {
+  __shared__ __attribute__((aligned(16))) double smem[TrmmTile::LDS_DOUBLES];
+  trmm_sumsq_body<true, TRMM_DUAL>(W, ldw, nullptr, C, nI, 0, ss_part, 0, nullptr, nullptr, st, smem);
+}
+// one shape by name, for gpx_debug_stage_product_f64
+__global__ void __launch_bounds__(WG, 2)
+trmm_stage_narrow_kernel(const double* __restrict__ W, int64_t ldw, int64_t C, int nI, double* __restrict__ ss_part,
+                         PruneStage st) {
+  __shared__ double red[TNW];
+  trmm_sumsq_body<true, TRMM_NARROW>(W, ldw, nullptr, C, nI, 0, ss_part, 0, nullptr, nullptr, st, red);
 }
 
 // ---- 1+2 fused, small n (npad <= 256) ----------------------------------------------------------
@@ -1682,6 +1837,29 @@ static int prune_stage_bounds(int nI, int* R) {
   return S;
 }
 
+static int sweep_cu_count(Context* c) {
+  if (c->cu_count <= 0) {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) == hipSuccess &&
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
+      c->cu_count = cus;
+  }
+  return c->cu_count > 0 ? c->cu_count : 0;  // (unknown: the wide shape throughout)
+}
+
+// A stage after the first of a chunk, super-chunk or round: `tiles` wide tiles at most, how many are active only the
+// device knows.  One launch of the dual kernel; its workgroups take the narrow shape when the stage's wide tiles would
+// not give every CU one (trmm_sumsq_body).  The grid is the larger of the two shapes' needs: the narrow shape runs
+// below cus wide tiles only, so it needs fewer than 4 cus workgroups.
+static void launch_tail_stage(Context* c, const double* W, int64_t ldw, int64_t C, int nI, double* ss_part,
+                              PruneStage st, int tiles) {
+  const int cus = sweep_cu_count(c);
+  st.narrow_below = cus;
+  const int64_t wide = (int64_t)tiles * st.nrows;
+  const int64_t narrow = 4 * (wide < cus ? wide : (int64_t)cus);
+  trmm_stage_dual_kernel<<<(unsigned)(wide > narrow ? wide : narrow), WG, 0, c->stream>>>(W, ldw, C, nI, ss_part, st);
+}
+
 hipError_t launch_sweep_chunk_pruned(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X,
                                      int64_t ldx, const double* W, int64_t ldw, const double* alpha, const double* Xs,
                                      int64_t ldxs, int64_t m_chunk, const SweepBuffers& b, const PruneState& ps,
@@ -1715,7 +1893,7 @@ hipError_t launch_sweep_chunk_pruned(Context* c, const gpx_kernel_params& p, int
     prune_init_kernel<<<1, 64, 0, c->stream>>>(ps.desc, ps.count, ps.tau, ps.stats, col0, ncols, R[1], S == 1, first);
     if (seed) {
       const int ncbt = (seed + TT - 1) / TT;
-      trmm_sumsq_kernel<<<ncbt * nI, WG, 0, c->stream>>>(W, ldw, b.kstar, C, nI, ncbt, b.ss_part, 0);
+      trmm_sumsq_narrow_kernel<<<4 * ncbt * nI, WG, 0, c->stream>>>(W, ldw, b.kstar, C, nI, ncbt, b.ss_part);
       host_stats[1] += seed;
       host_stats[2] += (int64_t)ncbt * nI;
     }
@@ -1738,8 +1916,11 @@ hipError_t launch_sweep_chunk_pruned(Context* c, const gpx_kernel_params& p, int
     constexpr int ROWS = 32;  // K* rows a compaction workgroup copies
     const dim3 gc((ncols / 2 + TT + WG - 1) / WG, npad / ROWS);
     for (int s = 0; s < S; ++s) {
-      const PruneStage st{pb, ps.desc + s, R[s], R[s + 1] - R[s]};
-      trmm_stage_kernel<<<tiles * st.nrows, WG, 0, c->stream>>>(W, ldw, C, nI, b.ss_part, st);
+      const PruneStage st{pb, ps.desc + s, R[s], R[s + 1] - R[s], 0};
+      if (s == 0)
+        trmm_stage_kernel<<<tiles * st.nrows, WG, 0, c->stream>>>(W, ldw, C, nI, b.ss_part, st);
+      else
+        launch_tail_stage(c, W, ldw, C, nI, b.ss_part, st, tiles);
       if (s == S - 1) break;
       sel.desc = ps.desc + s;
       sel.count = ps.count + s;
@@ -1803,7 +1984,7 @@ hipError_t launch_sweep_super_pruned(Context* c, const gpx_kernel_params& p, int
     {
       LaunchTimer tm(c, GPX_TIMER_TRMM);
       const int ncbt = (seed + TT - 1) / TT;
-      trmm_sumsq_kernel<<<ncbt * nI, WG, 0, c->stream>>>(W, ldw, b.kstar, C, nI, ncbt, b.ss_part, 0);
+      trmm_sumsq_narrow_kernel<<<4 * ncbt * nI, WG, 0, c->stream>>>(W, ldw, b.kstar, C, nI, ncbt, b.ss_part);
       host_stats[1] += seed;
       host_stats[2] += (int64_t)ncbt * nI;
     }
@@ -1851,7 +2032,7 @@ hipError_t launch_sweep_super_pruned(Context* c, const gpx_kernel_params& p, int
   sel.tau = ps.tau;
   {
     LaunchTimer tm(c, GPX_TIMER_TRMM);
-    const PruneStage st{pb, ps.desc, 0, R[1]};
+    const PruneStage st{pb, ps.desc, 0, R[1], 0};
     trmm_stage_kernel<<<tiles * st.nrows, WG, 0, c->stream>>>(W, ldw, MA, nI, ph.ss_part, st);
     sel.desc = ps.desc;
     sel.count = ps.count;
@@ -1901,8 +2082,8 @@ hipError_t launch_sweep_super_pruned(Context* c, const gpx_kernel_params& p, int
       LaunchTimer tm(c, GPX_TIMER_TRMM);
       const dim3 gc((cap / 2 + TT + WG - 1) / WG, npad / ROWS);
       for (int s = 0; s < ns; ++s) {
-        const PruneStage st{pb, ps.desc + 1 + s, Rr[s], Rr[s + 1] - Rr[s]};
-        trmm_stage_kernel<<<rtiles * st.nrows, WG, 0, c->stream>>>(W, ldw, MA, nI, ph.ss_part, st);
+        const PruneStage st{pb, ps.desc + 1 + s, Rr[s], Rr[s + 1] - Rr[s], 0};
+        launch_tail_stage(c, W, ldw, MA, nI, ph.ss_part, st, rtiles);
         if (s == ns - 1) break;
         sel.desc = ps.desc + 1 + s;
         sel.count = ps.count + 1 + s;
@@ -1921,6 +2102,45 @@ hipError_t launch_sweep_super_pruned(Context* c, const gpx_kernel_params& p, int
                                                    ph.rec_idx + *recs, index_offset, sel);
     *recs += rblocks;
   }
+  return hipGetLastError();
+}
+
+// gpx_debug_stage_product_f64's column set: the descriptor of slots 0 .. ncols - 1 in place and, with a list, its
+// {output column, slot} form padded with -1 to the last wide tile's end.
+__global__ void __launch_bounds__(WG) debug_stage_setup_kernel(PruneDesc* __restrict__ desc, int2* __restrict__ out,
+                                                               const int* __restrict__ list, int ncols, int ntiles) {
+  const int s = blockIdx.x * WG + threadIdx.x;
+  if (s == 0) {
+    PruneDesc d;
+    d.buf = 0;
+    d.col0 = 0;
+    d.ncols = ncols;
+    d.ntiles = ntiles;
+    d.list = list ? 0 : -1;
+    d.pad[0] = d.pad[1] = d.pad[2] = 0;
+    *desc = d;
+  }
+  if (list && s < ntiles * TT) out[s] = make_int2(s < ncols ? list[s] : -1, s);
+}
+
+size_t debug_stage_product_bytes(int64_t ncols) { return 256 + (size_t)((ncols + TT - 1) / TT) * TT * sizeof(int2); }
+
+hipError_t launch_debug_stage_product(Context* c, int npad, const double* W, int64_t ldw, const double* kstar,
+                                      int64_t ldk, int ncols, const int* list, int I0, int nrows, int shape, double* ss,
+                                      int64_t ldss, void* ws) {
+  const int nI = npad / TT, ntiles = (ncols + TT - 1) / TT;
+  PruneDesc* desc = reinterpret_cast<PruneDesc*>(ws);
+  int2* list2 = reinterpret_cast<int2*>(reinterpret_cast<char*>(ws) + 256);
+  debug_stage_setup_kernel<<<(ntiles * TT + WG - 1) / WG, WG, 0, c->stream>>>(desc, list2, list, ncols, ntiles);
+  PruneBufs pb{};
+  pb.kstar = kstar;
+  pb.ld0 = ldk;
+  pb.list0 = list2;
+  const PruneStage st{pb, desc, I0, nrows, 0};
+  if (shape == 0)
+    trmm_stage_kernel<<<ntiles * nrows, WG, 0, c->stream>>>(W, ldw, ldss, nI, ss, st);
+  else
+    trmm_stage_narrow_kernel<<<4 * ntiles * nrows, WG, 0, c->stream>>>(W, ldw, ldss, nI, ss, st);
   return hipGetLastError();
 }
 

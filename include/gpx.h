@@ -524,6 +524,18 @@ gpx_status gpx_debug_mu_bound_workspace_size(int64_t n, size_t* bytes);
 gpx_status gpx_debug_mu_bound_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X, int64_t ldx,
                                   const double* alpha, const double* Xs, int64_t m, int64_t ldxs, double* mu_approx,
                                   double* mu_slack, void* ws, size_t ws_bytes);
+/* One stage of the pruned sweep's product in a named tile shape, for bit checks (no production path uses it; DESIGN
+ * §3): row tiles I0 .. I0 + nrows - 1 of V = W^T K* over slots 0 .. ncols - 1 of a caller's K* buffer.  W: device,
+ * padded_n x padded_n upper triangular (pitch ldw), kstar: device, padded_n rows of pitch ldk >= ncols rounded up to
+ * 128 (the tiles read whole 128-column groups), both 16-byte aligned with even pitches.  shape 0: the wide 128 x 128
+ * tile, 1: the narrow 128 x 32 one.  ss[I * ldss + c] gets the sum over the 128 rows of row tile I of V[.][slot]^2,
+ * c = slot without a list (every slot up to ncols rounded up to 128 is written), else c = list[slot] (device, ncols
+ * entries in [-1, ldss); -1 marks a padding slot, which is not written).  A column has the same bits in either shape.
+ * ws: device, gpx_debug_stage_product_workspace_size bytes.  Asynchronous on the handle's stream, no allocation. */
+gpx_status gpx_debug_stage_product_workspace_size(int64_t ncols, size_t* bytes);
+gpx_status gpx_debug_stage_product_f64(gpx_handle h, int64_t n, const double* W, int64_t ldw, const double* kstar,
+                                       int64_t ldk, int64_t ncols, const int32_t* list, int32_t I0, int32_t nrows,
+                                       int32_t shape, double* ss, int64_t ldss, void* ws, size_t ws_bytes);
 
 #ifdef __cplusplus
 }
