@@ -23,6 +23,7 @@ GPX_TILE = 128
 GPX_MAX_Q = 32
 GPX_MAX_GRAD_CANDIDATES = 16384
 GPX_COMM_ID_BYTES = 128
+GPX_TOPK_SWEEP_MAX = 1024  # largest k of gpx_acquire_topk_f64
 
 GPX_OK, GPX_NOT_PD, GPX_INVALID_ARG, GPX_HIP_ERROR, GPX_RCCL_ERROR, GPX_TIMEOUT = 0, 1, 2, 3, 4, 5
 STATUS_NAMES = {0: "OK", 1: "NOT_PD", 2: "INVALID_ARG", 3: "HIP_ERROR", 4: "RCCL_ERROR", 5: "TIMEOUT"}
@@ -186,6 +187,10 @@ _PROTOS = {
                                          c_int64, c_int64, POINTER(AcqParamsC), c_int64, _p, _p, _p, _p,
                                          c_size_t]),
     "gpx_sweep_stats": (c_int32, [_h, POINTER(c_int64)]),
+    "gpx_acquire_topk_workspace_size": (c_int32, [c_int64, c_int64, c_int64, POINTER(c_size_t)]),
+    "gpx_acquire_topk_f64": (c_int32, [_h, POINTER(KernelParamsC), c_int64, _p, c_int64, _p, c_int64, _p, _p,
+                                       c_int64, c_int64, POINTER(AcqParamsC), c_int64, c_int64, _p, _p, _p,
+                                       c_size_t]),
     "gpx_sweep_multi_workspace_size": (c_int32, [c_int64, c_int64, POINTER(c_size_t)]),
     "gpx_acquire_argmax_multi_f64": (c_int32, [_h, POINTER(KernelParamsC), c_int64, c_int64, _p, c_int64,
                                                POINTER(c_void_p), POINTER(c_int64), POINTER(c_void_p),

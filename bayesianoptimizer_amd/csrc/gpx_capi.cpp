@@ -969,12 +969,16 @@ gpx_status gpx_posterior_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n
   return GPX_OK;
 }
 
-gpx_status gpx_acquire_argmax_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X, int64_t ldx,
-                                  const double* W, int64_t ldw, const double* alpha, const double* Xs, int64_t m,
-                                  int64_t ldxs, const gpx_acq_params* a, int64_t index_offset, double* best_val,
-                                  int64_t* best_idx, double* scores_out, void* ws, size_t ws_bytes) {
+// gpx_acquire_argmax_f64 (k = 0: best_val / best_idx, optional scores_out) and gpx_acquire_topk_f64 (k >= 1: val_out /
+// idx_out, the top-k part of the workspace behind the sweep's) share validation, chunking and counters.
+static gpx_status acquire_impl(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X, int64_t ldx,
+                               const double* W, int64_t ldw, const double* alpha, const double* Xs, int64_t m,
+                               int64_t ldxs, const gpx_acq_params* a, int64_t index_offset, double* best_val,
+                               int64_t* best_idx, double* scores_out, void* ws, size_t ws_bytes, int64_t k,
+                               double* val_out, int64_t* idx_out) {
   Context* c = reinterpret_cast<Context*>(h);
   if (!c) return GPX_INVALID_ARG;
+  const bool topk = val_out || idx_out || k != 0;
   GPX_TRY(check_params(c, p));
   GPX_TRY(check_n(c, n));
   if (m < 1) return fail(c, GPX_INVALID_ARG, "m must be >= 1");
@@ -988,16 +992,36 @@ gpx_status gpx_acquire_argmax_f64(gpx_handle h, const gpx_kernel_params* p, int6
   GPX_NONNULL(c, W);
   GPX_NONNULL(c, alpha);
   GPX_NONNULL(c, Xs);
-  GPX_NONNULL(c, best_val);
-  GPX_NONNULL(c, best_idx);
+  if (topk) {
+    if (k < 1 || k > m || k > GPX_TOPK_SWEEP_MAX)
+      return fail(c, GPX_INVALID_ARG, "k must be in [1, min(m, GPX_TOPK_SWEEP_MAX)]");
+    GPX_NONNULL(c, val_out);
+    GPX_NONNULL(c, idx_out);
+  } else {
+    GPX_NONNULL(c, best_val);
+    GPX_NONNULL(c, best_idx);
+  }
   const int64_t npad = padded(n);
   GPX_TRY(check_ld(c, ldx, p->d, "X", false));
   GPX_TRY(check_ld(c, ldw, npad, "W", true));
   GPX_TRY(check_ld(c, ldxs, p->d, "Xs", false));
   gpx::SweepBuffers b;
-  GPX_TRY(carve_sweep(c, npad, 1, m, ws, ws_bytes, &b));
+  gpx::TopkSweep tks;
+  const gpx::TopkSweep* tk = nullptr;
+  if (topk) {
+    const size_t sweep_bytes = gpx::sweep_workspace_bytes(npad, 1, m);
+    if (ws && ws_bytes < sweep_bytes + gpx::topk_sweep_bytes(npad, m, k))
+      return fail(c, GPX_INVALID_ARG, "acquire_topk workspace too small");
+    GPX_TRY(carve_sweep(c, npad, 1, m, ws, ws_bytes, &b));
+    gpx::topk_sweep_carve(reinterpret_cast<char*>(ws) + sweep_bytes, npad, m, k, &tks);
+  } else {
+    GPX_TRY(carve_sweep(c, npad, 1, m, ws, ws_bytes, &b));
+  }
   // scores_out wants every score: the full sweep
   const bool prune = !scores_out && gpx::sweep_prune_ok(c, *p, (int)npad);
+  if (topk && prune) tk = &tks;
+  // the top-k call where the pruned sweep does not apply: the full sweep into its own score array, then the sort
+  if (topk && !prune) scores_out = tks.scores;
   // the MFMA K* build's configurations take the lazy form (K* in full height for the first tile's survivors only)
   const bool lazy = prune && gpx::sweep_lazy_ok(*p);
   gpx::PruneState ps;
@@ -1023,9 +1047,10 @@ gpx_status gpx_acquire_argmax_f64(gpx_handle h, const gpx_kernel_params* p, int6
       GPX_TRY(hip_check(c,
                         gpx::launch_sweep_super_pruned(c, *p, (int)n, (int)npad, X, ldx, W, ldw, alpha, Xs + s * ldxs,
                                                        ldxs, ms, b, ps, ph, a, &rec, index_offset + s, s == 0,
-                                                       c->sweep_stats),
+                                                       c->sweep_stats, tk),
                         "acquire"));
     }
+    if (tk) return hip_check(c, gpx::launch_topk_result(c, *tk, val_out, idx_out), "topk result");
     return hip_check(c, gpx::launch_argmax_final(c, ph.rec_val, ph.rec_idx, rec, best_val, best_idx), "argmax");
   }
   for (int64_t s = 0; s < m; s += b.chunk) {
@@ -1034,7 +1059,7 @@ gpx_status gpx_acquire_argmax_f64(gpx_handle h, const gpx_kernel_params* p, int6
     GPX_TRY(hip_check(c,
                       prune ? gpx::launch_sweep_chunk_pruned(c, *p, (int)n, (int)npad, X, ldx, W, ldw, alpha,
                                                              Xs + s * ldxs, ldxs, mc, b, ps, a, rec, index_offset + s,
-                                                             s == 0, c->sweep_stats)
+                                                             s == 0, c->sweep_stats, tk)
                             : gpx::launch_sweep_chunk(c, *p, (int)n, (int)npad, X, ldx, W, ldw, alpha, 1,
                                                       Xs + s * ldxs, ldxs, mc, b, 1, a, nullptr, nullptr, nullptr, 0,
                                                       nullptr, scores_out ? scores_out + s : nullptr, rec,
@@ -1043,7 +1068,36 @@ gpx_status gpx_acquire_argmax_f64(gpx_handle h, const gpx_kernel_params* p, int6
     rec += (mc + 255) / 256;
   }
   if (!prune) c->sweep_stats[2] = c->sweep_stats[3];
+  if (tk) return hip_check(c, gpx::launch_topk_result(c, *tk, val_out, idx_out), "topk result");
+  if (topk) {
+    GPX_TRY(hip_check(c, gpx::launch_topk(c, tks.scores, m, k, idx_out, val_out, tks.sort_ws, tks.sort_bytes), "topk"));
+    return hip_check(c, gpx::launch_index_shift(c, idx_out, k, index_offset), "topk indices");
+  }
   return hip_check(c, gpx::launch_argmax_final(c, b.rec_val, b.rec_idx, rec, best_val, best_idx), "argmax");
+}
+
+gpx_status gpx_acquire_argmax_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X, int64_t ldx,
+                                  const double* W, int64_t ldw, const double* alpha, const double* Xs, int64_t m,
+                                  int64_t ldxs, const gpx_acq_params* a, int64_t index_offset, double* best_val,
+                                  int64_t* best_idx, double* scores_out, void* ws, size_t ws_bytes) {
+  return acquire_impl(h, p, n, X, ldx, W, ldw, alpha, Xs, m, ldxs, a, index_offset, best_val, best_idx, scores_out, ws,
+                      ws_bytes, 0, nullptr, nullptr);
+}
+
+gpx_status gpx_acquire_topk_workspace_size(int64_t n, int64_t m, int64_t k, size_t* bytes) {
+  if (!bytes || n < 1 || m < 1 || k < 1 || k > m || k > GPX_TOPK_SWEEP_MAX) return GPX_INVALID_ARG;
+  const int64_t npad = padded(n);
+  *bytes = gpx::sweep_workspace_bytes(npad, 1, m) + gpx::topk_sweep_bytes(npad, m, k);
+  return GPX_OK;
+}
+
+gpx_status gpx_acquire_topk_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X, int64_t ldx,
+                                const double* W, int64_t ldw, const double* alpha, const double* Xs, int64_t m,
+                                int64_t ldxs, const gpx_acq_params* a, int64_t index_offset, int64_t k, double* val_out,
+                                int64_t* idx_out, void* ws, size_t ws_bytes) {
+  if (h && k == 0) return fail(reinterpret_cast<Context*>(h), GPX_INVALID_ARG, "k must be >= 1");
+  return acquire_impl(h, p, n, X, ldx, W, ldw, alpha, Xs, m, ldxs, a, index_offset, nullptr, nullptr, nullptr, ws,
+                      ws_bytes, k, val_out, idx_out);
 }
 
 gpx_status gpx_sweep_stats(gpx_handle h, int64_t* out) {

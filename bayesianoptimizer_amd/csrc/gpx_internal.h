@@ -189,16 +189,38 @@ struct PruneState {  // device pointers into the sweep workspace
 };
 size_t sweep_prune_bytes(int64_t npad, int64_t m);
 void sweep_prune_carve(void* base, int64_t npad, int64_t C, PruneState* ps);
+// The top-k form of the pruned sweep (gpx_acquire_topk_f64): device pointers into the call's top-k workspace.
+// Every launch that scores candidates in full appends their (score, global index) to the scored list, and
+// topk_pool_kernel, enqueued behind it, merges the list into the pool of the k best pairs so far and sets the incumbent
+// to the pool's k-th score (-inf while the pool holds fewer than k).  nullptr in the launch functions: the argmax form.
+static_assert(GPX_TOPK_SWEEP_MAX == PRUNE_SEED, "the seed block fills the pool for every legal k");
+struct TopkSweep {
+  int k;
+  int* head;          // [0] entries in the scored list, [1] entries in the pool
+  double* pool_val;   // k pairs in the result's order (score descending, index ascending)
+  int64_t* pool_idx;
+  double* list_val;   // the scored list: one entry per candidate a launch can score in full (sweep_chunk_size)
+  int64_t* list_idx;
+  double* scores;     // the composed path's score array (m) and its top-k workspace
+  void* sort_ws;
+  size_t sort_bytes;
+};
+size_t topk_sweep_bytes(int64_t npad, int64_t m, int64_t k);
+void topk_sweep_carve(void* base, int64_t npad, int64_t m, int64_t k, TopkSweep* tk);
+// the pool's pairs to the caller's arrays (pruned path) / the composed path's local indices to global ones
+hipError_t launch_topk_result(Context* c, const TopkSweep& tk, double* val_out, int64_t* idx_out);
+hipError_t launch_index_shift(Context* c, int64_t* idx, int64_t k, int64_t offset);
 bool sweep_fused_ok(const Context* c, const gpx_kernel_params& p, int npad, int nrhs);
 // the pruned path applies: unfused sweep, padded n >= the option's threshold (the caller excludes scores_out != NULL)
 bool sweep_prune_ok(const Context* c, const gpx_kernel_params& p, int npad);
 // One chunk of gpx_acquire_argmax_f64 through the staged product; first: the call's first chunk (resets the incumbent
-// and the counters, scores the seed block in full).  host_stats[1], [2] gain the seed block's share.
+// and the counters, scores the seed block in full).  host_stats[1], [2] gain the seed block's share.  tk: the top-k form
+// (gpx_acquire_topk_f64): same launches, the incumbent is the k-th best exact score instead of the best.
 hipError_t launch_sweep_chunk_pruned(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X,
                                      int64_t ldx, const double* W, int64_t ldw, const double* alpha, const double* Xs,
                                      int64_t ldxs, int64_t m_chunk, const SweepBuffers& b, const PruneState& ps,
                                      const gpx_acq_params* a, int64_t rec_offset, int64_t index_offset, bool first,
-                                     int64_t* host_stats);
+                                     int64_t* host_stats, const TopkSweep* tk = nullptr);
 // The lazy form (launch_sweep_super_pruned): K* in full height only for the survivors of the first row tile.
 constexpr int PRUNE_HEAD_ROWS = 128;  // K* rows the head phase stores: the product's first row tile
 struct PruneHead {    // device pointers into the sweep workspace, after the compact buffers
@@ -220,7 +242,7 @@ hipError_t launch_sweep_super_pruned(Context* c, const gpx_kernel_params& p, int
                                      int64_t ldx, const double* W, int64_t ldw, const double* alpha, const double* Xs,
                                      int64_t ldxs, int64_t m_super, const SweepBuffers& b, const PruneState& ps,
                                      const PruneHead& ph, const gpx_acq_params* a, int64_t* recs, int64_t index_offset,
-                                     bool first, int64_t* host_stats);
+                                     bool first, int64_t* host_stats, const TopkSweep* tk = nullptr);
 // K(X, Xs) through the sweep's K* build (gpx_debug_kstar_f64): list = nullptr the full-store build of columns 0 .. m-1,
 // else the gather build of columns list[0 .. *count - 1] (m: the most the list can hold).  out: npad rows of pitch ldout.
 hipError_t launch_debug_kstar(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X, int64_t ldx,

@@ -23,6 +23,7 @@
 // (value, index) pair has the bits of the full sweep.  Where the MFMA K* build applies, the pruned form is lazy
 // (launch_sweep_super_pruned): K* rows 0 .. 127 and the mean partials for every candidate of a super-chunk, the first
 // stage and its bound pass as one launch each, and full-height K* columns rebuilt from the survivor list for the rest.
+// gpx_acquire_topk_f64 is the same pruned sweep with the k-th best exact score as its incumbent (topk_pool_kernel).
 #include "gpx_internal.h"
 #include "gpx_device.h"
 #include "gpx_trmm_asm.h"
@@ -1333,6 +1334,11 @@ struct PruneSel {
   const int2* list2;  // read only (PruneDesc::list = 2); its survivors go to list0
   const double* mu_bound;  // mode 4, the lazy head's pass: mu_approx at [c], mu_slack at [C + c] (mu_bound_kernel) stand
                            // in for the mean partials
+  // the top-k form (gpx_acquire_topk_f64; null everywhere else): mode 1 appends every valid candidate's (score, global
+  // index) to the scored list and leaves the incumbent alone (tau = nullptr): topk_pool_kernel sets it
+  double* sc_val;
+  int64_t* sc_idx;
+  int* sc_count;
 };
 constexpr double PRUNE_EPS = 1e-9;  // margin of the bound test over acq_score's rounding
 
@@ -1422,6 +1428,22 @@ __global__ void __launch_bounds__(WG) finalize_kernel(FinalizeArgs fa, int mode,
     if (keep) survivors[base + __popcll(mask & ((1ull << lane) - 1))] = make_int2((int)c, (int)t);
     return;
   }
+  if (ps.sc_count) {
+    // the top-k form's scored list, as mode 4's survivors: one ballot and one atomic add per wave, any slot order.  The
+    // value is gpx_topk_f64's key of the score (NaN is -inf already, -0 becomes +0)
+    const unsigned long long mask = __ballot(valid);
+    if (mask != 0) {
+      const int lane = threadIdx.x & 63;
+      int base = 0;
+      if (lane == 0) base = atomicAdd(ps.sc_count, __popcll(mask));
+      base = __shfl(base, 0);
+      if (valid) {
+        const int slot = base + __popcll(mask & ((1ull << lane) - 1));
+        ps.sc_val[slot] = score + 0.0;
+        ps.sc_idx[slot] = index_base + c;
+      }
+    }
+  }
   // block argmax
   double bv = score;
   int64_t bi = valid ? index_base + c : INT64_MAX;
@@ -1448,11 +1470,13 @@ __global__ void __launch_bounds__(WG) finalize_kernel(FinalizeArgs fa, int mode,
 }
 
 // The pruned sweep's per-chunk reset (one thread): the first stage's column set (the chunk's columns from col0 on, in
-// place), zero survivor counts, and on the call's first chunk the incumbent (-inf) and the counters.
+// place), zero survivor counts, and on the call's first chunk the incumbent (-inf), the counters and, in the top-k form
+// (tk_head), the scored list's and the pool's counts.
 __global__ void prune_init_kernel(PruneDesc* __restrict__ desc, int* __restrict__ count,
                                   unsigned long long* __restrict__ tau, int64_t* __restrict__ stats, int col0,
-                                  int ncols, int rows0, int last, int first) {
+                                  int ncols, int rows0, int last, int first, int* __restrict__ tk_head) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  if (first && tk_head) tk_head[0] = tk_head[1] = 0;  // the top-k form: empty scored list, empty pool
   PruneDesc d;
   d.buf = 0;
   d.col0 = col0;
@@ -1548,6 +1572,139 @@ __global__ void __launch_bounds__(WG) argmax_final_kernel(const double* __restri
   }
 }
 
+// ---- the top-k form of the pruned sweep (gpx_acquire_topk_f64) ---------------------------------------
+// The result's order: larger score first, equal scores -> lower index (gpx_topk_f64's stable descending sort of its
+// keys; the list's values are those keys, so no NaN and no -0 gets here).  Indices are distinct, so the order is total
+// and the k best of a set do not depend on the order its members arrive in.
+__device__ __forceinline__ bool topk_before(double va, int64_t ia, double vb, int64_t ib) {
+  return va > vb || (va == vb && ia < ib);
+}
+constexpr int TOPK_LDS = 2 * GPX_TOPK_SWEEP_MAX;  // entries of the merge buffer: the pool and as many new ones
+
+// One workgroup, enqueued behind every launch that scores candidates in full (finalize_kernel mode 1 with a scored
+// list): merges the list's n entries into the pool of the k best (score, index) pairs scored so far, empties the list
+// and sets the incumbent of the bound passes that follow:
+//     tau = the pool's k-th score once the pool holds k pairs, else -inf.
+// Soundness.  tau is the k-th best of a subset of the call's exact scores, hence <= the k-th best of all of them.  The
+// bound pass (mode 4) drops a candidate only if ub + PRUNE_EPS (|ub| + |tau| + 1) < tau with ub >= its exact score: a
+// dropped candidate scores strictly below k candidates scored in full, so it is not among the call's k best and does
+// not tie with the k-th; a candidate that ties the k-th place is always scored, and the lowest index wins it in the
+// merge.  Every member of the final k best is therefore scored in full and passes through a merge: the pool at the end
+// of the call is the answer.  With k = 1 tau takes the values the argmax form's atomicMax gives it.
+// Entries that cannot enter a full pool (not before its k-th pair) are filtered by a ballot pass before anything is
+// sorted: after the seed block that is almost all of them, so an unprunable round costs a read of its list.  What is
+// left is appended behind the pool in LDS and merged by a bitonic sort over the next power of two (at most TOPK_LDS
+// pairs, 32 KB), in batches when a launch produced more than the buffer takes.  No hand-off between workgroups: the
+// launch boundaries of the stream order list, pool and incumbent.  An empty list returns at once.
+__global__ void __launch_bounds__(WG) topk_pool_kernel(int k, int cap, int* __restrict__ head,
+                                                       double* __restrict__ pool_val, int64_t* __restrict__ pool_idx,
+                                                       const double* __restrict__ list_val,
+                                                       const int64_t* __restrict__ list_idx,
+                                                       unsigned long long* __restrict__ tau) {
+  __shared__ double sv[TOPK_LDS];
+  __shared__ int64_t si[TOPK_LDS];
+  __shared__ int wcnt[WG / 64];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  int n = head[0];
+  if (n <= 0) return;
+  n = n < cap ? n : cap;
+  int pn = head[1];
+  pn = pn < 0 ? 0 : pn < k ? pn : k;
+  for (int e = t; e < pn; e += WG) {
+    sv[e] = pool_val[e];
+    si[e] = pool_idx[e];
+  }
+  __syncthreads();
+  int fill = 0;  // new entries behind the pool (uniform)
+  bool merged = false;
+  // pool + new entries -> sorted, the best min(k, all) of them the new pool
+  auto merge = [&]() {
+    const int total = pn + fill;
+    int P = 2;
+    while (P < total) P <<= 1;
+    for (int e = total + t; e < P; e += WG) {
+      sv[e] = -INFINITY;
+      si[e] = INT64_MAX;  // behind every real pair
+    }
+    __syncthreads();
+    for (int size = 2; size <= P; size <<= 1)
+      for (int stride = size >> 1; stride > 0; stride >>= 1) {
+        for (int e = t; e < P / 2; e += WG) {
+          const int lo = 2 * e - (e & (stride - 1)), hi = lo + stride;
+          const double vl = sv[lo], vh = sv[hi];
+          const int64_t il = si[lo], ih = si[hi];
+          const bool up = (lo & size) == 0;
+          if (up ? topk_before(vh, ih, vl, il) : topk_before(vl, il, vh, ih)) {
+            sv[lo] = vh, si[lo] = ih;
+            sv[hi] = vl, si[hi] = il;
+          }
+        }
+        __syncthreads();
+      }
+    pn = total < k ? total : k;
+    fill = 0;
+    merged = true;
+  };
+  for (int base = 0; base < n; base += WG) {
+    const int e = base + t;
+    bool take = e < n;
+    double v = 0.0;
+    int64_t i = 0;
+    if (take) {
+      v = list_val[e];
+      i = list_idx[e];
+      if (pn == k) take = topk_before(v, i, sv[k - 1], si[k - 1]);
+    }
+    const unsigned long long mask = __ballot(take);
+    if (lane == 0) wcnt[w] = __popcll(mask);
+    __syncthreads();
+    int off = pn + fill, tot = 0;
+    for (int q = 0; q < WG / 64; ++q) {
+      if (q < w) off += wcnt[q];
+      tot += wcnt[q];
+    }
+    if (take) {
+      const int slot = off + __popcll(mask & ((1ull << lane) - 1));
+      sv[slot] = v;
+      si[slot] = i;
+    }
+    fill += tot;
+    __syncthreads();
+    if (pn + fill > TOPK_LDS - WG) merge();  // (the next pass could overflow the buffer)
+  }
+  if (fill) merge();
+  if (merged) {
+    for (int e = t; e < pn; e += WG) {
+      pool_val[e] = sv[e];
+      pool_idx[e] = si[e];
+    }
+  }
+  if (t == 0) {
+    head[0] = 0;
+    if (merged) {
+      head[1] = pn;
+      *tau = tau_key(pn == k ? sv[k - 1] : -INFINITY);
+    }
+  }
+}
+
+__global__ void __launch_bounds__(WG) topk_result_kernel(int k, const int* __restrict__ head,
+                                                         const double* __restrict__ pool_val,
+                                                         const int64_t* __restrict__ pool_idx,
+                                                         double* __restrict__ val_out, int64_t* __restrict__ idx_out) {
+  const int e = blockIdx.x * WG + threadIdx.x;
+  if (e >= k) return;
+  // (the pool is full at the end of a call: k <= the seed block <= the candidates scored in full)
+  const bool have = e < head[1];
+  val_out[e] = have ? pool_val[e] : -INFINITY;
+  idx_out[e] = have ? pool_idx[e] : INT64_MAX;
+}
+
+__global__ void __launch_bounds__(WG) index_shift_kernel(int64_t* __restrict__ idx, int64_t k, int64_t offset) {
+  const int64_t e = (int64_t)blockIdx.x * WG + threadIdx.x;
+  if (e < k) idx[e] += offset;
+}
+
 // ---- host side -------------------------------------------------------------------------------------------
 int64_t sweep_chunk_size(int64_t npad, int64_t m) {
   // K* chunk of at most ~1 GiB, multiple of 256 candidates (tools/chunk_sweep.sh at n = 4096: 256 MiB / 8192
@@ -1641,6 +1798,63 @@ void sweep_prune_carve_head(const PruneState& ps, int64_t npad, int64_t C, int64
   ph->ss_part = ph->mu_part + (size_t)(npad / NB) * MA;
   ph->rec_val = ph->ss_part + (size_t)(npad / TT) * MA;
   ph->rec_idx = reinterpret_cast<int64_t*>(ph->rec_val + sweep_lazy_records(npad, m));
+}
+
+// The top-k part of gpx_acquire_topk_f64's workspace, behind the sweep workspace: header (256 bytes), pool (k pairs),
+// scored list (a pair per candidate of a chunk: no launch scores more in full), then what the composed path needs: m
+// scores and gpx_topk_f64's workspace.  Every part rounded up to 256 bytes.
+static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+size_t topk_sweep_bytes(int64_t npad, int64_t m, int64_t k) {
+  const int64_t C = sweep_chunk_size(npad, m);
+  return 256 + 256 + 2 * up256((size_t)k * 8) + 2 * up256((size_t)C * 8) + up256((size_t)m * 8) +
+         topk_workspace_bytes(m);
+}
+void topk_sweep_carve(void* base, int64_t npad, int64_t m, int64_t k, TopkSweep* tk) {
+  const int64_t C = sweep_chunk_size(npad, m);
+  char* q = reinterpret_cast<char*>(((uintptr_t)base + 255) & ~(uintptr_t)255);
+  tk->k = (int)k;
+  tk->head = reinterpret_cast<int*>(q);
+  q += 256;
+  tk->pool_val = reinterpret_cast<double*>(q);
+  q += up256((size_t)k * 8);
+  tk->pool_idx = reinterpret_cast<int64_t*>(q);
+  q += up256((size_t)k * 8);
+  tk->list_val = reinterpret_cast<double*>(q);
+  q += up256((size_t)C * 8);
+  tk->list_idx = reinterpret_cast<int64_t*>(q);
+  q += up256((size_t)C * 8);
+  tk->scores = reinterpret_cast<double*>(q);
+  q += up256((size_t)m * 8);
+  tk->sort_ws = q;
+  tk->sort_bytes = topk_workspace_bytes(m);
+}
+
+// finalize_kernel mode 1's view of a scoring launch: the argmax form raises the incumbent itself, the top-k form feeds
+// the scored list and leaves the incumbent to topk_pool_kernel
+static PruneSel score_sel(PruneSel sel, const PruneState& ps, const TopkSweep* tk) {
+  sel.count = nullptr;
+  sel.tau = tk ? nullptr : ps.tau;
+  if (tk) {
+    sel.sc_val = tk->list_val;
+    sel.sc_idx = tk->list_idx;
+    sel.sc_count = tk->head;
+  }
+  return sel;
+}
+static void launch_topk_pool(Context* c, const PruneState& ps, const TopkSweep* tk, int64_t C) {
+  if (!tk) return;
+  topk_pool_kernel<<<1, WG, 0, c->stream>>>(tk->k, (int)C, tk->head, tk->pool_val, tk->pool_idx, tk->list_val,
+                                            tk->list_idx, ps.tau);
+}
+hipError_t launch_topk_result(Context* c, const TopkSweep& tk, double* val_out, int64_t* idx_out) {
+  LaunchTimer tm(c, GPX_TIMER_ACQ);
+  topk_result_kernel<<<(tk.k + WG - 1) / WG, WG, 0, c->stream>>>(tk.k, tk.head, tk.pool_val, tk.pool_idx, val_out,
+                                                                 idx_out);
+  return hipGetLastError();
+}
+hipError_t launch_index_shift(Context* c, int64_t* idx, int64_t k, int64_t offset) {
+  index_shift_kernel<<<(unsigned)((k + WG - 1) / WG), WG, 0, c->stream>>>(idx, k, offset);
+  return hipGetLastError();
 }
 
 
@@ -1864,7 +2078,7 @@ hipError_t launch_sweep_chunk_pruned(Context* c, const gpx_kernel_params& p, int
                                      int64_t ldx, const double* W, int64_t ldw, const double* alpha, const double* Xs,
                                      int64_t ldxs, int64_t m_chunk, const SweepBuffers& b, const PruneState& ps,
                                      const gpx_acq_params* a, int64_t rec_offset, int64_t index_offset, bool first,
-                                     int64_t* host_stats) {
+                                     int64_t* host_stats, const TopkSweep* tk) {
   const int64_t C = b.chunk;
   const int nJB = npad / NB, nI = npad / TT;
   int R[PRUNE_MAX_STAGES];
@@ -1890,7 +2104,8 @@ hipError_t launch_sweep_chunk_pruned(Context* c, const gpx_kernel_params& p, int
   pb.list2 = nullptr;
   {
     LaunchTimer tm(c, GPX_TIMER_TRMM);
-    prune_init_kernel<<<1, 64, 0, c->stream>>>(ps.desc, ps.count, ps.tau, ps.stats, col0, ncols, R[1], S == 1, first);
+    prune_init_kernel<<<1, 64, 0, c->stream>>>(ps.desc, ps.count, ps.tau, ps.stats, col0, ncols, R[1], S == 1, first,
+                                               tk ? tk->head : nullptr);
     if (seed) {
       const int ncbt = (seed + TT - 1) / TT;
       trmm_sumsq_narrow_kernel<<<4 * ncbt * nI, WG, 0, c->stream>>>(W, ldw, b.kstar, C, nI, ncbt, b.ss_part);
@@ -1900,11 +2115,11 @@ hipError_t launch_sweep_chunk_pruned(Context* c, const gpx_kernel_params& p, int
   }
   if (seed) {
     LaunchTimer tm(c, GPX_TIMER_ACQ);
-    PruneSel sel{};
-    sel.tau = ps.tau;
     finalize_kernel<<<seed_blocks, WG, 0, c->stream>>>(fa, 1, Xs, ldxs, seed, C, 1, nJB, nI, b.mu_part, b.ss_part,
                                                        nullptr, 0, nullptr, nullptr, b.rec_val + rec_offset,
-                                                       b.rec_idx + rec_offset, index_offset, sel);
+                                                       b.rec_idx + rec_offset, index_offset,
+                                                       score_sel(PruneSel{}, ps, tk));
+    launch_topk_pool(c, ps, tk, C);
   }
   if (ncols == 0) return hipGetLastError();
   PruneSel sel{};
@@ -1934,10 +2149,11 @@ hipError_t launch_sweep_chunk_pruned(Context* c, const gpx_kernel_params& p, int
   {
     LaunchTimer tm(c, GPX_TIMER_ACQ);
     sel.desc = ps.desc + S - 1;
-    sel.count = nullptr;
     finalize_kernel<<<blocks, WG, 0, c->stream>>>(fa, 1, Xs, ldxs, m_chunk, C, 1, nJB, nI, b.mu_part, b.ss_part,
                                                   nullptr, 0, nullptr, nullptr, b.rec_val + rec_offset + seed_blocks,
-                                                  b.rec_idx + rec_offset + seed_blocks, index_offset, sel);
+                                                  b.rec_idx + rec_offset + seed_blocks, index_offset,
+                                                  score_sel(sel, ps, tk));
+    launch_topk_pool(c, ps, tk, C);
   }
   return hipGetLastError();
 }
@@ -1961,7 +2177,7 @@ hipError_t launch_sweep_super_pruned(Context* c, const gpx_kernel_params& p, int
                                      int64_t ldx, const double* W, int64_t ldw, const double* alpha, const double* Xs,
                                      int64_t ldxs, int64_t m_super, const SweepBuffers& b, const PruneState& ps,
                                      const PruneHead& ph, const gpx_acq_params* a, int64_t* recs, int64_t index_offset,
-                                     bool first, int64_t* host_stats) {
+                                     bool first, int64_t* host_stats, const TopkSweep* tk) {
   const bool mu_bound = c->sweep_prune != -2 && sweep_mu_bound_ok(p);
   const int64_t C = b.chunk, MA = ph.super;
   const int nJB = npad / NB, nI = npad / TT;
@@ -1977,7 +2193,8 @@ hipError_t launch_sweep_super_pruned(Context* c, const gpx_kernel_params& p, int
   const int tiles = (ncols + TT - 1) / TT, blocks = (ncols + WG - 1) / WG;
   {
     LaunchTimer tm(c, GPX_TIMER_TRMM);
-    prune_init_kernel<<<1, 64, 0, c->stream>>>(ps.desc, ps.count, ps.tau, ps.stats, col0, ncols, R[1], 0, first);
+    prune_init_kernel<<<1, 64, 0, c->stream>>>(ps.desc, ps.count, ps.tau, ps.stats, col0, ncols, R[1], 0, first,
+                                               tk ? tk->head : nullptr);
   }
   if (seed) {
     launch_kstar(c, p, n, npad, X, ldx, alpha, 1, Xs, ldxs, seed, b);
@@ -1989,11 +2206,11 @@ hipError_t launch_sweep_super_pruned(Context* c, const gpx_kernel_params& p, int
       host_stats[2] += (int64_t)ncbt * nI;
     }
     LaunchTimer tm(c, GPX_TIMER_ACQ);
-    PruneSel sel{};
-    sel.tau = ps.tau;
     finalize_kernel<<<seed_blocks, WG, 0, c->stream>>>(fa, 1, Xs, ldxs, seed, C, 1, nJB, nI, b.mu_part, b.ss_part,
                                                        nullptr, 0, nullptr, nullptr, ph.rec_val + *recs,
-                                                       ph.rec_idx + *recs, index_offset, sel);
+                                                       ph.rec_idx + *recs, index_offset,
+                                                       score_sel(PruneSel{}, ps, tk));
+    launch_topk_pool(c, ps, tk, C);
     *recs += seed_blocks;
   }
   if (ncols == 0) return hipGetLastError();
@@ -2096,10 +2313,10 @@ hipError_t launch_sweep_super_pruned(Context* c, const gpx_kernel_params& p, int
     }
     LaunchTimer tm(c, GPX_TIMER_ACQ);
     sel.desc = ps.desc + ns;
-    sel.count = nullptr;
     finalize_kernel<<<rblocks, WG, 0, c->stream>>>(fa, 1, Xs, ldxs, m_super, MA, 1, nJB, nI, ph.mu_part, ph.ss_part,
                                                    nullptr, 0, nullptr, nullptr, ph.rec_val + *recs,
-                                                   ph.rec_idx + *recs, index_offset, sel);
+                                                   ph.rec_idx + *recs, index_offset, score_sel(sel, ps, tk));
+    launch_topk_pool(c, ps, tk, C);
     *recs += rblocks;
   }
   return hipGetLastError();

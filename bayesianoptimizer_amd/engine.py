@@ -578,9 +578,46 @@ class GPEngine:
             return best_val, best_idx, scores
         return best_val, best_idx
 
+    def acquire_topk(self, state: GPState, Xs, k: int, kind: Union[str, int] = "logei", best_f: float = 0.0,
+                     beta: float = 4.0, y_mean: float = 0.0, y_scale: float = 1.0,
+                     alpha: Optional[torch.Tensor] = None, index_offset: int = 0):
+        """The k best candidates as device tensors (values[k], indices[k]): what ``acquire(return_scores=True)``
+        followed by ``topk(scores, k)`` gives (descending, ties -> lower index first), through the pruned sweep where
+        it applies (gpx_acquire_topk_f64; 1 <= k <= min(m, GPX_TOPK_SWEEP_MAX))."""
+        Xs = self._as_f64(Xs, "Xs")
+        if Xs.shape[1] != state.d:
+            raise ValueError(f"Xs has {Xs.shape[1]} columns, model has d={state.d}")
+        m = Xs.shape[0]
+        if m == 0:
+            raise ValueError("empty candidate set")
+        k = int(k)
+        self.inverse(state)
+        kid = ACQ_KINDS[kind.lower()] if isinstance(kind, str) else int(kind)
+        if alpha is None:
+            alpha = state.alpha[:, 0]
+        alpha = alpha.to(device=self.device, dtype=torch.float64).contiguous()
+        if alpha.numel() != state.npad:
+            raise ValueError("alpha must have padded_n entries")
+        ap = AcqParamsC()
+        ap.kind, ap.best_f, ap.beta, ap.y_mean, ap.y_scale = kid, float(best_f), float(beta), float(y_mean), \
+            float(y_scale)
+        nbytes = ctypes.c_size_t()
+        self._check(self.lib.gpx_acquire_topk_workspace_size(state.n, m, k, ctypes.byref(nbytes)))
+        val = torch.empty((k,), dtype=torch.float64, device=self.device)
+        idx = torch.empty((k,), dtype=torch.int64, device=self.device)
+        ws = self.workspace("sweep", nbytes.value)
+        pc = state.params.to_c(state.d)
+        self._bind_stream()
+        self._check(self.lib.gpx_acquire_topk_f64(
+            self.handle, ctypes.byref(pc), state.n, _ptr(state.X), state.X.stride(0), _ptr(state.W), state.W.stride(0),
+            _ptr(alpha), _ptr(Xs), m, Xs.stride(0), ctypes.byref(ap), int(index_offset), k, _ptr(val), _ptr(idx),
+            _ptr(ws), ws.numel()))
+        return val, idx
+
     def sweep_stats(self):
-        """Work counters of the last `acquire` call (synchronises the stream): (candidates seen, candidates whose
-        variance product was computed to its last row tile, 128x128 product tiles executed, tiles of the full sweep)."""
+        """Work counters of the last `acquire` / `acquire_topk` call (synchronises the stream): (candidates seen,
+        candidates whose variance product was computed to its last row tile, 128x128 product tiles executed, tiles of
+        the full sweep)."""
         out = (ctypes.c_int64 * 4)()
         self._check(self.lib.gpx_sweep_stats(self.handle, out))
         return tuple(int(v) for v in out)

@@ -276,6 +276,13 @@ class ExactGP:
         if self.independent:
             return self.engine.acquire_multi(self.states, X, kind, best_f=best_f, beta=beta, weights=w, y_mean=ym,
                                              y_scale=ys, index_offset=index_offset, return_scores=return_scores)
+        st, alpha, y_mean, s = self._shared_objective(w, ym, ys)
+        return self.engine.acquire(st, X, kind, best_f=best_f, beta=beta, y_mean=y_mean, y_scale=s,
+                                   alpha=alpha, index_offset=index_offset, return_scores=return_scores)
+
+    def _shared_objective(self, w, ym, ys):
+        """(state, combined alpha, y_mean, y_scale) of the linear objective over outputs that share the factor."""
+        T = self.num_outputs
         st = self.state
         ymv = torch.zeros(T, dtype=torch.float64) if ym is None else torch.tensor(ym, dtype=torch.float64)
         ysv = torch.ones(T, dtype=torch.float64) if ys is None else torch.tensor(ys, dtype=torch.float64)
@@ -288,8 +295,31 @@ class ExactGP:
         c = float(st.params.const_mean)
         alpha = (st.alpha[:, :T] @ ws.to(st.alpha.device)) / s
         y_mean = float((wt * ymv).sum()) + c * (float(ws.sum()) - s)
-        return self.engine.acquire(st, X, kind, best_f=best_f, beta=beta, y_mean=y_mean, y_scale=s,
-                                   alpha=alpha.contiguous(), index_offset=index_offset, return_scores=return_scores)
+        return st, alpha.contiguous(), y_mean, s
+
+    def sweep_objective_topk(self, X, kind: str, weights: Sequence[float], k: int, best_f: float = 0.0,
+                             beta: float = 4.0, index_offset: int = 0):
+        """The k best candidates of ``sweep_objective`` as (values[k], indices[k]), descending, ties -> lower index
+        first; indices are index_offset + the row of X.  Outputs that share the factor take one
+        ``GPEngine.acquire_topk`` with the combined alpha (the pruned sweep with the k-th best exact score as its
+        incumbent) when the engine has it and k <= GPX_TOPK_SWEEP_MAX; everything else composes the full sweep with
+        scores and ``topk``."""
+        from ._capi import GPX_TOPK_SWEEP_MAX
+
+        if not self.fitted:
+            self.fit()
+        k = int(k)
+        if not self.independent and hasattr(self.engine, "acquire_topk") and 1 <= k <= GPX_TOPK_SWEEP_MAX:
+            ym, ys = self._untransform()
+            w = [float(v) for v in weights]
+            if len(w) != self.num_outputs:
+                raise ValueError(f"expected {self.num_outputs} objective weights, got {len(w)}")
+            st, alpha, y_mean, s = self._shared_objective(w, ym, ys)
+            return self.engine.acquire_topk(st, X, k, kind, best_f=best_f, beta=beta, y_mean=y_mean, y_scale=s,
+                                            alpha=alpha, index_offset=index_offset)
+        _, _, score = self.sweep_objective(X, kind, weights, best_f=best_f, beta=beta, return_scores=True)
+        val, idx = self.engine.topk(score, k)
+        return val, (idx + int(index_offset) if index_offset else idx)
 
 
 class _Analytic:

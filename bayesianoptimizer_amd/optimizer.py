@@ -484,13 +484,13 @@ class BayesianOptimizer:
     def _analytic_sweep(self, k: int) -> torch.Tensor:
         """Sobol grid scored on the objective sum_t w_t f_t of the modelled outputs (ExactGP.sweep_objective: the
         combined alpha of one shared factorisation, or the multi-output sweep over independent outputs), best k by
+        ExactGP.sweep_objective_topk: the pruned top-k sweep for a shared factorisation, else the full sweep and
         gpx_topk_f64."""
         gp = self.gp_model
         grid = self._tensor(self._sobol_grid(self.config.raw_samples))
         w = self._acq_weights()
-        _, _, score = gp.sweep_objective(self.x_tf(grid), self.acquisition, w.tolist(), best_f=self._incumbent(w),
-                                         beta=self.config.beta, return_scores=True)
-        _, order = self.engine.topk(score, min(k, grid.shape[0]))
+        _, order = gp.sweep_objective_topk(self.x_tf(grid), self.acquisition, w.tolist(), min(k, grid.shape[0]),
+                                           best_f=self._incumbent(w), beta=self.config.beta)
         return grid[order.to(grid.device)]
 
     def _acquire_qlogei(self, k: int) -> torch.Tensor:

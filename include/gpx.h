@@ -152,7 +152,7 @@ size_t gpx_acq_params_size(void);
  *                          down to the launch after a flush)
  *  GPX_OPT_POTRF_SPLIT     panel row blocks per workgroup: -1 (default) split in 2 where the launch still fits the
  *                          co-resident slots, 1 never split, 3 split only where the split launch fits one workgroup per CU
- *  GPX_OPT_SWEEP_PRUNE     gpx_acquire_argmax_f64 without scores_out on the K* + trmm path: 1 (default) the pruned sweep
+ *  GPX_OPT_SWEEP_PRUNE     gpx_acquire_argmax_f64 without scores_out, and gpx_acquire_topk_f64, on the K* + trmm path: 1 (default) the pruned sweep
  *                          from padded n 384 on, 0 the full sweep, 2 the pruned sweep at every padded n >= 384 (tests),
  *                          -2 as 2 but the lazy form's head phase computes every candidate's exact mean instead of the
  *                          bound of it that 1 and 2 take for the RBF kernel (A/B measurements, tests; 3 is not a value).
@@ -322,11 +322,33 @@ gpx_status gpx_acquire_argmax_f64(gpx_handle h, const gpx_kernel_params* p, int6
                                   const double* Xs, int64_t m, int64_t ldxs, const gpx_acq_params* a,
                                   int64_t index_offset, double* best_val, int64_t* best_idx,
                                   double* scores_out, void* ws, size_t ws_bytes);
-/* Work counters of the handle's last gpx_acquire_argmax_f64 call (synchronises the handle's stream; the workspace of
- * that call must still be allocated): out_host[0] candidates seen, [1] candidates whose last 128-row tile of the
- * variance product was computed, [2] 128 x 128 product tiles executed, [3] the tiles the full sweep executes (0 / 0 on
- * the fused small-n path, which has no tiles). */
+/* Work counters of the handle's last sweep, a gpx_acquire_argmax_f64 or gpx_acquire_topk_f64 call (synchronises the
+ * handle's stream; the workspace of that call must still be allocated): out_host[0] candidates seen, [1] candidates
+ * whose last 128-row tile of the variance product was computed, [2] 128 x 128 product tiles executed, [3] the tiles the
+ * full sweep executes (0 / 0 on the fused small-n path, which has no tiles). */
 gpx_status gpx_sweep_stats(gpx_handle h, int64_t* out_host);
+
+/* The k best candidates of the sweep above without the full sweep: val_out / idx_out (device, k each) hold exactly what
+ * gpx_acquire_argmax_f64 with scores_out = S followed by gpx_topk_f64(S, m, k) gives: the k largest scores in
+ * descending order, equal scores with the lower index first, a NaN score ranked (and returned) as -inf, -0 as +0;
+ * the values have the bits of the full sweep's scores and the indices are index_offset + local index.
+ * Where the pruned sweep applies (GPX_OPT_SWEEP_PRUNE, the K* + trmm path) the incumbent of its bound test is the k-th
+ * best score computed in full so far: a dropped candidate lies strictly below k exactly scored ones, so it can neither
+ * be among the k best nor tie with the k-th.  Elsewhere (GPX_OPT_SWEEP_PRUNE = 0, the fused small-n sweep, padded
+ * n < 384) the call runs the full sweep into a score array of its own workspace and gpx_topk_f64's sort.
+ * Arguments and validation as gpx_acquire_argmax_f64, plus 1 <= k <= min(m, GPX_TOPK_SWEEP_MAX): the pruned sweep
+ * scores its leading GPX_TOPK_SWEEP_MAX candidates in full before its first bound pass, which fills the pool of the k
+ * best for every legal k.  Asynchronous on the handle's stream, no allocation, no host synchronisation, the same bits
+ * on every call.  gpx_acquire_topk_workspace_size: gpx_sweep_workspace_size(n, 1, m) plus the top-k part (a 256-byte
+ * header, the pool of k 16-byte pairs, one 16-byte scored-list entry per candidate of a sweep chunk, the composed
+ * path's m scores and gpx_topk_workspace_size(m), each rounded up to 256 bytes). */
+enum { GPX_TOPK_SWEEP_MAX = 1024 };
+gpx_status gpx_acquire_topk_workspace_size(int64_t n, int64_t m, int64_t k, size_t* bytes);
+gpx_status gpx_acquire_topk_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X, int64_t ldx,
+                                const double* W, int64_t ldw, const double* alpha, const double* Xs, int64_t m,
+                                int64_t ldxs, const gpx_acq_params* a, int64_t index_offset, int64_t k,
+                                double* val_out /* k, device */, int64_t* idx_out /* k, device */,
+                                void* ws, size_t ws_bytes);
 
 /* Candidate sweep of a LINEAR OBJECTIVE over T independent GPs on the same training inputs X (the outputs of the batched
  * fits above, or of separate fits / appends of the same n): f = sum_t w_t (y_mean[t] + y_scale[t] g_t) with g_t the
