@@ -22,6 +22,8 @@ GPX_MAX_RHS = 8
 GPX_TILE = 128
 GPX_MAX_Q = 32
 GPX_MAX_GRAD_CANDIDATES = 16384
+GPX_MAX_JOINT = 8192  # points per gpx_joint_moments_f64 call
+GPX_MAX_BASELINE = 64  # baseline points of gpx_cross_cov_grad_f64 / gpx_mc_nei_f64
 GPX_COMM_ID_BYTES = 128
 GPX_TOPK_SWEEP_MAX = 1024  # largest k of gpx_acquire_topk_f64
 
@@ -123,6 +125,17 @@ class McAcqParamsC(ctypes.Structure):
     ]
 
 
+class McNeiParamsC(ctypes.Structure):
+    _fields_ = [
+        ("log", c_int32),
+        ("fat_relu", c_int32),
+        ("fat_max", c_int32),
+        ("reserved", c_int32),
+        ("tau_relu", c_double),
+        ("tau_max", c_double),
+    ]
+
+
 _h = c_void_p
 _p = c_void_p  # device pointers
 _PROTOS = {
@@ -179,6 +192,16 @@ _PROTOS = {
     "gpx_mc_acq_workspace_size": (c_int32, [c_int64, c_int64, c_int64, POINTER(c_size_t)]),
     "gpx_mc_acq_f64": (c_int32, [_h, POINTER(McAcqParamsC), c_int64, c_int64, c_int64, _p, _p, _p, _p, _p, _p, _p, _p,
                                  c_size_t]),
+    "gpx_joint_moments_workspace_size": (c_int32, [c_int64, c_int64, POINTER(c_size_t)]),
+    "gpx_joint_moments_f64": (c_int32, [_h, POINTER(KernelParamsC), c_int64, _p, c_int64, _p, c_int64, _p, _p, c_int64,
+                                        c_int64, _p, _p, _p, c_int64, _p, c_size_t]),
+    "gpx_cross_cov_grad_workspace_size": (c_int32, [c_int64, c_int64, c_int64, POINTER(c_size_t)]),
+    "gpx_cross_cov_grad_f64": (c_int32, [_h, POINTER(KernelParamsC), c_int64, _p, c_int64, _p, c_int64, _p, c_int64,
+                                         c_int64, _p, c_int64, c_int64, _p, _p, _p, c_size_t]),
+    "gpx_mcnei_params_size": (c_size_t, []),
+    "gpx_mc_nei_workspace_size": (c_int32, [c_int64, c_int64, c_int64, c_int64, POINTER(c_size_t)]),
+    "gpx_mc_nei_f64": (c_int32, [_h, POINTER(McNeiParamsC), c_int64, c_int64, c_int64, c_int64, _p, _p, _p, _p, _p, _p,
+                                 _p, _p, _p, _p, _p, _p, _p, c_size_t]),
     "gpx_sweep_workspace_size": (c_int32, [c_int64, c_int64, c_int64, POINTER(c_size_t)]),
     "gpx_posterior_f64": (c_int32, [_h, POINTER(KernelParamsC), c_int64, _p, c_int64, _p, c_int64, _p, c_int64,
                                     _p, c_int64, c_int64, POINTER(c_double), POINTER(c_double), _p, c_int64, _p,
@@ -263,7 +286,7 @@ def load() -> ctypes.CDLL:
     # the struct definitions above must match the ones compiled into the library (a truncated struct would make the
     # library read past the caller's object, include/gpx.h)
     for cls, fn in ((KernelParamsC, lib.gpx_kernel_params_size), (AcqParamsC, lib.gpx_acq_params_size),
-                    (McAcqParamsC, lib.gpx_mcacq_params_size)):
+                    (McAcqParamsC, lib.gpx_mcacq_params_size), (McNeiParamsC, lib.gpx_mcnei_params_size)):
         if ctypes.sizeof(cls) != fn():
             raise GPXLibraryError(f"{cls.__name__} is {ctypes.sizeof(cls)} bytes, libgpx expects {fn()}")
     _lib = lib

@@ -24,6 +24,11 @@ The Monte-Carlo part after the moments runs either in torch (the default qLogEI:
 logsumexp chains, differentiated by autograd) or in one libgpx call, ``gpx_mc_acq_f64`` (``fused=True``, ``fat_max=True``
 and ``qPosteriorStandardDeviation``, the exact-mode acquisition of ``optimization/Bayesian6.py:113-130, 896-919``): value
 and the gradients w.r.t. the moments from one kernel, chained to ``gpx_moments_grad_f64``'s derivatives by ``_Moments``.
+
+``qNoisyExpectedImprovement`` / ``qLogNoisyExpectedImprovement`` (``optimization/Bayesian1.py:118-140``) score the
+improvement over the best of the baseline points WITHIN each MC sample: the baseline's joint posterior once per
+acquisition object (``gpx_joint_moments_f64``), the cross-covariance of the q-batch to it at every evaluation
+(``gpx_cross_cov_grad_f64``, chained by ``_Cross``), and the conditional sampling and reduction in ``gpx_mc_nei_f64``.
 """
 from __future__ import annotations
 
@@ -70,6 +75,24 @@ class _Moments(torch.autograd.Function):
             Gs = G + G.transpose(1, 2)
             gX = gX + torch.einsum("bac,bajc->baj", Gs, dcov.reshape(m // q, q, d, q)).reshape(m, d)
         return gX, None, None, None, None
+
+
+class _Cross(torch.autograd.Function):
+    """cross (m, nb): posterior cross-covariance of the candidates to the fixed baseline points; backward from
+    gpx_cross_cov_grad_f64's derivatives: dL/dx_aj = sum_b gcross[a, b] dcross[a, j, b] (the baseline does not move)."""
+
+    @staticmethod
+    def forward(ctx, Xs, engine, state, Sb, Xb):
+        need_grad = bool(ctx.needs_input_grad[0])
+        cross, dcross = engine.cross_cov_grad(state, Sb, Xb, Xs.detach(), need_grad=need_grad)
+        if need_grad:
+            ctx.save_for_backward(dcross)
+        return cross
+
+    @staticmethod
+    def backward(ctx, gcross):
+        (dcross,) = ctx.saved_tensors
+        return torch.einsum("ab,ajb->aj", gcross, dcross), None, None, None, None
 
 
 class _Objective:
@@ -246,6 +269,31 @@ class _McAcq(torch.autograd.Function):
         return gvalue.unsqueeze(-1) * gmean, gvalue.view(-1, 1, 1) * gcov, None, None, None, None
 
 
+class _McNei(torch.autograd.Function):
+    """value (B) of gpx_mc_nei_f64 from (mean (B, q), cov (B, q, q), cross (B, q, nb)) and the per-q set-up (Linv, zb,
+    best, zq); backward scales the kernel's gmean / gcov / gcross by the incoming gradient.  Without a gradient to give
+    the call is value-only.  Raises LinAlgError when a batch's conditional covariance did not factor after the jitter
+    retries, like _McAcq."""
+
+    @staticmethod
+    def forward(ctx, mean, cov, cross, engine, setup, opts):
+        need_grad = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+        Linv, zb, best, zq = setup
+        value, gmean, gcov, gcross, info = engine.mc_nei(mean.detach(), cov.detach(), cross.detach(), Linv, zb, best, zq,
+                                                         need_grad=need_grad, **opts)
+        if bool((info < 0).any()):
+            raise torch.linalg.LinAlgError("q-batch conditional covariance not positive definite after jitter")
+        if need_grad:
+            ctx.save_for_backward(gmean, gcov, gcross)
+        return value
+
+    @staticmethod
+    def backward(ctx, gvalue):
+        gmean, gcov, gcross = ctx.saved_tensors
+        g = gvalue.view(-1, 1, 1)
+        return gvalue.unsqueeze(-1) * gmean, g * gcov, g * gcross, None, None, None
+
+
 # ---- acquisition functions (differentiable in X of shape B x q x d) -----------------------------------------
 class AnalyticAcquisition:
     """q = 1 analytic scores on the differentiable posterior: EI / LogEI / UCB / posterior variance (the forms of the
@@ -344,6 +392,154 @@ class qPosteriorStandardDeviation:
         mu, cov = posterior_moments(self.model, X, self.objective)
         z = self.sampler.base_samples(X.shape[1], X.device)
         return _McAcq.apply(mu, cov, self.model.engine, z, "qpsd", {})
+
+
+def _as_objective(model, objective, output: int = 0) -> "_Objective":
+    if isinstance(objective, _Objective):
+        return objective
+    return _Objective(model, objective.weights if objective is not None else None, output)
+
+
+def joint_posterior(model, X: torch.Tensor, objective: Optional[_Objective] = None, want_solve: bool = False):
+    """Noise-free joint posterior of the objective at the points X (n x d, model input space): mean (n), covariance
+    (n x n) and, with ``want_solve``, each term's K^{-1} K(X_train, X) for ``_Cross`` (else None)."""
+    obj = objective or _Objective(model)
+    X = X.to(device=model.engine.device, dtype=torch.float64).contiguous()
+    mean_t = torch.full((X.shape[0],), obj.offset, dtype=torch.float64, device=X.device)
+    cov_t = torch.zeros((X.shape[0], X.shape[0]), dtype=torch.float64, device=X.device)
+    solves = []
+    for st, alpha, ms, vs in obj.terms:
+        mean, cov, Sb = model.engine.joint_moments(st, X, alpha, want_solve=want_solve)
+        mean_t = mean_t + ms * mean
+        cov_t = cov_t + vs * cov
+        solves.append(Sb)
+    return mean_t, cov_t, (solves if want_solve else None)
+
+
+def _prune_from_samples(samples: torch.Tensor, max_points: int) -> torch.Tensor:
+    """Indices (ascending) of the points that are the argmax of at least one row of samples (S x n); above
+    ``max_points`` the ones with the highest counts, ties to the lower index."""
+    n = samples.shape[1]
+    counts = torch.bincount(samples.argmax(dim=1), minlength=n).cpu()
+    keep = (counts > 0).nonzero().view(-1)
+    if keep.numel() > max_points:
+        order = sorted(keep.tolist(), key=lambda i: (-int(counts[i]), i))[:max_points]
+        keep = torch.tensor(sorted(order), dtype=torch.int64)
+    return keep
+
+
+def prune_inferior_points(model, X: torch.Tensor, objective=None, num_samples: int = 2048,
+                          max_points: int = _capi.GPX_MAX_BASELINE, seed: int = 0, output: int = 0) -> torch.Tensor:
+    """The rows of X (n x d) that are likely to be the best point under the model's posterior (BoTorch
+    prune_inferior_points [upstream, unverified: restated from the public algorithm]): ``num_samples`` joint samples of
+    the objective at all of X; a point is kept if it is the maximum of at least one sample; if more than ``max_points``
+    survive, those that are the maximum most often (ties to the lower index).  Rows keep their order.  The samples
+    come from the Cholesky factor of the joint covariance with the jitter ladder, or from its eigendecomposition
+    (negative eigenvalues clamped) when it does not factor: the noise-free covariance at many training points is
+    close to singular."""
+    if X.dim() != 2 or X.shape[0] < 1:
+        raise ValueError("X must be n x d with n >= 1")
+    if X.shape[0] > _capi.GPX_MAX_JOINT:
+        raise ValueError(f"at most {_capi.GPX_MAX_JOINT} points can be pruned jointly, got {X.shape[0]}")
+    if max_points < 1:
+        raise ValueError("max_points must be at least 1")
+    obj = _as_objective(model, objective, output)
+    mean, cov, _ = joint_posterior(model, X, obj)
+    cov = 0.5 * (cov + cov.T)
+    try:
+        root = psd_safe_cholesky(cov)
+    except torch.linalg.LinAlgError:
+        evals, evecs = torch.linalg.eigh(cov)
+        root = evecs * evals.clamp_min(0.0).sqrt()
+    g = torch.Generator().manual_seed(int(seed))
+    z = torch.randn(int(num_samples), X.shape[0], dtype=torch.float64, generator=g).to(cov.device)
+    keep = _prune_from_samples(mean + z @ root.T, int(max_points))
+    return X[keep.to(X.device)]
+
+
+class qNoisyExpectedImprovement:
+    """MC q-batch noisy expected improvement (the acquisition of optimization/Bayesian1.py:118-140 [upstream: BoTorch
+    qNoisyExpectedImprovement in its cached-root form, unverified]): joint samples of the objective at the baseline
+    points and the q-batch, improvement of the batch's best over the baseline's best WITHIN each sample, mean over the
+    samples.  The sampler draws S x (nb + q) base samples, the baseline columns first.  ``X_baseline`` (model input
+    space) is pruned to the points that can be the incumbent (``prune_inferior_points``) unless ``prune_baseline`` is
+    off; at most GPX_MAX_BASELINE points remain.  The baseline's moments, factor and per-sample incumbents are formed
+    once per q and cached; every evaluation is gpx_moments_grad_f64 + gpx_cross_cov_grad_f64 per objective term and one
+    gpx_mc_nei_f64."""
+
+    _log = False
+
+    def __init__(self, model, X_baseline: torch.Tensor, sampler: Optional[SobolQMCNormalSampler] = None,
+                 objective=None, prune_baseline: bool = True, output: int = 0, prune_seed: int = 0):
+        self.model = model
+        self.sampler = sampler or SobolQMCNormalSampler(torch.Size([512]))
+        self.objective = _as_objective(model, objective, output)
+        Xb = torch.as_tensor(X_baseline, dtype=torch.float64).to(model.engine.device)
+        if Xb.dim() != 2 or Xb.shape[0] < 1:
+            raise ValueError("X_baseline must be nb x d with nb >= 1")
+        if prune_baseline:
+            Xb = prune_inferior_points(model, Xb, self.objective, seed=prune_seed)
+        if Xb.shape[0] > _capi.GPX_MAX_BASELINE:
+            raise ValueError(f"at most {_capi.GPX_MAX_BASELINE} baseline points, got {Xb.shape[0]} (prune_baseline=True)")
+        self.X_baseline = Xb.contiguous()
+        self._baseline = None
+        self._setups = {}
+
+    def _opts(self) -> dict:
+        return {"log": self._log}
+
+    def _setup(self, q: int):
+        """(Linv, zb, best, zq) for q-batches of size q"""
+        if q not in self._setups:
+            if self._baseline is None:
+                mu_b, cov_bb, solves = joint_posterior(self.model, self.X_baseline, self.objective, want_solve=True)
+                Lb = psd_safe_cholesky(0.5 * (cov_bb + cov_bb.T))
+                eye = torch.eye(Lb.shape[0], dtype=torch.float64, device=Lb.device)
+                Linv = torch.linalg.solve_triangular(Lb, eye, upper=False)
+                self._baseline = (mu_b, Lb, Linv.contiguous(), solves)
+            mu_b, Lb, Linv, _ = self._baseline
+            nb = mu_b.shape[0]
+            z = self.sampler.base_samples(nb + q, mu_b.device)
+            zb, zq = z[:, :nb].contiguous(), z[:, nb:].contiguous()
+            best = (mu_b + zb @ Lb.T).amax(dim=1)
+            self._setups[q] = (Linv, zb, best, zq)
+        return self._setups[q]
+
+    def __call__(self, X: torch.Tensor) -> torch.Tensor:
+        if X.dim() == 2:
+            X = X.unsqueeze(0)
+        B, q, d = X.shape
+        setup = self._setup(q)
+        solves = self._baseline[3]
+        mu, cov = posterior_moments(self.model, X, self.objective)
+        nb = self.X_baseline.shape[0]
+        cross = torch.zeros((B, q, nb), dtype=torch.float64, device=X.device)
+        for (st, _, _, vs), Sb in zip(self.objective.terms, solves):
+            cross = cross + vs * _Cross.apply(X.reshape(B * q, d), self.model.engine, st, Sb,
+                                              self.X_baseline).reshape(B, q, nb)
+        return _McNei.apply(mu, cov, cross, self.model.engine, setup, self._opts())
+
+
+class qLogNoisyExpectedImprovement(qNoisyExpectedImprovement):
+    """qNoisyExpectedImprovement in qLogEI's log-space form [upstream: BoTorch qLogNoisyExpectedImprovement,
+    unverified]: log-improvement log_fatplus(f - best_s, tau_relu) (or log_softplus with fat=False) against the sample's
+    incumbent, q-reduction by fatmax (``fat_max=True``, BoTorch's default) or tau_max * logsumexp, logmeanexp over the
+    samples."""
+
+    _log = True
+
+    def __init__(self, model, X_baseline: torch.Tensor, sampler: Optional[SobolQMCNormalSampler] = None,
+                 objective=None, prune_baseline: bool = True, output: int = 0, fat: bool = True, fat_max: bool = True,
+                 tau_max: float = TAU_MAX, tau_relu: float = TAU_RELU, prune_seed: int = 0):
+        super().__init__(model, X_baseline, sampler, objective, prune_baseline, output, prune_seed)
+        self.fat = bool(fat)
+        self.fat_max = bool(fat_max)
+        self.tau_max = float(tau_max)
+        self.tau_relu = float(tau_relu)
+
+    def _opts(self) -> dict:
+        return {"log": True, "fat_relu": self.fat, "fat_max": self.fat_max, "tau_max": self.tau_max,
+                "tau_relu": self.tau_relu}
 
 
 def qlogei_from_moments(mu: torch.Tensor, cov: torch.Tensor, z: torch.Tensor, best_f: float, fat: bool = True,

@@ -912,6 +912,125 @@ gpx_status gpx_mc_acq_f64(gpx_handle h, const gpx_mcacq_params* a, int64_t B, in
                    "mc_acq");
 }
 
+gpx_status gpx_joint_moments_workspace_size(int64_t n, int64_t mb, size_t* bytes) {
+  if (!bytes || n < 1 || mb < 1 || mb > GPX_MAX_JOINT) return GPX_INVALID_ARG;
+  *bytes = gpx::joint_moments_ws_doubles((int)padded(n), (int)mb) * sizeof(double) + 256;
+  return GPX_OK;
+}
+
+gpx_status gpx_joint_moments_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X, int64_t ldx,
+                                 const double* W, int64_t ldw, const double* alpha, const double* Xb, int64_t mb,
+                                 int64_t ldxb, double* mean_b, double* cov_bb, double* Sb, int64_t ldsb, void* ws,
+                                 size_t ws_bytes) {
+  Context* c = reinterpret_cast<Context*>(h);
+  if (!c) return GPX_INVALID_ARG;
+  GPX_TRY(check_params(c, p));
+  GPX_TRY(check_n(c, n));
+  if (mb < 1 || mb > GPX_MAX_JOINT) return fail(c, GPX_INVALID_ARG, "mb must be in [1, GPX_MAX_JOINT]");
+  GPX_NONNULL(c, X);
+  GPX_NONNULL(c, W);
+  GPX_NONNULL(c, alpha);
+  GPX_NONNULL(c, Xb);
+  GPX_NONNULL(c, mean_b);
+  GPX_NONNULL(c, cov_bb);
+  GPX_NONNULL(c, ws);
+  const int64_t npad = padded(n);
+  GPX_TRY(check_ld(c, ldx, p->d, "X", false));
+  GPX_TRY(check_ld(c, ldw, npad, "W", true));
+  GPX_TRY(check_ld(c, ldxb, p->d, "Xb", false));
+  if (Sb) GPX_TRY(check_ld(c, ldsb, (mb + 63) / 64 * 64, "Sb", true));
+  size_t need = 0;
+  GPX_TRY(gpx_joint_moments_workspace_size(n, mb, &need));
+  if (ws_bytes < need) return fail(c, GPX_INVALID_ARG, "joint_moments workspace too small");
+  GPX_USE_DEVICE(c);
+  return hip_check(c, gpx::launch_joint_moments(c, *p, (int)n, (int)npad, X, ldx, W, ldw, alpha, Xb, (int)mb, ldxb,
+                                                mean_b, cov_bb, Sb, ldsb, align256(ws)),
+                   "joint_moments");
+}
+
+gpx_status gpx_cross_cov_grad_workspace_size(int64_t n, int64_t nb, int64_t m, size_t* bytes) {
+  if (!bytes || n < 1 || nb < 1 || nb > GPX_MAX_BASELINE || m < 1 || m > GPX_MAX_GRAD_CANDIDATES)
+    return GPX_INVALID_ARG;
+  *bytes = 0;
+  return GPX_OK;
+}
+
+gpx_status gpx_cross_cov_grad_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X, int64_t ldx,
+                                  const double* Sb, int64_t ldsb, const double* Xb, int64_t nb, int64_t ldxb,
+                                  const double* Xs, int64_t m, int64_t ldxs, double* cross, double* dcross, void* ws,
+                                  size_t ws_bytes) {
+  Context* c = reinterpret_cast<Context*>(h);
+  if (!c) return GPX_INVALID_ARG;
+  (void)ws;
+  (void)ws_bytes;
+  GPX_TRY(check_params(c, p));
+  GPX_TRY(check_n(c, n));
+  if (nb < 1 || nb > GPX_MAX_BASELINE) return fail(c, GPX_INVALID_ARG, "nb must be in [1, GPX_MAX_BASELINE]");
+  if (m < 1 || m > GPX_MAX_GRAD_CANDIDATES) return fail(c, GPX_INVALID_ARG, "m must be in [1, GPX_MAX_GRAD_CANDIDATES]");
+  GPX_NONNULL(c, X);
+  GPX_NONNULL(c, Sb);
+  GPX_NONNULL(c, Xb);
+  GPX_NONNULL(c, Xs);
+  GPX_NONNULL(c, cross);
+  GPX_TRY(check_ld(c, ldx, p->d, "X", false));
+  GPX_TRY(check_ld(c, ldsb, nb, "Sb", false));
+  GPX_TRY(check_ld(c, ldxb, p->d, "Xb", false));
+  GPX_TRY(check_ld(c, ldxs, p->d, "Xs", false));
+  GPX_USE_DEVICE(c);
+  return hip_check(c, gpx::launch_cross_cov_grad(c, *p, (int)n, X, ldx, Sb, ldsb, Xb, (int)nb, ldxb, Xs, (int)m, ldxs,
+                                                 cross, dcross),
+                   "cross_cov_grad");
+}
+
+size_t gpx_mcnei_params_size(void) { return sizeof(gpx_mcnei_params); }
+
+gpx_status gpx_mc_nei_workspace_size(int64_t B, int64_t q, int64_t nb, int64_t S, size_t* bytes) {
+  if (!bytes || q < 1 || q > GPX_MAX_Q || B < 1 || B * q > GPX_MAX_GRAD_CANDIDATES || nb < 1 ||
+      nb > GPX_MAX_BASELINE || S < 1 || S > (int64_t)1 << 20)
+    return GPX_INVALID_ARG;
+  *bytes = gpx::mc_nei_ws_doubles(B, q, nb, S) * sizeof(double) + 256;
+  return GPX_OK;
+}
+
+gpx_status gpx_mc_nei_f64(gpx_handle h, const gpx_mcnei_params* a, int64_t B, int64_t q, int64_t nb, int64_t S,
+                          const double* mean, const double* cov, const double* cross, const double* Linv,
+                          const double* zb, const double* best, const double* zq, double* value, double* gmean,
+                          double* gcov, double* gcross, int32_t* info, void* ws, size_t ws_bytes) {
+  Context* c = reinterpret_cast<Context*>(h);
+  if (!c) return GPX_INVALID_ARG;
+  GPX_NONNULL(c, a);
+  if ((a->log != 0 && a->log != 1) || (a->fat_relu != 0 && a->fat_relu != 1) || (a->fat_max != 0 && a->fat_max != 1))
+    return fail(c, GPX_INVALID_ARG, "gpx_mcnei_params.log / fat_relu / fat_max must be 0 or 1");
+  if (a->reserved != 0) return fail(c, GPX_INVALID_ARG, "gpx_mcnei_params.reserved must be 0");
+  if (!(a->tau_relu > 0.0) || !(a->tau_max > 0.0) || !std::isfinite(a->tau_relu) || !std::isfinite(a->tau_max))
+    return fail(c, GPX_INVALID_ARG, "tau_relu and tau_max must be positive and finite");
+  if (q < 1 || q > GPX_MAX_Q) return fail(c, GPX_INVALID_ARG, "q must be in [1, GPX_MAX_Q]");
+  if (B < 1 || B * q > GPX_MAX_GRAD_CANDIDATES)
+    return fail(c, GPX_INVALID_ARG, "B must be at least 1 and B * q at most GPX_MAX_GRAD_CANDIDATES");
+  if (nb < 1 || nb > GPX_MAX_BASELINE) return fail(c, GPX_INVALID_ARG, "nb must be in [1, GPX_MAX_BASELINE]");
+  if (S < 1 || S > (int64_t)1 << 20) return fail(c, GPX_INVALID_ARG, "S must be in [1, 2^20]");
+  const int ngrad = (gmean != nullptr) + (gcov != nullptr) + (gcross != nullptr);
+  if (ngrad != 0 && ngrad != 3)
+    return fail(c, GPX_INVALID_ARG, "gmean, gcov and gcross must be all NULL or all set");
+  GPX_NONNULL(c, mean);
+  GPX_NONNULL(c, cov);
+  GPX_NONNULL(c, cross);
+  GPX_NONNULL(c, Linv);
+  GPX_NONNULL(c, zb);
+  GPX_NONNULL(c, best);
+  GPX_NONNULL(c, zq);
+  GPX_NONNULL(c, value);
+  GPX_NONNULL(c, info);
+  GPX_NONNULL(c, ws);
+  size_t need = 0;
+  GPX_TRY(gpx_mc_nei_workspace_size(B, q, nb, S, &need));
+  if (ws_bytes < need) return fail(c, GPX_INVALID_ARG, "mc_nei workspace too small");
+  GPX_USE_DEVICE(c);
+  return hip_check(c, gpx::launch_mc_nei(c, *a, (int)B, (int)q, (int)nb, (int)S, mean, cov, cross, Linv, zb, best, zq,
+                                         value, gmean, gcov, gcross, info, align256(ws)),
+                   "mc_nei");
+}
+
 gpx_status gpx_sweep_workspace_size(int64_t n, int64_t nrhs, int64_t m, size_t* bytes) {
   if (!bytes || n < 1 || m < 1 || nrhs < 1 || nrhs > GPX_MAX_RHS) return GPX_INVALID_ARG;
   *bytes = gpx::sweep_workspace_bytes(padded(n), nrhs, m);

@@ -310,6 +310,23 @@ hipError_t launch_mc_acq(Context* c, const gpx_mcacq_params& a, int B, int q, in
                          const double* cov, const double* z, double* value, double* gmean, double* gcov, int32_t* info,
                          double* ws);
 
+// MC noisy expected improvement from the moments and the cross-covariance to the baseline (gpx_mcacq.hip); gmean /
+// gcov / gcross all null: value only
+size_t mc_nei_ws_doubles(int64_t B, int64_t q, int64_t nb, int64_t S);
+hipError_t launch_mc_nei(Context* c, const gpx_mcnei_params& a, int B, int q, int nb, int S, const double* mean,
+                         const double* cov, const double* cross, const double* Linv, const double* zb,
+                         const double* best, const double* zq, double* value, double* gmean, double* gcov,
+                         double* gcross, int32_t* info, double* ws);
+
+// joint posterior at the baseline points and the cross-covariance of candidates to them (gpx_grad.hip)
+size_t joint_moments_ws_doubles(int npad, int mb);
+hipError_t launch_joint_moments(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X, int64_t ldx,
+                                const double* W, int64_t ldw, const double* alpha, const double* Xb, int mb,
+                                int64_t ldxb, double* mean_b, double* cov_bb, double* Sb, int64_t ldsb, double* ws);
+hipError_t launch_cross_cov_grad(Context* c, const gpx_kernel_params& p, int n, const double* X, int64_t ldx,
+                                 const double* Sb, int64_t ldsb, const double* Xb, int nb, int64_t ldxb,
+                                 const double* Xs, int m, int64_t ldxs, double* cross, double* dcross);
+
 size_t mll_workspace_bytes(int64_t npad);
 hipError_t launch_mll(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X, int64_t ldx,
                       const double* Y, int64_t ldy, int nrhs, const double* L, int64_t ldl, const double* W,

@@ -740,6 +740,93 @@ class GPEngine:
                                             _ptr(value), _ptr(gmean), _ptr(gcov), _ptr(info), _ptr(ws), ws.numel()))
         return value, gmean, gcov, info
 
+    def joint_moments(self, state: GPState, Xb, alpha: Optional[torch.Tensor] = None, want_solve: bool = True):
+        """Joint noise-free posterior at the points Xb (mb x d) in the engine's standardised units
+        (gpx_joint_moments_f64): mean_b (mb), cov_bb (mb x mb) and, with ``want_solve``, Sb = K^{-1} K(X, Xb)
+        (padded_n x mb rounded up to 64), the operand of ``cross_cov_grad`` (None otherwise)."""
+        Xb = self._as_f64(Xb, "Xb")
+        mb, d = Xb.shape
+        if d != state.d:
+            raise ValueError(f"Xb has {d} columns, model has d={state.d}")
+        self.inverse(state)
+        if alpha is None:
+            alpha = state.alpha[:, 0]
+        alpha = alpha.to(device=self.device, dtype=torch.float64).contiguous()
+        if alpha.numel() != state.npad:
+            raise ValueError("alpha must have padded_n entries")
+        dev = self.device
+        mean_b = torch.empty((mb,), dtype=torch.float64, device=dev)
+        cov_bb = torch.empty((mb, mb), dtype=torch.float64, device=dev)
+        Sb = torch.empty((state.npad, (mb + 63) // 64 * 64), dtype=torch.float64, device=dev) if want_solve else None
+        nbytes = ctypes.c_size_t()
+        self._check(self.lib.gpx_joint_moments_workspace_size(state.n, mb, ctypes.byref(nbytes)))
+        ws = self.workspace("joint_moments", nbytes.value)
+        pc = state.params.to_c(d)
+        self._bind_stream()
+        self._check(self.lib.gpx_joint_moments_f64(
+            self.handle, ctypes.byref(pc), state.n, _ptr(state.X), state.X.stride(0), _ptr(state.W), state.W.stride(0),
+            _ptr(alpha), _ptr(Xb), mb, Xb.stride(0), _ptr(mean_b), _ptr(cov_bb), _ptr(Sb),
+            Sb.stride(0) if Sb is not None else 0, _ptr(ws), ws.numel()))
+        return mean_b, cov_bb, Sb
+
+    def cross_cov_grad(self, state: GPState, Sb, Xb, Xs, need_grad: bool = True):
+        """Posterior cross-covariance of the candidates Xs (m x d) to the baseline points Xb (nb x d) and its
+        derivative w.r.t. the candidates (gpx_cross_cov_grad_f64), with Sb from ``joint_moments`` on the same Xb:
+        cross (m x nb), dcross (m x d x nb; None with ``need_grad=False``)."""
+        Xs = self._as_f64(Xs, "Xs")
+        Xb = self._as_f64(Xb, "Xb")
+        m, d = Xs.shape
+        nb = Xb.shape[0]
+        if d != state.d or Xb.shape[1] != state.d:
+            raise ValueError(f"Xs / Xb must have d={state.d} columns")
+        if Sb.dim() != 2 or Sb.shape[0] != state.npad or Sb.shape[1] < nb or Sb.stride(1) != 1:
+            raise ValueError("Sb must be the padded_n-row solve that joint_moments returned for Xb")
+        dev = self.device
+        cross = torch.empty((m, nb), dtype=torch.float64, device=dev)
+        dcross = torch.empty((m, d, nb), dtype=torch.float64, device=dev) if need_grad else None
+        nbytes = ctypes.c_size_t()
+        self._check(self.lib.gpx_cross_cov_grad_workspace_size(state.n, nb, m, ctypes.byref(nbytes)))
+        pc = state.params.to_c(d)
+        self._bind_stream()
+        self._check(self.lib.gpx_cross_cov_grad_f64(
+            self.handle, ctypes.byref(pc), state.n, _ptr(state.X), state.X.stride(0), _ptr(Sb), Sb.stride(0), _ptr(Xb),
+            nb, Xb.stride(0), _ptr(Xs), m, Xs.stride(0), _ptr(cross), _ptr(dcross), None, 0))
+        return cross, dcross
+
+    def mc_nei(self, mean, cov, cross, Linv, zb, best, zq, log: bool = False, fat_relu: bool = True,
+               fat_max: bool = True, tau_max: float = 1e-2, tau_relu: float = 1e-6, need_grad: bool = True):
+        """Monte-Carlo noisy expected improvement of B q-batches (gpx_mc_nei_f64): mean (B x q), cov (B x q x q),
+        cross (B x q x nb) to the baseline, Linv (nb x nb) the inverse of the baseline's factor, base samples zb
+        (S x nb) and zq (S x q), per-sample incumbent best (S).  Returns device tensors (value (B), gmean, gcov, gcross,
+        info (B)); the gradients are None with ``need_grad=False``.  info as in ``mc_acq``."""
+        dev = self.device
+        f64 = lambda t: t.to(device=dev, dtype=torch.float64).contiguous()  # noqa: E731
+        mean, cov, cross, Linv, zb, best, zq = (f64(t) for t in (mean, cov, cross, Linv, zb, best, zq))
+        if mean.dim() != 2 or cov.shape != (mean.shape[0], mean.shape[1], mean.shape[1]):
+            raise ValueError(f"mean must be B x q and cov B x q x q, got {tuple(mean.shape)} and {tuple(cov.shape)}")
+        B, q = mean.shape
+        if cross.dim() != 3 or cross.shape[:2] != (B, q):
+            raise ValueError(f"cross must be {B} x {q} x nb, got {tuple(cross.shape)}")
+        nb = cross.shape[2]
+        S = zq.shape[0]
+        if Linv.shape != (nb, nb) or zb.shape != (S, nb) or zq.shape != (S, q) or best.shape != (S,):
+            raise ValueError("Linv must be nb x nb, zb S x nb, zq S x q and best S")
+        value = torch.empty((B,), dtype=torch.float64, device=dev)
+        gmean = torch.empty((B, q), dtype=torch.float64, device=dev) if need_grad else None
+        gcov = torch.empty((B, q, q), dtype=torch.float64, device=dev) if need_grad else None
+        gcross = torch.empty((B, q, nb), dtype=torch.float64, device=dev) if need_grad else None
+        info = torch.empty((B,), dtype=torch.int32, device=dev)
+        ap = _capi.McNeiParamsC(int(bool(log)), int(bool(fat_relu)), int(bool(fat_max)), 0, float(tau_relu),
+                                float(tau_max))
+        nbytes = ctypes.c_size_t()
+        self._check(self.lib.gpx_mc_nei_workspace_size(B, q, nb, S, ctypes.byref(nbytes)))
+        ws = self.workspace("mc_nei", nbytes.value)
+        self._bind_stream()
+        self._check(self.lib.gpx_mc_nei_f64(self.handle, ctypes.byref(ap), B, q, nb, S, _ptr(mean), _ptr(cov),
+                                            _ptr(cross), _ptr(Linv), _ptr(zb), _ptr(best), _ptr(zq), _ptr(value),
+                                            _ptr(gmean), _ptr(gcov), _ptr(gcross), _ptr(info), _ptr(ws), ws.numel()))
+        return value, gmean, gcov, gcross, info
+
     def argmax_combine(self, vals: torch.Tensor, idx: torch.Tensor):
         """Deterministic (max value, lowest index) over device records (after the cross-rank gather)."""
         vals = vals.to(device=self.device, dtype=torch.float64).contiguous().reshape(-1)

@@ -25,6 +25,8 @@ hyperparameters are tied), in which case new observations are folded in by the b
   q-batch limit (``GPX_MAX_Q``) are built greedily in chunks, each chunk conditioned on the ones before it with their
   posterior means as fantasy observations (kriging believer); ``GPConfig.qlogei_fat_max`` selects BoTorch's default
   fat-tailed q-reduction;
+* ``"qnei"`` / ``"qlognei"`` (``Bayesian1.py:118-140``): ``optimize_acqf`` on MC qNoisyExpectedImprovement (or its log
+  form) with the training inputs as the pruned baseline, chunked like ``"qlogei"``;
 * ``"qpsd"`` (Bayesian6's exact mode, ``Bayesian6.py:896-919``): per output one ``optimize_acqf`` on the MC posterior
   standard deviation of that output (``acqf.qPosteriorStandardDeviation``), the batch split evenly over the outputs.
 
@@ -100,6 +102,9 @@ class GPConfig:
     maxiter: int = 200
     # acquisition="qlogei": BoTorch's default q-reduction (fatmax) instead of tau_max * logsumexp (acqf.fatmax)
     qlogei_fat_max: bool = False
+    # acquisition="qnei" / "qlognei": with more training points than this, only the ones with the highest posterior-mean
+    # objective enter the pruning of the baseline (the reference prunes all of train_X, Bayesian1.py:118-127)
+    nei_baseline_pool: int = 1024
 
 
 # ---- persistence -----------------------------------------------------------------------------------------------
@@ -205,7 +210,7 @@ class BayesianOptimizer:
         self.objective_index = kwargs.get("objective_index", None)
         self.objective_weights = kwargs.get("objective_weights", None)
         self.acquisition = str(kwargs.get("acquisition", "variance")).lower()
-        if self.acquisition not in ("variance", "logei", "ei", "ucb", "qlogei", "qpsd"):
+        if self.acquisition not in ("variance", "logei", "ei", "ucb", "qlogei", "qpsd", "qnei", "qlognei"):
             raise ValueError(f"unknown acquisition '{self.acquisition}'")
         self.seed = kwargs.get("seed", None)
         self._rng = np.random.default_rng(self.seed)
@@ -460,6 +465,8 @@ class BayesianOptimizer:
             return self._acquire_qlogei(k)
         if self.acquisition == "qpsd":
             return self._acquire_qpsd(k)
+        if self.acquisition in ("qnei", "qlognei"):
+            return self._acquire_qnei(k, log=self.acquisition == "qlognei")
         return self._analytic_sweep(k)
 
     def _pool_scan(self, k: int) -> torch.Tensor:
@@ -514,6 +521,47 @@ class BayesianOptimizer:
             acq = qLogExpectedImprovement(model, best_f=best_f, objective=objective,
                                           sampler=SobolQMCNormalSampler(torch.Size([cfg.mc_samples]), seed),
                                           fat_max=cfg.qlogei_fat_max)
+            cand, _ = optimize_acqf(_UnitCube(acq, model, x_tf), unit_box, q=q, num_restarts=cfg.num_restarts,
+                                    raw_samples=cfg.acqf_raw_samples,
+                                    options={"batch_limit": cfg.batch_limit, "maxiter": cfg.maxiter}, seed=seed)
+            cand = cand.detach().reshape(q, self.dim)
+            picked.append(cand)
+            remaining -= q
+            if remaining > 0:  # condition on the chunk: fantasy observations = current posterior means
+                Xf = x_tf(cand.to(self.gp_device))
+                fantasy = model.posterior(Xf).mean
+                model = ExactGP(torch.cat([model.train_X, Xf]), torch.cat([model.train_Y, fantasy]), model.params,
+                                engine=self.engine, jitter_schedule=model.jitter_schedule).fit()
+        return torch.cat(picked)
+
+    def _acquire_qnei(self, k: int, log: bool) -> torch.Tensor:
+        """optimize_acqf on MC qNoisyExpectedImprovement (Bayesian1.py:118-140: X_baseline = the training inputs,
+        pruned to the points that can be the incumbent; the reference's 12 restarts and 256 raw samples are
+        ``GPConfig`` settings) or its log form, with the optimize_acqf settings and the chunking of
+        ``_acquire_qlogei``: after each chunk of at most GPX_MAX_Q points the model is conditioned on the chunk's
+        posterior means, so the fantasy points join the baseline.  Above ``GPConfig.nei_baseline_pool`` training points
+        only the ones with the highest posterior-mean objective enter the pruning."""
+        from .acqf import (LinearMCObjective, SobolQMCNormalSampler, optimize_acqf, qLogNoisyExpectedImprovement,
+                           qNoisyExpectedImprovement)
+
+        cfg = self.config
+        w = self._acq_weights()
+        objective = LinearMCObjective(w.cpu())
+        unit_box = torch.stack([torch.zeros(self.dim), torch.ones(self.dim)]).to(self.dtype)
+        x_tf = self.x_tf
+        model = self.gp_model
+        cls = qLogNoisyExpectedImprovement if log else qNoisyExpectedImprovement
+        picked: List[torch.Tensor] = []
+        remaining = k
+        while remaining > 0:
+            q = min(remaining, _capi.GPX_MAX_Q)
+            seed = int(self._rng.integers(0, 1 << 30))
+            Xb = model.train_X
+            if Xb.shape[0] > cfg.nei_baseline_pool:
+                score = model.posterior(Xb).mean.to(w.dtype) @ w.to(Xb.device)
+                Xb = Xb[torch.topk(score, cfg.nei_baseline_pool).indices.sort().values]
+            acq = cls(model, Xb, objective=objective, prune_seed=seed,
+                      sampler=SobolQMCNormalSampler(torch.Size([cfg.mc_samples]), seed))
             cand, _ = optimize_acqf(_UnitCube(acq, model, x_tf), unit_box, q=q, num_restarts=cfg.num_restarts,
                                     raw_samples=cfg.acqf_raw_samples,
                                     options={"batch_limit": cfg.batch_limit, "maxiter": cfg.maxiter}, seed=seed)

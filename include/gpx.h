@@ -38,6 +38,8 @@ extern "C" {
 #define GPX_MAX_LD (1 << 20)            /* leading dimension limit of the matrix arguments (K, L, W) */
 #define GPX_MAX_Q 32                    /* q-batch size of gpx_moments_grad_f64 */
 #define GPX_MAX_GRAD_CANDIDATES 16384  /* candidates per gpx_moments_grad_f64 call */
+#define GPX_MAX_JOINT 8192             /* points per gpx_joint_moments_f64 call */
+#define GPX_MAX_BASELINE 64            /* baseline points of gpx_cross_cov_grad_f64 / gpx_mc_nei_f64 */
 
 typedef struct gpx_context* gpx_handle;
 typedef struct gpx_comm_s* gpx_comm;   /* RCCL communicator of the cross-GPU record exchange */
@@ -430,6 +432,63 @@ gpx_status gpx_mc_acq_f64(gpx_handle h, const gpx_mcacq_params* a, int64_t B, in
                           const double* mean /* B x q */, const double* cov /* B x q x q */,
                           const double* z /* S x q base samples */, double* value /* B */,
                           double* gmean /* B x q or NULL */, double* gcov /* B x q x q or NULL */,
+                          int32_t* info /* B */, void* ws, size_t ws_bytes);
+
+/* ---- noisy expected improvement (qNoisyExpectedImprovement, optimization/Bayesian1.py:118-140) -------------------- */
+/* Joint noise-free posterior at mb points Xb (mb x d): mean_b[c] = const_mean + k_c^T alpha and the full covariance
+ * cov_bb[c * mb + e] = k(xb_c, xb_e) - k_c^T K^{-1} k_e (K* on the device, V = W^T K*, K_bb - V^T V on fp64 MFMA).  Sb,
+ * when not NULL, receives K^{-1} K(X, Xb) = W V as padded_n rows of length ldsb >= mb rounded up to 64: the operand of
+ * gpx_cross_cov_grad_f64.  The set-up call of qNEI (once per baseline) and of the pruning of the baseline.
+ * Limits: 1 <= mb <= GPX_MAX_JOINT.  Device arrays; deterministic. */
+gpx_status gpx_joint_moments_workspace_size(int64_t n, int64_t mb, size_t* bytes);
+gpx_status gpx_joint_moments_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X, int64_t ldx,
+                                 const double* W, int64_t ldw, const double* alpha, const double* Xb, int64_t mb,
+                                 int64_t ldxb, double* mean_b /* mb */, double* cov_bb /* mb x mb */,
+                                 double* Sb /* padded_n x ldsb or NULL */, int64_t ldsb, void* ws, size_t ws_bytes);
+
+/* Posterior cross-covariance of m candidates Xs to nb fixed baseline points Xb and its derivative w.r.t. the candidates
+ * (the baseline does not move, so the derivative is complete), with Sb from gpx_joint_moments_f64 on the same Xb:
+ *   cross[a * nb + b]            = k(x_a, xb_b) - sum_i k(x_a, X_i) Sb[i][b]
+ *   dcross[(a * d + j) * nb + b] = d1 k(x_a, xb_b)/dx_aj - sum_i d1 k(x_a, X_i)/dx_aj Sb[i][b]
+ * dcross may be NULL (value-only scoring: another kernel, four candidates per workgroup, so cross then agrees with
+ * the gradient call's to rounding, not to the bit).  Both run on the vector units.
+ * Limits: 1 <= nb <= GPX_MAX_BASELINE, 1 <= m <= GPX_MAX_GRAD_CANDIDATES.  The workspace is unused (0 bytes asked). */
+gpx_status gpx_cross_cov_grad_workspace_size(int64_t n, int64_t nb, int64_t m, size_t* bytes);
+gpx_status gpx_cross_cov_grad_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X, int64_t ldx,
+                                  const double* Sb, int64_t ldsb, const double* Xb, int64_t nb, int64_t ldxb,
+                                  const double* Xs, int64_t m, int64_t ldxs, double* cross /* m x nb */,
+                                  double* dcross /* m x d x nb or NULL */, void* ws, size_t ws_bytes);
+
+/* Monte-Carlo noisy expected improvement of B q-batches, baseline first, then the q-batch (BoTorch's cached-root form
+ * [upstream, unverified]).  The caller forms once per baseline: L_b = chol of the baseline's joint covariance,
+ * Linv = L_b^{-1} (nb x nb, row-major), base samples zb (S x nb) and zq (S x q), and the per-sample incumbent
+ * best[s] = max_j (mu_b + L_b zb_s)_j.  Per q-batch, with mean (q), cov (q x q) and cross (q x nb) of the objective:
+ *   A = cross Linv^T, D = (cov + cov^T) / 2 - A A^T = L L^T with the jitter ladder and info[] of gpx_mc_acq_f64
+ *   f_si = mean_i + sum_j A_ij zb_sj + sum_{j <= i} L_ij zq_sj
+ *   log = 0 (qNEI)     value = (1/S) sum_s max(0, max_i f_si - best_s); the gradient of the max goes to the lowest
+ *                      maximal index; a batch in which no sample improves has value 0 and gradients exactly 0
+ *   log = 1 (qLogNEI)  li_si = log tau_relu + log_improvement((f_si - best_s) / tau_relu), r_s and value as QLOGEI of
+ *                      gpx_mc_acq_f64 (fat_relu, fat_max, tau_relu, tau_max with the same meaning)
+ * gmean = d value / d mean, gcov = d value / d cov (symmetric), gcross = d value / d cross = (Abar - 2 gcov A) Linv with
+ * Abar_ij = sum_s fbar_si zb_sj.  gmean, gcov and gcross are all NULL (value only) or all set; the value has the same
+ * bits either way.  Limits: those of gpx_mc_acq_f64 and 1 <= nb <= GPX_MAX_BASELINE.  Bad arguments are
+ * GPX_INVALID_ARG, and nothing is launched.  Every sum runs in a fixed order: two calls give the same bits. */
+typedef struct {
+  int32_t log;      /* 0 qNEI, 1 qLogNEI */
+  int32_t fat_relu; /* log = 1: 1 log_fatplus, 0 log_softplus */
+  int32_t fat_max;  /* log = 1: 1 fatmax (alpha = 2), 0 tau_max * logsumexp */
+  int32_t reserved; /* must be 0 */
+  double tau_relu, tau_max;
+} gpx_mcnei_params;
+/* sizeof(gpx_mcnei_params) (32) as compiled into the library, for a binding's load-time check */
+size_t gpx_mcnei_params_size(void);
+gpx_status gpx_mc_nei_workspace_size(int64_t B, int64_t q, int64_t nb, int64_t S, size_t* bytes);
+gpx_status gpx_mc_nei_f64(gpx_handle h, const gpx_mcnei_params* a, int64_t B, int64_t q, int64_t nb, int64_t S,
+                          const double* mean /* B x q */, const double* cov /* B x q x q */,
+                          const double* cross /* B x q x nb */, const double* Linv /* nb x nb */,
+                          const double* zb /* S x nb */, const double* best /* S */, const double* zq /* S x q */,
+                          double* value /* B */, double* gmean /* B x q or NULL */,
+                          double* gcov /* B x q x q or NULL */, double* gcross /* B x q x nb or NULL */,
                           int32_t* info /* B */, void* ws, size_t ws_bytes);
 
 /* ---- cross-GPU selection exchange (SURVEY §8b gpx_allreduce_argmax, §8e) ------------------------------------------ */
