@@ -465,9 +465,61 @@ __device__ __forceinline__ double exp_half_neg_fast(double r2) {  // ~ exp(-r2 /
 constexpr double MUF_Y_LIMIT = 16.0, MUF_Q_LIMIT = 65536.0, MUF_EPS2 = 0x1p-80;
 constexpr double MUF_LOG2E = 1.44269504088896340735992468100189;
 
+// The fp32 factorised form (mu_fact32_kernel; 4 < d <= 8, the DMAX = 8 instance).  The same factorisation, but
+// y is never held in fp64: the fragments are A = fl32(fl(log2(e) a_j)) and B = fl32(b), the dot product runs on
+// v_mfma_f32_16x16x4_f32 (KS = DMAX / 4 chained instructions on a zero accumulator) and e = v_exp_f32 of its result;
+// everything behind e (alpha", the fp32 runs, the fp64 sums, G, the scalings) is mu_fact_kernel's, except that a run is
+// MUF32_RUN = 8 rows of a lane, not 16.  Nothing downstream of y saw more than 24 bits of it before either; the price is the dot product's own fp32 rounding, which grows with d and Y_c, so the form is taken by
+// eps1_32(c) itself: a workgroup eligible for a factorised form (Y_c <= MUF_Y_LIMIT, Q_c <= MUF_Q_LIMIT) runs here only
+// if every candidate of it has eps1_32(c) <= MUF32_EPS1_MAX (1 - 2^-12) (written so that NaN fails); otherwise it flags
+// itself (mu_slack = -2) for mu_fact_kernel.  So every candidate on either factorised form has eps1 < 2^-18.
+//
+// Proof of |mu_approx - mu| <= mu_slack here: (e), (f) and (h) stand (the fp64 MFMA's D u Y_c in (f) is no longer spent);
+// (g) is replaced by (g32), with d = p.d the number of coordinates that are not padding.
+//  (g32) fp32 part, relative to |alpha"_j| e_j.
+//      fragments.  A_i = La_i (1 + t1), B_i = b_i (1 + t2), |t| <= v, La_i = fl(log2(e) a_i) (its u is in (f)).
+//      the MFMA.  The arithmetic model assumed: the instruction takes f32 operands and returns an f32 accumulator, and
+//      every product and every addition in it is rounded to nearest at worst once each, in any order (a fused or wider
+//      internal sum only does better); a chain of KS instructions adds KS - 1 roundings inside the same count.  Then
+//          |yhat - sum_i A_i B_i| <= gamma_d sum_i |A_i B_i|,   gamma_d = d v / (1 - d v),
+//      d products and d - 1 additions (the first lands on a zero accumulator, exactly).  Padded coordinates have A_i =
+//      B_i = 0: exact zeros under any model.  The result is the fp32 number v_exp_f32 reads: the old "y -> fp32" term
+//      is part of this one.  tools/probes/mfma_f32_probe.hip measures the model on adversarial inputs (cancelling
+//      pairs, one large and many small terms, magnitudes over 2^40, random signs, denormals): DESIGN §3 quotes the
+//      largest error in units of v sum |A_i B_i|.
+//      Cauchy-Schwarz on the rounded fragments: sum |A_i B_i| <= (1 + v)^2 sum |La_i b_i| <= (1 + v)^2 (1 + u) log2(e)
+//      |a||b| <= Y_c (1 + 2^-22) (Y_c carries 1 + 2^-40 for its own roundings).  Together
+//          |yhat - log2(e) a.b| <= (d + 2) v Y_c (1 + 2^-20)  (+ the fp64 roundings of (f)),
+//      on 2^y relative ln 2 (d + 2) v Y_c (1 + 2^-16) (second order: ln 2 (d + 2) v Y_c <= 2^-17).
+//      as in (g): the instruction 2 v (1 ulp), alpha"'s rounding v, the run of MUF32_RUN = 8 FMAs 8 v (two runs per row
+//      block: npad / 32 + 6 fp64 additions per term instead of npad / 64 + 6, still inside eps64's 2 (n + 64) u with
+//      the exact path's npad / 64 + 18).  With the factor 1 + 2^-8 as in (g):
+//          eps1_32(c) = ((MUF32_RUN + 3 + 0.6932 (d + 2) Y_c) 2^-24 + eps64) (1 + 2^-8);
+//      at d = 8 it is below 2^-18 for Y_c <= 7.6, at d = 5 for Y_c <= 10.8.  (Runs of 16 give 19 in place of 11 and Y_c
+//      <= 6.45 at d = 8, which sends 20 of the bench step's 4096 workgroups to the fp64 form, where they run alone for
+//      0.15 ms; runs of 8 cost 0.02 ms in this kernel: step 7.05 against 7.21 ms, profiles/r13_run_length_ab.jsonl.)
+//      fp32 range.  |La_i| <= log2(e) sqrt(M2) and |b_i| <= |b| are at most 2^8.6 under Q_c <= 2^16, every product and
+//      partial sum at most 2^17.2: no overflow.  A fragment, a product or a partial sum below 2^-126 may be flushed or
+//      rounded as a denormal: an absolute error of at most 2^-126 each, times the other operand (<= 2^9) for a fragment;
+//      over d <= 8 coordinates less than 2^-112 on y, so 2^-112 relative on 2^y: far inside the factor 1 + 2^-8 (which
+//      leaves 11 v 2^-8 > 2^-29 unspent).  |yhat| <= Y_c (1 + (d + 2) v (1 + 2^-20)) < 16.001: v_exp_f32 returns a
+//      normal number (>= 2^-17), no flush, and its 1 ulp holds.
+//  The slack is mu_fact_kernel's expression with eps1_32(c).  MUF32_EPS1_MAX = 2^-18; the 2^-12 of margin in the
+//  eligibility test covers the roundings of eps1_32 itself (a few u), A~ against the true sum |alpha_j| k_j (eps1
+//  relative) and the slack's 1 + 2^-30, so the written slack is below 2^-18 sum |alpha_j| k_j + MUF_EPS2 |outputscale|
+//  |alpha|_1 (1 + 2^-30).  Zero alpha, padded rows, NaN and infinite candidates: as on the fp64 form.
+//  Only DMAX = 8 is built.  At DMAX = 16 the limit admits Y_c < 3.6 only, which unit-cube candidates do not meet; at
+//  DMAX = 4 the form was built and tested (with runs of 16), but its looser bound let three more candidates of 45,000
+//  through the head in a d = 4 call whose sweep_stats tests/test_gpu_sweep_narrow.py pins, so d <= 4 keeps the fp64 form.
+constexpr bool mu_fp32_form(int DMAX) { return DMAX == 8; }
+constexpr double MUF32_EPS1_MAX = 0x1p-18;
+constexpr int MUF32_RUN = 8;  // rows a lane sums in fp32 before the run goes to the fp64 sums (8 or 16; see (g32))
+typedef float f4 __attribute__((ext_vector_type(4)));  // v_mfma_f32_16x16x4_f32's accumulator
+
 // The buffer's head: MUF_HEAD doubles of call-wide values, then the row blocks' records (MuPrep), the factorised form's
 // records (MuFact) and the row blocks' sums and maxima (MuStat).
 constexpr int MUF_FALLBACK = 0;  // int64: workgroups of the last call that took mu_bound_kernel's path
+constexpr int MUF_FP64FORM = 20;  // int64: workgroups of the last call that took mu_fact_kernel (the fp64 factorised form)
 constexpr int MUF_M2 = 1, MUF_SCALE = 2, MUF_L1 = 3, MUF_CEN = 4, MUF_HEAD = 32;
 
 // Per row block of 64 training rows: kstar_mfma_kernel's prologue (scaled rows, centre = mean of the valid rows, centred
@@ -483,6 +535,13 @@ template <int DMAX>
 struct MuFact {
   static constexpr int FRAG = 0, AL = NB * DMAX, STRIDE = AL + NB / 2;
 };
+// The fp32 form's record of a row block (DMAX = 8), after the MuStat records: the fragments fl32(log2(e) a) in the same
+// MFMA order as floats, then alpha" as 64 floats in the order of the f32 accumulator (register r of lane 16 kq + m is row
+// 4 kq + r of the 16 x 16 result, not kq + 4 r): row 16 s + 4 kq + r at float 16 kq + 4 s + r.  Offsets in floats.
+template <int DMAX>
+struct MuFact32 {
+  static constexpr int FRAG = 0, AL = NB * DMAX, STRIDE_D = mu_fp32_form(DMAX) ? (NB * DMAX + NB) / 2 : 0;  // STRIDE_D in doubles
+};
 // A row block's column sums of the scaled rows, then max |a|^2, max |alpha'| and sum |alpha| over its valid rows.
 template <int DMAX>
 struct MuStat {
@@ -490,12 +549,20 @@ struct MuStat {
 };
 size_t mu_prep_doubles(int64_t npad, int d) {
   const int D = d <= 4 ? 4 : d <= 8 ? 8 : 16;
-  return MUF_HEAD + (size_t)(npad / NB) * ((NB * D + 2 * NB + D + 2) + (NB * D + NB / 2) + (D + 4));
+  const int f32 = mu_fp32_form(D) ? (NB * D + NB) / 2 : 0;  // MuFact32
+  return MUF_HEAD + (size_t)(npad / NB) * ((NB * D + 2 * NB + D + 2) + (NB * D + NB / 2) + (D + 4) + f32);
 }
 template <int DMAX>
 __device__ __forceinline__ double* mu_stat(double* prep, int npad, int jb) {
   return prep + MUF_HEAD + (int64_t)(npad / NB) * (MuPrep<DMAX>::STRIDE + MuFact<DMAX>::STRIDE) +
          (int64_t)jb * MuStat<DMAX>::STRIDE;
+}
+template <int DMAX>
+__device__ __forceinline__ const float* mu_fact32_rec(const double* prep, int npad, int jb) {
+  return reinterpret_cast<const float*>(prep + MUF_HEAD +
+                                        (int64_t)(npad / NB) * (MuPrep<DMAX>::STRIDE + MuFact<DMAX>::STRIDE +
+                                                                MuStat<DMAX>::STRIDE) +
+                                        (int64_t)jb * MuFact32<DMAX>::STRIDE_D);
 }
 
 // |a|^2 of row j for the centre cen: the value the row factor, M2 and (through M2) the eligibility test all use.
@@ -601,6 +668,7 @@ __global__ void __launch_bounds__(WG) mu_prep_kernel(gpx_kernel_params p, int n,
       inv_scale = 1.0 / scale;
       if (jb == 0) {
         reinterpret_cast<unsigned long long*>(prep)[MUF_FALLBACK] = 0ull;
+        reinterpret_cast<unsigned long long*>(prep)[MUF_FP64FORM] = 0ull;
         prep[MUF_M2] = m2;
         prep[MUF_SCALE] = scale;
         prep[MUF_L1] = l1;
@@ -622,6 +690,22 @@ __global__ void __launch_bounds__(WG) mu_prep_kernel(gpx_kernel_params p, int n,
       double ap = 0.0;
       if (j < n) ap = alpha[j] * exp(-0.5 * mu_row_norm<DMAX>(p, X, ldx, j, gc)) * inv_scale;
       reinterpret_cast<float*>(fo + F::AL)[t] = (float)ap;
+    }
+    if constexpr (mu_fp32_form(DMAX)) {  // the fp32 form's record: the same values, rounded once more
+      using G = MuFact32<DMAX>;
+      float* go = const_cast<float*>(mu_fact32_rec<DMAX>(prep, npad, jb));
+      for (int e = t; e < NB * DMAX; e += WG) {
+        const int lane = e & 63, k = (e >> 6) % KS, s = (e >> 6) / KS;
+        const int j = j0 + 16 * s + (lane & 15), col = 4 * k + (lane >> 4);
+        const double a = (col < d && j < n) ? X[(int64_t)j * ldx + col] / p.lengthscale[col] - gc[col] : 0.0;
+        go[G::FRAG + e] = (float)(a * MUF_LOG2E);
+      }
+      if (t < NB) {
+        const int kq = t >> 4, s = (t >> 2) & 3, r = t & 3, j = j0 + 16 * s + 4 * kq + r;
+        double ap = 0.0;
+        if (j < n) ap = alpha[j] * exp(-0.5 * mu_row_norm<DMAX>(p, X, ldx, j, gc)) * inv_scale;
+        go[G::AL + t] = (float)ap;
+      }
     }
   }
   double* out = prep + MUF_HEAD + (int64_t)jb * P::STRIDE;
@@ -742,6 +826,180 @@ __global__ void __launch_bounds__(WG) mu_bound_kernel(gpx_kernel_params p, int n
   }
 }
 
+// The classification of a workgroup of 256 candidates, by the first kernel behind mu_prep_kernel (mu_fact32_kernel, or
+// mu_class_kernel where the fp32 form is not built): not eligible for a factorised form -> mu_slack = -1 and the
+// fallback counter (mu_bound_kernel runs it); eligible but not for the fp32 form (FP32 false, or some eps1_32(c) over the
+// limit) -> mu_slack = -2 and the MUF_FP64FORM counter (mu_fact_kernel runs it); else true: the caller computes.
+// nbq = |b|^2 of thread t's candidate; yc, q, eps32 are returned for it.
+template <bool FP32>
+__device__ __forceinline__ bool mu_classify(const gpx_kernel_params& p, int n, double* __restrict__ prep, double nbq,
+                                            int64_t c, int64_t m_chunk, double* __restrict__ mu_slack, double& yc,
+                                            double& q, double& eps32) {
+  const double m2 = prep[MUF_M2];
+  yc = MUF_LOG2E * sqrt(m2 * nbq) * (1.0 + 0x1p-40), q = m2 + nbq;
+  eps32 = (((double)(MUF32_RUN + 3) + (0.6932 * (double)(p.d + 2)) * yc) * 0x1p-24 + (256.0 * q + 512.0 + 2.0 * (double)(n + 64)) * 0x1p-53) *
+          (1.0 + 0x1p-8);
+  const bool ok = c >= m_chunk || (yc <= MUF_Y_LIMIT && q <= MUF_Q_LIMIT);  // (NaN fails)
+  unsigned long long* cnt = reinterpret_cast<unsigned long long*>(prep);
+  if (!__syncthreads_and(ok)) {
+    if (c < m_chunk) mu_slack[c] = -1.0;
+    if (threadIdx.x == 0) atomicAdd(cnt + MUF_FALLBACK, 1ull);
+    return false;
+  }
+  const bool ok32 = FP32 && (c >= m_chunk || eps32 <= MUF32_EPS1_MAX * (1.0 - 0x1p-12));  // (NaN fails)
+  if (!__syncthreads_and(ok32)) {
+    if (c < m_chunk) mu_slack[c] = -2.0;
+    if (threadIdx.x == 0) atomicAdd(cnt + MUF_FP64FORM, 1ull);
+    return false;
+  }
+  return true;
+}
+
+template <int DMAX>
+__device__ __forceinline__ double mu_cand_norm(const gpx_kernel_params& p, const double* __restrict__ prep,
+                                               const double* __restrict__ Xs, int64_t ldxs, int64_t c, int64_t m_chunk) {
+  const double* __restrict__ gc = prep + MUF_CEN;
+  double nbq = 0.0;
+#pragma unroll
+  for (int k = 0; k < DMAX; ++k) {
+    const double v = (k < p.d && c < m_chunk) ? Xs[c * ldxs + k] : 0.0;
+    const double b = k < p.d ? v / p.lengthscale[k] - gc[k] : 0.0;
+    nbq = fma(b, b, nbq);
+  }
+  return nbq;
+}
+
+// d <= 4 and d > 8: the classification alone (every eligible workgroup to mu_fact_kernel).
+template <int DMAX>
+__global__ void __launch_bounds__(WG) mu_class_kernel(gpx_kernel_params p, int n, double* __restrict__ prep,
+                                                      const double* __restrict__ Xs, int64_t ldxs, int64_t m_chunk,
+                                                      double* __restrict__ mu_slack) {
+  const int64_t c = (int64_t)blockIdx.x * WG + threadIdx.x;
+  double yc, q, eps32;
+  (void)mu_classify<false>(p, n, prep, mu_cand_norm<DMAX>(p, prep, Xs, ldxs, c, m_chunk), c, m_chunk, mu_slack, yc, q,
+                           eps32);
+}
+
+// The fp32 factorised form (proof: (g32) above).  mu_fact_kernel's structure with float fragments, four-float
+// accumulators and e = v_exp_f32(acc) directly; the f32 MFMA's accumulator puts row 4 kq + r of a row step in register
+// r, so the lane's four alpha" of step s are rows 16 s + 4 kq + r (MuFact32's order).  It classifies every workgroup
+// first (mu_classify) and computes only those whose candidates all pass the fp32 form's limit.
+template <int DMAX>
+__global__ void __launch_bounds__(WG) mu_fact32_kernel(gpx_kernel_params p, int n, int npad, double* __restrict__ prep,
+                                                       const double* __restrict__ Xs, int64_t ldxs, int64_t m_chunk,
+                                                       double* __restrict__ mu_approx, double* __restrict__ mu_slack) {
+  using F = MuFact32<DMAX>;
+  constexpr int KS = DMAX / 4;
+  const int d = p.d, t = threadIdx.x;
+  const int64_t c0 = (int64_t)blockIdx.x * WG, c = c0 + t;
+  const int nblk = (n + NB - 1) / NB;  // row blocks with a valid row
+  const double* __restrict__ gc = prep + MUF_CEN;
+  const double nbq = mu_cand_norm<DMAX>(p, prep, Xs, ldxs, c, m_chunk);
+  double yc, q, eps1;
+  if (!mu_classify<true>(p, n, prep, nbq, c, m_chunk, mu_slack, yc, q, eps1)) return;
+  const int lane = t & 63, w = t >> 6, m = lane & 15, kq = lane >> 4;
+  float bf[4][KS];
+#pragma unroll
+  for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+    for (int k = 0; k < KS; ++k) {
+      const int64_t cc = c0 + 64 * w + 16 * cb + m;
+      const int col = 4 * k + kq;
+      const double v = (col < d && cc < m_chunk) ? Xs[cc * ldxs + col] : 0.0;
+      bf[cb][k] = col < d ? (float)(v / p.lengthscale[col] - gc[col]) : 0.0f;
+    }
+  float af[4][KS], afn[4][KS];
+  float4 al[4], aln[4];
+  auto load = [&](int jb, float(&a)[4][KS], float4(&l)[4]) {
+    const float* __restrict__ in = mu_fact32_rec<DMAX>(prep, npad, jb);
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int k = 0; k < KS; ++k) a[s][k] = in[F::FRAG + (s * KS + k) * 64 + lane];
+    const float4* __restrict__ ap = reinterpret_cast<const float4*>(in + F::AL) + 4 * kq;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) l[s] = ap[s];
+  };
+  auto mm = [&](const float(&a)[KS], f4(&acc)[4]) {
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) {
+      acc[cb] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+      for (int k = 0; k < KS; ++k) acc[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[k], bf[cb][k], acc[cb], 0, 0, 0);
+    }
+  };
+  float Sf[4], Af[4];
+  auto entries = [&](const f4(&acc)[4], const float4 l) {  // rows 4 kq + r of the step, alpha" in l
+    const float lr[4] = {l.x, l.y, l.z, l.w};
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb) {
+        const float e = __builtin_amdgcn_exp2f(acc[cb][r]);
+        Sf[cb] = fmaf(lr[r], e, Sf[cb]);
+        Af[cb] = fmaf(fabsf(lr[r]), e, Af[cb]);
+      }
+  };
+  double S[4] = {0.0, 0.0, 0.0, 0.0}, A[4] = {0.0, 0.0, 0.0, 0.0};
+  f4 acc0[4], acc1[4];
+  load(0, af, al);
+  mm(af[0], acc0);
+#pragma unroll 1
+  for (int jb = 0; jb < nblk; ++jb) {
+    load(jb + 1 < nblk ? jb + 1 : jb, afn, aln);
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) Sf[cb] = Af[cb] = 0.0f;
+    mm(af[1], acc1);
+    entries(acc0, al[0]);
+    mm(af[2], acc0);
+    entries(acc1, al[1]);
+    if constexpr (MUF32_RUN == 8) {
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb) {
+        S[cb] += (double)Sf[cb];
+        A[cb] += (double)Af[cb];
+        Sf[cb] = Af[cb] = 0.0f;
+      }
+    }
+    mm(af[3], acc1);
+    entries(acc0, al[2]);
+    mm(afn[0], acc0);  // (the last block's again after the last: unused)
+    entries(acc1, al[3]);
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) {
+      S[cb] += (double)Sf[cb];
+      A[cb] += (double)Af[cb];
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      // (an empty asm on each loaded register: without it hipcc moves the loads into the next trip, next to their uses,
+      // and the loop waits for memory eight times per row block)
+      asm volatile("" : "+v"(aln[s].x), "+v"(aln[s].y), "+v"(aln[s].z), "+v"(aln[s].w));
+      al[s] = aln[s];
+#pragma unroll
+      for (int k = 0; k < KS; ++k) {
+        asm volatile("" : "+v"(afn[s][k]));
+        af[s][k] = afn[s][k];
+      }
+    }
+  }
+#pragma unroll
+  for (int cb = 0; cb < 4; ++cb) {
+    S[cb] += __shfl_xor(S[cb], 16);
+    S[cb] += __shfl_xor(S[cb], 32);
+    A[cb] += __shfl_xor(A[cb], 16);
+    A[cb] += __shfl_xor(A[cb], 32);
+  }
+  if (c < m_chunk) {
+    const double s = kq == 0 ? S[0] : kq == 1 ? S[1] : kq == 2 ? S[2] : S[3];
+    const double a = kq == 0 ? A[0] : kq == 1 ? A[1] : kq == 2 ? A[2] : A[3];
+    const double g = exp(-0.5 * nbq), scale = prep[MUF_SCALE], os = fabs(p.outputscale);
+    const double at = (os * (scale * a)) * g;
+    mu_approx[c] = (p.outputscale * (scale * s)) * g;
+    mu_slack[c] = (eps1 * at + MUF_EPS2 * os * prep[MUF_L1]) * (1.0 + 0x1p-30);
+  }
+}
+
 // The factorised form.  Workgroup x: candidates 256 x .. 256 x + 255 against every row block, no LDS: a lane keeps the
 // fragments of its wave's 64 candidates in registers for the whole kernel (the centre is the same for every row block)
 // and reads the row blocks' fragments and alpha" from their records (every wave reads the same lines; the next block's
@@ -751,12 +1009,13 @@ template <int DMAX>
 __global__ void __launch_bounds__(WG) mu_fact_kernel(gpx_kernel_params p, int n, int npad,
                                                      const double* __restrict__ prep, const double* __restrict__ Xs,
                                                      int64_t ldxs, int64_t m_chunk, double* __restrict__ mu_approx,
-                                                     double* __restrict__ mu_slack,
-                                                     unsigned long long* __restrict__ fallback) {
+                                                     double* __restrict__ mu_slack) {
   using F = MuFact<DMAX>;
   constexpr int KS = DMAX / 4;
   const int d = p.d, t = threadIdx.x;
   const int64_t c0 = (int64_t)blockIdx.x * WG, c = c0 + t;
+  // (the barrier: thread 0 writes mu_slack[c0] at the end, after every wave has read the flag)
+  if (!__syncthreads_and(mu_slack[c0] == -2.0)) return;  // only the workgroups mu_classify sent here
   const int nblk = (n + NB - 1) / NB;  // row blocks with a valid row
   const double* __restrict__ gc = prep + MUF_CEN;
   const double m2 = prep[MUF_M2];
@@ -768,12 +1027,6 @@ __global__ void __launch_bounds__(WG) mu_fact_kernel(gpx_kernel_params p, int n,
     nbq = fma(b, b, nbq);
   }
   const double yc = MUF_LOG2E * sqrt(m2 * nbq) * (1.0 + 0x1p-40), q = m2 + nbq;
-  const bool ok = c >= m_chunk || (yc <= MUF_Y_LIMIT && q <= MUF_Q_LIMIT);  // (NaN fails)
-  if (!__syncthreads_and(ok)) {
-    if (c < m_chunk) mu_slack[c] = -1.0;
-    if (t == 0) atomicAdd(fallback, 1ull);
-    return;
-  }
   const int lane = t & 63, w = t >> 6, m = lane & 15, kq = lane >> 4;
   double bf[4][KS];
 #pragma unroll
@@ -1920,8 +2173,9 @@ static void launch_kstar(Context* c, const gpx_kernel_params& p, int n, int npad
 #undef GPX_KSTAR_K
 }
 
-// The head phase's mean bound of m_chunk candidates (mu_colsum_kernel, mu_rowstat_kernel and mu_prep_kernel, then mu_fact_kernel for the
-// eligible workgroups and mu_bound_kernel for the others); prep: mu_prep_doubles(npad, d) doubles of scratch.
+// The head phase's mean bound of m_chunk candidates (mu_colsum_kernel, mu_rowstat_kernel and mu_prep_kernel, then
+// mu_fact32_kernel for the workgroups inside the fp32 form's limit (4 < d <= 8), mu_fact_kernel for the other eligible ones
+// and mu_bound_kernel for the rest); prep: mu_prep_doubles(npad, d) doubles of scratch.
 bool sweep_mu_bound_ok(const gpx_kernel_params& p) { return p.kind == GPX_KERNEL_RBF && !p.cov_fp32 && p.d <= 16; }
 
 hipError_t launch_mu_bound(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X, int64_t ldx,
@@ -1929,19 +2183,23 @@ hipError_t launch_mu_bound(Context* c, const gpx_kernel_params& p, int n, int np
                            double* mu_approx, double* mu_slack) {
   LaunchTimer tm(c, GPX_TIMER_KSTAR);
   const unsigned nwg = (unsigned)((m_chunk + WG - 1) / WG);
-  unsigned long long* fallback = reinterpret_cast<unsigned long long*>(prep) + MUF_FALLBACK;
-#define GPX_MU_BOUND(D)                                                                                            \
-  (mu_colsum_kernel<D><<<npad / NB, WG, 0, c->stream>>>(p, n, npad, X, ldx, prep),                                  \
-   mu_rowstat_kernel<D><<<npad / NB, NB, 0, c->stream>>>(p, n, npad, X, ldx, alpha, prep),                          \
-   mu_prep_kernel<D><<<npad / NB, WG, 0, c->stream>>>(p, n, npad, X, ldx, alpha, prep),                             \
-   mu_fact_kernel<D><<<nwg, WG, 0, c->stream>>>(p, n, npad, prep, Xs, ldxs, m_chunk, mu_approx, mu_slack, fallback), \
+  // FIRST classifies every workgroup and, for 4 < d <= 8, computes those on the fp32 form; the two kernels behind it run the
+  // workgroups it flagged -2 and -1, the others returning at once.
+#define GPX_MU_BOUND(D, FIRST)                                                                            \
+  (mu_colsum_kernel<D><<<npad / NB, WG, 0, c->stream>>>(p, n, npad, X, ldx, prep),                         \
+   mu_rowstat_kernel<D><<<npad / NB, NB, 0, c->stream>>>(p, n, npad, X, ldx, alpha, prep),                 \
+   mu_prep_kernel<D><<<npad / NB, WG, 0, c->stream>>>(p, n, npad, X, ldx, alpha, prep), FIRST,             \
+   mu_fact_kernel<D><<<nwg, WG, 0, c->stream>>>(p, n, npad, prep, Xs, ldxs, m_chunk, mu_approx, mu_slack), \
    mu_bound_kernel<D><<<nwg, WG, 0, c->stream>>>(p, n, prep, Xs, ldxs, m_chunk, mu_approx, mu_slack))
+#define GPX_MU_CLASS(D) mu_class_kernel<D><<<nwg, WG, 0, c->stream>>>(p, n, prep, Xs, ldxs, m_chunk, mu_slack)
   if (p.d <= 4)
-    GPX_MU_BOUND(4);
+    GPX_MU_BOUND(4, GPX_MU_CLASS(4));
   else if (p.d <= 8)
-    GPX_MU_BOUND(8);
+    GPX_MU_BOUND(8, (mu_fact32_kernel<8><<<nwg, WG, 0, c->stream>>>(p, n, npad, prep, Xs, ldxs, m_chunk, mu_approx,
+                                                                     mu_slack)));
   else
-    GPX_MU_BOUND(16);
+    GPX_MU_BOUND(16, GPX_MU_CLASS(16));
+#undef GPX_MU_CLASS
 #undef GPX_MU_BOUND
   return hipGetLastError();
 }
@@ -2227,7 +2485,8 @@ hipError_t launch_sweep_super_pruned(Context* c, const gpx_kernel_params& p, int
       // the mean's bound instead of the mean.  Its two values per candidate go to the mean partials' rows of blocks 2
       // and 3 (the head rows' launch wrote blocks 0 and 1; nothing writes the others before the gather), the row
       // blocks' records to the chunk's K* buffer, idle between the seed block's scoring and the first gather
-      // (mu_prep_doubles <= 38 npad + 32 doubles, the buffer holds npad x C >= 256 npad).
+      // (mu_prep_doubles <= 38 npad + 32 doubles: 35.1 per row at DMAX = 16, 23.4 at DMAX = 8 with the fp32 form's
+      // records; the buffer holds npad x C >= 256 npad).
       static_assert(PRUNE_MIN_NPAD / NB >= 4, "mean partial rows 2 and 3 exist");
       (void)launch_mu_bound(c, p, n, npad, X, ldx, alpha, Xs, ldxs, m_super, b.kstar, ph.mu_part + 2 * MA,
                             ph.mu_part + 3 * MA);  // (the launch error is read at the end)

@@ -600,7 +600,9 @@ gpx_status gpx_debug_kstar_mu_f64(gpx_handle h, const gpx_kernel_params* p, int6
 /* The pruned sweep's bound of the posterior mean, through the production kernel (RBF, fp64 covariance, d <= 16; DESIGN
  * §3): mu_approx[c] - mu_slack[c] <= mu_c <= mu_approx[c] + mu_slack[c] for c < m, mu_c being the mean the full build's
  * partials sum to (without the constant mean).  ws: gpx_debug_mu_bound_workspace_size bytes; on return the int64 at its
- * start (rounded up to 256 bytes) counts the workgroups of 256 candidates that took the unfactorised form of the bound. */
+ * start (rounded up to 256 bytes) counts the workgroups of 256 candidates that took the unfactorised form of the bound,
+ * and the int64 at byte 160 from there those that took the fp64 factorised form (eligible for a factorised form, but d <=
+ * 4, d > 8 or over the fp32 form's error limit); every other workgroup ran the fp32 factorised form. */
 gpx_status gpx_debug_mu_bound_workspace_size(int64_t n, size_t* bytes);
 gpx_status gpx_debug_mu_bound_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X, int64_t ldx,
                                   const double* alpha, const double* Xs, int64_t m, int64_t ldxs, double* mu_approx,
