@@ -5,8 +5,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <string>
+#include <utility>
 #include "gpx_internal.h"
 
 using gpx::Context;
@@ -1031,25 +1033,49 @@ gpx_status gpx_mc_nei_f64(gpx_handle h, const gpx_mcnei_params* a, int64_t B, in
                    "mc_nei");
 }
 
-gpx_status gpx_sweep_workspace_size(int64_t n, int64_t nrhs, int64_t m, size_t* bytes) {
-  if (!bytes || n < 1 || m < 1 || nrhs < 1 || nrhs > GPX_MAX_RHS) return GPX_INVALID_ARG;
-  *bytes = gpx::sweep_workspace_bytes(padded(n), nrhs, m);
+// ---- the sweep entry points' shared checks (the first failing one wins, in the order of the calls below) ----
+// the model and the candidate count; m_max = 0: any m >= 1 (the sweeps chunk it), else the debug calls' cap
+static gpx_status check_sweep_sizes(Context* c, const gpx_kernel_params* p, int64_t n, int64_t m, int64_t m_max = 0) {
+  GPX_TRY(check_params(c, p));
+  GPX_TRY(check_n(c, n));
+  if (m < 1 || (m_max && m > m_max))
+    return fail(c, GPX_INVALID_ARG, m_max ? "m must be in [1, 2^30]" : "m must be >= 1");
   return GPX_OK;
 }
-
-static gpx_status carve_sweep(Context* c, int64_t npad, int64_t nrhs, int64_t m, void* ws, size_t ws_bytes,
-                              gpx::SweepBuffers* b) {
+constexpr int64_t kDebugMaxM = (int64_t)1 << 30;
+// the arrays (every pointer, then the pitches of X, W where the call has one, and Xs)
+using NamedPtr = std::pair<const void*, const char*>;
+static gpx_status check_sweep_arrays(Context* c, std::initializer_list<NamedPtr> ptrs, const gpx_kernel_params* p,
+                                     int64_t ldx, int64_t ldxs, const int64_t* ldw = nullptr, int64_t npad = 0) {
+  for (const NamedPtr& q : ptrs)
+    if (!q.first) return fail(c, GPX_INVALID_ARG, std::string(q.second) + " is NULL");
+  GPX_TRY(check_ld(c, ldx, p->d, "X", false));
+  if (ldw) GPX_TRY(check_ld(c, *ldw, npad, "W", true));
+  return check_ld(c, ldxs, p->d, "Xs", false);
+}
+// the acquisition and the index offset (y_scale: the single-output calls, which untransform by a's own pair)
+static gpx_status check_acq(Context* c, const gpx_acq_params* a, int64_t index_offset, bool y_scale) {
+  if (!a) return fail(c, GPX_INVALID_ARG, "acquisition params pointer is NULL");
+  if (a->kind < GPX_ACQ_EI || a->kind > GPX_ACQ_VARIANCE) return fail(c, GPX_INVALID_ARG, "unknown acquisition kind");
+  if (a->reserved != 0) return fail(c, GPX_INVALID_ARG, "gpx_acq_params.reserved must be 0");
+  if (y_scale && !(a->y_scale > 0.0)) return fail(c, GPX_INVALID_ARG, "y_scale must be positive");
+  if (a->kind == GPX_ACQ_UCB && !(a->beta >= 0.0)) return fail(c, GPX_INVALID_ARG, "UCB beta must be >= 0");
+  if (index_offset < 0) return fail(c, GPX_INVALID_ARG, "index_offset must be >= 0");
+  return GPX_OK;
+}
+// the workspace against the layout's total, then every pointer into it
+static gpx_status carve_sweep(Context* c, const gpx::SweepLayout& L, void* ws, size_t ws_bytes, const char* too_small,
+                              gpx::SweepWorkspace* w, int64_t k = 0) {
+  if (ws && ws_bytes < L.total) return fail(c, GPX_INVALID_ARG, too_small);
   if (!ws) return fail(c, GPX_INVALID_ARG, "sweep workspace is NULL");
-  if (ws_bytes < gpx::sweep_workspace_bytes(npad, nrhs, m)) return fail(c, GPX_INVALID_ARG, "sweep workspace too small");
-  const int64_t C = gpx::sweep_chunk_size(npad, m);
-  double* base = align256(ws);
-  b->chunk = C;
-  b->kstar = base;
-  b->mu_part = b->kstar + (size_t)npad * C;
-  b->ss_part = b->mu_part + (size_t)(npad / gpx::NB) * nrhs * C;
-  b->rec_val = b->ss_part + (size_t)(npad / 128) * C;
-  const int64_t nrec = (m + 255) / 256 + 1;
-  b->rec_idx = reinterpret_cast<int64_t*>(b->rec_val + nrec);
+  *w = gpx::sweep_carve(ws, L, k);
+  return GPX_OK;
+}
+static size_t ws_skew(const void* ws) { return (size_t)(-reinterpret_cast<uintptr_t>(ws) & 255); }
+
+gpx_status gpx_sweep_workspace_size(int64_t n, int64_t nrhs, int64_t m, size_t* bytes) {
+  if (!bytes || n < 1 || m < 1 || nrhs < 1 || nrhs > GPX_MAX_RHS) return GPX_INVALID_ARG;
+  *bytes = gpx::sweep_layout(padded(n), nrhs, m).total;
   return GPX_OK;
 }
 
@@ -1059,31 +1085,20 @@ gpx_status gpx_posterior_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n
                              double* mean_out, int64_t ldmean, double* var_out, void* ws, size_t ws_bytes) {
   Context* c = reinterpret_cast<Context*>(h);
   if (!c) return GPX_INVALID_ARG;
-  GPX_TRY(check_params(c, p));
-  GPX_TRY(check_n(c, n));
+  GPX_TRY(check_sweep_sizes(c, p, n, m));
   if (nrhs < 1 || nrhs > GPX_MAX_RHS) return fail(c, GPX_INVALID_ARG, "nrhs must be in [1, 8]");
-  if (m < 1) return fail(c, GPX_INVALID_ARG, "m must be >= 1");
-  GPX_NONNULL(c, X);
-  GPX_NONNULL(c, W);
-  GPX_NONNULL(c, alpha);
-  GPX_NONNULL(c, Xs);
-  GPX_NONNULL(c, mean_out);
-  GPX_NONNULL(c, var_out);
   const int64_t npad = padded(n);
-  GPX_TRY(check_ld(c, ldx, p->d, "X", false));
-  GPX_TRY(check_ld(c, ldw, npad, "W", true));
-  GPX_TRY(check_ld(c, ldxs, p->d, "Xs", false));
+  GPX_TRY(check_sweep_arrays(c, {{X, "X"}, {W, "W"}, {alpha, "alpha"}, {Xs, "Xs"}, {mean_out, "mean_out"},
+                                 {var_out, "var_out"}}, p, ldx, ldxs, &ldw, npad));
   GPX_TRY(check_ld(c, ldmean, nrhs, "mean", false));
-  gpx::SweepBuffers b;
-  GPX_TRY(carve_sweep(c, npad, nrhs, m, ws, ws_bytes, &b));
+  gpx::SweepWorkspace w;
+  GPX_TRY(carve_sweep(c, gpx::sweep_layout(npad, nrhs, m), ws, ws_bytes, "sweep workspace too small", &w));
   GPX_USE_DEVICE(c);
-  for (int64_t s = 0; s < m; s += b.chunk) {
-    const int64_t mc = (m - s) < b.chunk ? (m - s) : b.chunk;
-    GPX_TRY(hip_check(c,
-                      gpx::launch_sweep_chunk(c, *p, (int)n, (int)npad, X, ldx, W, ldw, alpha, (int)nrhs, Xs + s * ldxs,
-                                              ldxs, mc, b, 0, nullptr, y_mean_host, y_scale_host,
-                                              mean_out + s * ldmean, ldmean, var_out + s, nullptr, 0, 0),
-                      "posterior"));
+  const gpx::SweepModel M{c, *p, (int)n, (int)npad, X, ldx, W, ldw, alpha, (int)nrhs};
+  for (int64_t s = 0; s < m; s += w.b.chunk) {
+    const gpx::SweepCands q{Xs + s * ldxs, ldxs, gpx::sweep_span_size(false, s, m, w.b.chunk, 0), 0};
+    const gpx::SweepOut out{nullptr, y_mean_host, y_scale_host, mean_out + s * ldmean, ldmean, var_out + s};
+    GPX_TRY(hip_check(c, gpx::launch_sweep_chunk(M, q, w.b, 0, nullptr, out), "posterior"));
   }
   return GPX_OK;
 }
@@ -1098,101 +1113,57 @@ static gpx_status acquire_impl(gpx_handle h, const gpx_kernel_params* p, int64_t
   Context* c = reinterpret_cast<Context*>(h);
   if (!c) return GPX_INVALID_ARG;
   const bool topk = val_out || idx_out || k != 0;
-  GPX_TRY(check_params(c, p));
-  GPX_TRY(check_n(c, n));
-  if (m < 1) return fail(c, GPX_INVALID_ARG, "m must be >= 1");
-  if (!a) return fail(c, GPX_INVALID_ARG, "acquisition params pointer is NULL");
-  if (a->kind < GPX_ACQ_EI || a->kind > GPX_ACQ_VARIANCE) return fail(c, GPX_INVALID_ARG, "unknown acquisition kind");
-  if (a->reserved != 0) return fail(c, GPX_INVALID_ARG, "gpx_acq_params.reserved must be 0");
-  if (!(a->y_scale > 0.0)) return fail(c, GPX_INVALID_ARG, "y_scale must be positive");
-  if (a->kind == GPX_ACQ_UCB && !(a->beta >= 0.0)) return fail(c, GPX_INVALID_ARG, "UCB beta must be >= 0");
-  if (index_offset < 0) return fail(c, GPX_INVALID_ARG, "index_offset must be >= 0");
-  GPX_NONNULL(c, X);
-  GPX_NONNULL(c, W);
-  GPX_NONNULL(c, alpha);
-  GPX_NONNULL(c, Xs);
-  if (topk) {
-    if (k < 1 || k > m || k > GPX_TOPK_SWEEP_MAX)
-      return fail(c, GPX_INVALID_ARG, "k must be in [1, min(m, GPX_TOPK_SWEEP_MAX)]");
-    GPX_NONNULL(c, val_out);
-    GPX_NONNULL(c, idx_out);
-  } else {
-    GPX_NONNULL(c, best_val);
-    GPX_NONNULL(c, best_idx);
-  }
+  GPX_TRY(check_sweep_sizes(c, p, n, m));
+  GPX_TRY(check_acq(c, a, index_offset, true));
+  if (topk && (k < 1 || k > m || k > GPX_TOPK_SWEEP_MAX))
+    return fail(c, GPX_INVALID_ARG, "k must be in [1, min(m, GPX_TOPK_SWEEP_MAX)]");
   const int64_t npad = padded(n);
-  GPX_TRY(check_ld(c, ldx, p->d, "X", false));
-  GPX_TRY(check_ld(c, ldw, npad, "W", true));
-  GPX_TRY(check_ld(c, ldxs, p->d, "Xs", false));
-  gpx::SweepBuffers b;
-  gpx::TopkSweep tks;
-  const gpx::TopkSweep* tk = nullptr;
-  if (topk) {
-    const size_t sweep_bytes = gpx::sweep_workspace_bytes(npad, 1, m);
-    if (ws && ws_bytes < sweep_bytes + gpx::topk_sweep_bytes(npad, m, k))
-      return fail(c, GPX_INVALID_ARG, "acquire_topk workspace too small");
-    GPX_TRY(carve_sweep(c, npad, 1, m, ws, ws_bytes, &b));
-    gpx::topk_sweep_carve(reinterpret_cast<char*>(ws) + sweep_bytes, npad, m, k, &tks);
-  } else {
-    GPX_TRY(carve_sweep(c, npad, 1, m, ws, ws_bytes, &b));
-  }
+  GPX_TRY(check_sweep_arrays(c, {{X, "X"}, {W, "W"}, {alpha, "alpha"}, {Xs, "Xs"},
+                                 {topk ? val_out : best_val, topk ? "val_out" : "best_val"},
+                                 {topk ? idx_out : best_idx, topk ? "idx_out" : "best_idx"}}, p, ldx, ldxs, &ldw, npad));
+  gpx::SweepWorkspace w;
+  GPX_TRY(carve_sweep(c, gpx::sweep_layout(npad, 1, m, k, false, topk ? gpx::topk_workspace_bytes(m) : 0, ws_skew(ws)),
+                      ws, ws_bytes, topk ? "acquire_topk workspace too small" : "sweep workspace too small", &w, k));
+  const gpx::SweepBuffers& b = w.b;
   // scores_out wants every score: the full sweep
   const bool prune = !scores_out && gpx::sweep_prune_ok(c, *p, (int)npad);
-  if (topk && prune) tk = &tks;
+  const gpx::TopkSweep* tk = topk && prune ? &w.tk : nullptr;
   // the top-k call where the pruned sweep does not apply: the full sweep into its own score array, then the sort
-  if (topk && !prune) scores_out = tks.scores;
+  if (topk && !prune) scores_out = w.tk.scores;
   // the MFMA K* build's configurations take the lazy form (K* in full height for the first tile's survivors only)
   const bool lazy = prune && gpx::sweep_lazy_ok(*p);
-  gpx::PruneState ps;
-  gpx::PruneHead ph;
-  if (prune) gpx::sweep_prune_carve(b.rec_idx + (m + 255) / 256 + 1, npad, b.chunk, &ps);
-  if (lazy) gpx::sweep_prune_carve_head(ps, npad, b.chunk, gpx::sweep_super_size(npad, m), m, &ph);
   GPX_USE_DEVICE(c);
   const bool fused = gpx::sweep_fused_ok(c, *p, (int)npad, 1);
+  const auto tiles = [&](int64_t mc) { return (mc + 127) / 128 * (npad / 128); };
   c->sweep_stats[0] = m;
   c->sweep_stats[1] = prune ? 0 : m;
-  c->sweep_stats[2] = c->sweep_stats[3] = 0;
-  c->sweep_stats_dev = prune ? ps.stats : nullptr;
+  c->sweep_stats[2] = 0;
+  // [3]: the tiles of the full sweep, with the full path's chunking
+  c->sweep_stats[3] = fused ? 0 : m / b.chunk * tiles(b.chunk) + tiles(m % b.chunk);
+  c->sweep_stats_dev = prune ? w.ps.stats : nullptr;
+  // spans of a chunk, or on the lazy path of a super-chunk (sweep_span_size: the call's first is one chunk long)
+  const gpx::SweepModel M{c, *p, (int)n, (int)npad, X, ldx, W, ldw, alpha, 1};
   int64_t rec = 0;
-  if (lazy) {
-    for (int64_t s = 0; s < m; s += b.chunk)  // [3]: the tiles of the full sweep, with the full path's chunking
-      c->sweep_stats[3] += (((m - s) < b.chunk ? (m - s) : b.chunk) + 127) / 128 * (npad / 128);
-    // the call's first super-chunk is one chunk long: everything after it is bounded against the best of a chunk's
-    // scores instead of the seed block's alone (one super-chunk of 2^20 from the seed on: 23537 product tiles and
-    // 17.6 ms on the bench problem instead of 9121 and 10.2, profiles/r08_variants_probe.jsonl)
-    for (int64_t s = 0, ms = 0; s < m; s += ms) {
-      const int64_t lim = (s == 0 && b.chunk < ph.super) ? b.chunk : ph.super;
-      ms = (m - s) < lim ? (m - s) : lim;
-      GPX_TRY(hip_check(c,
-                        gpx::launch_sweep_super_pruned(c, *p, (int)n, (int)npad, X, ldx, W, ldw, alpha, Xs + s * ldxs,
-                                                       ldxs, ms, b, ps, ph, a, &rec, index_offset + s, s == 0,
-                                                       c->sweep_stats, tk),
-                        "acquire"));
-    }
-    if (tk) return hip_check(c, gpx::launch_topk_result(c, *tk, val_out, idx_out), "topk result");
-    return hip_check(c, gpx::launch_argmax_final(c, ph.rec_val, ph.rec_idx, rec, best_val, best_idx), "argmax");
-  }
-  for (int64_t s = 0; s < m; s += b.chunk) {
-    const int64_t mc = (m - s) < b.chunk ? (m - s) : b.chunk;
-    if (!fused) c->sweep_stats[3] += (mc + 127) / 128 * (npad / 128);
-    GPX_TRY(hip_check(c,
-                      prune ? gpx::launch_sweep_chunk_pruned(c, *p, (int)n, (int)npad, X, ldx, W, ldw, alpha,
-                                                             Xs + s * ldxs, ldxs, mc, b, ps, a, rec, index_offset + s,
-                                                             s == 0, c->sweep_stats, tk)
-                            : gpx::launch_sweep_chunk(c, *p, (int)n, (int)npad, X, ldx, W, ldw, alpha, 1,
-                                                      Xs + s * ldxs, ldxs, mc, b, 1, a, nullptr, nullptr, nullptr, 0,
-                                                      nullptr, scores_out ? scores_out + s : nullptr, rec,
-                                                      index_offset + s),
-                      "acquire"));
-    rec += (mc + 255) / 256;
+  for (int64_t s = 0, ms = 0; s < m; s += ms) {
+    ms = gpx::sweep_span_size(lazy, s, m, b.chunk, w.ph.super);
+    const gpx::SweepCands q{Xs + s * ldxs, ldxs, ms, index_offset + s};
+    const gpx::SweepOut out{scores_out ? scores_out + s : nullptr};
+    const hipError_t e =
+        lazy    ? gpx::launch_sweep_super_pruned(M, q, b, w.ps, w.ph, a, &rec, s == 0, c->sweep_stats, tk)
+        : prune ? gpx::launch_sweep_chunk_pruned(M, q, b, w.ps, a, rec, s == 0, c->sweep_stats, tk)
+                : gpx::launch_sweep_chunk(M, q, b, 1, a, out, rec);
+    GPX_TRY(hip_check(c, e, "acquire"));
+    if (!lazy) rec += (ms + 255) / 256;  // (the lazy path counts its own: the rounds' blocks)
   }
   if (!prune) c->sweep_stats[2] = c->sweep_stats[3];
   if (tk) return hip_check(c, gpx::launch_topk_result(c, *tk, val_out, idx_out), "topk result");
   if (topk) {
-    GPX_TRY(hip_check(c, gpx::launch_topk(c, tks.scores, m, k, idx_out, val_out, tks.sort_ws, tks.sort_bytes), "topk"));
+    GPX_TRY(hip_check(c, gpx::launch_topk(c, w.tk.scores, m, k, idx_out, val_out, w.tk.sort_ws, w.tk.sort_bytes), "topk"));
     return hip_check(c, gpx::launch_index_shift(c, idx_out, k, index_offset), "topk indices");
   }
-  return hip_check(c, gpx::launch_argmax_final(c, b.rec_val, b.rec_idx, rec, best_val, best_idx), "argmax");
+  return hip_check(c, gpx::launch_argmax_final(c, lazy ? w.ph.rec_val : b.rec_val, lazy ? w.ph.rec_idx : b.rec_idx, rec,
+                                               best_val, best_idx),
+                   "argmax");
 }
 
 gpx_status gpx_acquire_argmax_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X, int64_t ldx,
@@ -1205,8 +1176,7 @@ gpx_status gpx_acquire_argmax_f64(gpx_handle h, const gpx_kernel_params* p, int6
 
 gpx_status gpx_acquire_topk_workspace_size(int64_t n, int64_t m, int64_t k, size_t* bytes) {
   if (!bytes || n < 1 || m < 1 || k < 1 || k > m || k > GPX_TOPK_SWEEP_MAX) return GPX_INVALID_ARG;
-  const int64_t npad = padded(n);
-  *bytes = gpx::sweep_workspace_bytes(npad, 1, m) + gpx::topk_sweep_bytes(npad, m, k);
+  *bytes = gpx::sweep_layout(padded(n), 1, m, k, false, gpx::topk_workspace_bytes(m)).total;
   return GPX_OK;
 }
 
@@ -1248,15 +1218,9 @@ gpx_status gpx_debug_kstar_f64(gpx_handle h, const gpx_kernel_params* p, int64_t
                                double* out, int64_t ldout, void* ws, size_t ws_bytes) {
   Context* c = reinterpret_cast<Context*>(h);
   if (!c) return GPX_INVALID_ARG;
-  GPX_TRY(check_params(c, p));
-  GPX_TRY(check_n(c, n));
-  if (m < 1 || m > ((int64_t)1 << 30)) return fail(c, GPX_INVALID_ARG, "m must be in [1, 2^30]");
-  GPX_NONNULL(c, X);
-  GPX_NONNULL(c, Xs);
-  GPX_NONNULL(c, out);
+  GPX_TRY(check_sweep_sizes(c, p, n, m, kDebugMaxM));
+  GPX_TRY(check_sweep_arrays(c, {{X, "X"}, {Xs, "Xs"}, {out, "out"}}, p, ldx, ldxs));
   const int64_t npad = padded(n);
-  GPX_TRY(check_ld(c, ldx, p->d, "X", false));
-  GPX_TRY(check_ld(c, ldxs, p->d, "Xs", false));
   if (ldout < (m + 255) / 256 * 256) return fail(c, GPX_INVALID_ARG, "ldout must be >= m rounded up to 256");
   if (list && !count) return fail(c, GPX_INVALID_ARG, "count is NULL");
   if (list && !gpx::sweep_lazy_ok(*p))
@@ -1269,10 +1233,8 @@ gpx_status gpx_debug_kstar_f64(gpx_handle h, const gpx_kernel_params* p, int64_t
     scratch = align256(ws);
   }
   GPX_USE_DEVICE(c);
-  return hip_check(c,
-                   gpx::launch_debug_kstar(c, *p, (int)n, (int)npad, X, ldx, Xs, ldxs, m, list, count, out, ldout,
-                                           scratch),
-                   "debug_kstar");
+  const gpx::SweepModel M{c, *p, (int)n, (int)npad, X, ldx, nullptr, 0, nullptr, 1};
+  return hip_check(c, gpx::launch_debug_kstar(M, {Xs, ldxs, m, 0}, list, count, out, ldout, scratch), "debug_kstar");
 }
 
 gpx_status gpx_debug_kstar_mu_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X, int64_t ldx,
@@ -1280,25 +1242,17 @@ gpx_status gpx_debug_kstar_mu_f64(gpx_handle h, const gpx_kernel_params* p, int6
                                   const int32_t* count, double* out, int64_t ldout, double* mu_part, int64_t ldmu) {
   Context* c = reinterpret_cast<Context*>(h);
   if (!c) return GPX_INVALID_ARG;
-  GPX_TRY(check_params(c, p));
-  GPX_TRY(check_n(c, n));
-  if (m < 1 || m > ((int64_t)1 << 30)) return fail(c, GPX_INVALID_ARG, "m must be in [1, 2^30]");
-  GPX_NONNULL(c, X);
-  GPX_NONNULL(c, alpha);
-  GPX_NONNULL(c, Xs);
-  GPX_NONNULL(c, out);
-  GPX_NONNULL(c, mu_part);
+  GPX_TRY(check_sweep_sizes(c, p, n, m, kDebugMaxM));
+  GPX_TRY(check_sweep_arrays(c, {{X, "X"}, {alpha, "alpha"}, {Xs, "Xs"}, {out, "out"}, {mu_part, "mu_part"}}, p, ldx,
+                             ldxs));
   const int64_t npad = padded(n);
-  GPX_TRY(check_ld(c, ldx, p->d, "X", false));
-  GPX_TRY(check_ld(c, ldxs, p->d, "Xs", false));
   if (ldout < (m + 255) / 256 * 256) return fail(c, GPX_INVALID_ARG, "ldout must be >= m rounded up to 256");
   if (list && !count) return fail(c, GPX_INVALID_ARG, "count is NULL");
   if (list && ldmu < 1) return fail(c, GPX_INVALID_ARG, "ldmu must be >= 1");
   if (!gpx::sweep_lazy_ok(*p)) return fail(c, GPX_INVALID_ARG, "the MFMA K* build covers the fp64 covariance with d <= 16");
   GPX_USE_DEVICE(c);
-  return hip_check(c,
-                   gpx::launch_debug_kstar(c, *p, (int)n, (int)npad, X, ldx, Xs, ldxs, m, list, count, out, ldout,
-                                           nullptr, alpha, mu_part, ldmu),
+  const gpx::SweepModel M{c, *p, (int)n, (int)npad, X, ldx, nullptr, 0, alpha, 1};
+  return hip_check(c, gpx::launch_debug_kstar(M, {Xs, ldxs, m, 0}, list, count, out, ldout, nullptr, mu_part, ldmu),
                    "debug_kstar_mu");
 }
 
@@ -1350,34 +1304,23 @@ gpx_status gpx_debug_mu_bound_f64(gpx_handle h, const gpx_kernel_params* p, int6
                                   double* mu_slack, void* ws, size_t ws_bytes) {
   Context* c = reinterpret_cast<Context*>(h);
   if (!c) return GPX_INVALID_ARG;
-  GPX_TRY(check_params(c, p));
-  GPX_TRY(check_n(c, n));
-  if (m < 1 || m > ((int64_t)1 << 30)) return fail(c, GPX_INVALID_ARG, "m must be in [1, 2^30]");
-  GPX_NONNULL(c, X);
-  GPX_NONNULL(c, alpha);
-  GPX_NONNULL(c, Xs);
-  GPX_NONNULL(c, mu_approx);
-  GPX_NONNULL(c, mu_slack);
+  GPX_TRY(check_sweep_sizes(c, p, n, m, kDebugMaxM));
+  GPX_TRY(check_sweep_arrays(c, {{X, "X"}, {alpha, "alpha"}, {Xs, "Xs"}, {mu_approx, "mu_approx"},
+                                 {mu_slack, "mu_slack"}}, p, ldx, ldxs));
   const int64_t npad = padded(n);
-  GPX_TRY(check_ld(c, ldx, p->d, "X", false));
-  GPX_TRY(check_ld(c, ldxs, p->d, "Xs", false));
   if (!gpx::sweep_mu_bound_ok(*p))
     return fail(c, GPX_INVALID_ARG, "the mean bound covers the RBF kernel, the fp64 covariance and d <= 16");
   size_t need = 0;
   GPX_TRY(gpx_debug_mu_bound_workspace_size(n, &need));
   if (!ws || ws_bytes < need) return fail(c, GPX_INVALID_ARG, "debug_mu_bound workspace too small");
   GPX_USE_DEVICE(c);
-  return hip_check(c,
-                   gpx::launch_mu_bound(c, *p, (int)n, (int)npad, X, ldx, alpha, Xs, ldxs, m, align256(ws), mu_approx,
-                                        mu_slack),
-                   "debug_mu_bound");
+  const gpx::SweepModel M{c, *p, (int)n, (int)npad, X, ldx, nullptr, 0, alpha, 1};
+  return hip_check(c, gpx::launch_mu_bound(M, {Xs, ldxs, m, 0}, align256(ws), mu_approx, mu_slack), "debug_mu_bound");
 }
 
 gpx_status gpx_sweep_multi_workspace_size(int64_t n, int64_t m, size_t* bytes) {
   if (!bytes || n < 1 || m < 1) return GPX_INVALID_ARG;
-  const int64_t npad = padded(n);
-  *bytes = ((gpx::sweep_workspace_bytes(npad, 1, m) + 255) & ~(size_t)255) +
-           2 * (size_t)gpx::sweep_chunk_size(npad, m) * sizeof(double) + 256;
+  *bytes = gpx::sweep_layout(padded(n), 1, m, 0, true).total;
   return GPX_OK;
 }
 
@@ -1400,54 +1343,37 @@ gpx_status gpx_acquire_argmax_multi_f64(gpx_handle h, const gpx_kernel_params* p
     if (!std::isfinite(weights_host[t])) return fail(c, GPX_INVALID_ARG, "objective weights must be finite");
     if (y_scale_host && !(y_scale_host[t] > 0.0)) return fail(c, GPX_INVALID_ARG, "y_scale must be positive");
   }
-  GPX_TRY(check_n(c, n));
-  if (m < 1) return fail(c, GPX_INVALID_ARG, "m must be >= 1");
-  if (!a) return fail(c, GPX_INVALID_ARG, "acquisition params pointer is NULL");
-  if (a->kind < GPX_ACQ_EI || a->kind > GPX_ACQ_VARIANCE) return fail(c, GPX_INVALID_ARG, "unknown acquisition kind");
-  if (a->reserved != 0) return fail(c, GPX_INVALID_ARG, "gpx_acq_params.reserved must be 0");
-  if (a->kind == GPX_ACQ_UCB && !(a->beta >= 0.0)) return fail(c, GPX_INVALID_ARG, "UCB beta must be >= 0");
-  if (index_offset < 0) return fail(c, GPX_INVALID_ARG, "index_offset must be >= 0");
-  GPX_NONNULL(c, X);
-  GPX_NONNULL(c, W_host);
-  GPX_NONNULL(c, ldw_host);
-  GPX_NONNULL(c, alpha_host);
-  GPX_NONNULL(c, Xs);
-  GPX_NONNULL(c, best_val);
-  GPX_NONNULL(c, best_idx);
-  GPX_NONNULL(c, ws);
+  GPX_TRY(check_sweep_sizes(c, p, n, m));
+  GPX_TRY(check_acq(c, a, index_offset, false));
+  GPX_TRY(check_sweep_arrays(c, {{X, "X"}, {W_host, "W_host"}, {ldw_host, "ldw_host"}, {alpha_host, "alpha_host"},
+                                 {Xs, "Xs"}, {best_val, "best_val"}, {best_idx, "best_idx"}, {ws, "ws"}}, p, ldx, ldxs));
   const int64_t npad = padded(n);
-  GPX_TRY(check_ld(c, ldx, p->d, "X", false));
-  GPX_TRY(check_ld(c, ldxs, p->d, "Xs", false));
   for (int64_t t = 0; t < T; ++t) {
     if (!W_host[t] || !alpha_host[t]) return fail(c, GPX_INVALID_ARG, "W / alpha of output " + std::to_string(t) + " is NULL");
     GPX_TRY(check_ld(c, ldw_host[t], npad, "W", true));
   }
-  size_t need = 0;
-  GPX_TRY(gpx_sweep_multi_workspace_size(n, m, &need));
-  if (ws_bytes < need) return fail(c, GPX_INVALID_ARG, "multi-output sweep workspace too small");
-  gpx::SweepBuffers b;
-  const size_t sweep_bytes = (gpx::sweep_workspace_bytes(npad, 1, m) + 255) & ~(size_t)255;
-  GPX_TRY(carve_sweep(c, npad, 1, m, ws, sweep_bytes, &b));
+  gpx::SweepWorkspace w;
+  GPX_TRY(carve_sweep(c, gpx::sweep_layout(npad, 1, m, 0, true), ws, ws_bytes, "multi-output sweep workspace too small",
+                      &w));
+  const gpx::SweepBuffers& b = w.b;
   GPX_USE_DEVICE(c);
   gpx::MultiOutput mo;
-  mo.acc_mu = reinterpret_cast<double*>(reinterpret_cast<char*>(align256(ws)) + sweep_bytes);
-  mo.acc_var = mo.acc_mu + b.chunk;
+  mo.acc_mu = w.acc_mu;
+  mo.acc_var = w.acc_var;
   int64_t rec = 0;
   for (int64_t s = 0; s < m; s += b.chunk) {
-    const int64_t mc = (m - s) < b.chunk ? (m - s) : b.chunk;
+    const int64_t mc = gpx::sweep_span_size(false, s, m, b.chunk, 0);
     for (int64_t t = 0; t < T; ++t) {
       mo.weight = weights_host[t];
       mo.y_mean = y_mean_host ? y_mean_host[t] : 0.0;
       mo.y_scale = y_scale_host ? y_scale_host[t] : 1.0;
       mo.first = t == 0;
-      GPX_TRY(hip_check(c,
-                        gpx::launch_sweep_chunk(c, p[t], (int)n, (int)npad, X, ldx, W_host[t], ldw_host[t],
-                                                alpha_host[t], 1, Xs + s * ldxs, ldxs, mc, b, 1, a, nullptr,
-                                                nullptr, nullptr, 0, nullptr, nullptr, 0, 0, &mo),
+      const gpx::SweepModel M{c, p[t], (int)n, (int)npad, X, ldx, W_host[t], ldw_host[t], alpha_host[t], 1};
+      GPX_TRY(hip_check(c, gpx::launch_sweep_chunk(M, {Xs + s * ldxs, ldxs, mc, 0}, b, 1, a, gpx::SweepOut(), 0, &mo),
                         "acquire (multi-output)"));
     }
-    GPX_TRY(hip_check(c, gpx::launch_multi_score(c, mo, *a, mc, scores_out ? scores_out + s : nullptr, b.rec_val + rec,
-                                                 b.rec_idx + rec, index_offset + s),
+    GPX_TRY(hip_check(c, gpx::launch_multi_score(c, {nullptr, 0, mc, index_offset + s}, mo, *a,
+                                                 scores_out ? scores_out + s : nullptr, b.rec_val + rec, b.rec_idx + rec),
                       "acquire (multi-output score)"));
     rec += (mc + 255) / 256;
   }
@@ -1567,8 +1493,8 @@ gpx_status gpx_svgp_prepare_f64(gpx_handle h, const gpx_kernel_params* p, int64_
 gpx_status gpx_svgp_predict_workspace_size(int64_t M, int64_t m, size_t* bytes) {
   if (!bytes || M < 1 || m < 1) return GPX_INVALID_ARG;
   const int64_t Mpad = padded(M);
-  const int64_t C = gpx::sweep_chunk_size(Mpad, m);
-  *bytes = gpx::sweep_workspace_bytes(Mpad, 1, m) + (size_t)(Mpad / 128) * C * 8 + 512;
+  const gpx::SweepLayout L = gpx::sweep_layout(Mpad, 1, m);
+  *bytes = L.total + (size_t)(Mpad / 128) * L.C * 8 + 512;
   return GPX_OK;
 }
 
@@ -1598,9 +1524,9 @@ gpx_status gpx_svgp_predict_f64(gpx_handle h, const gpx_kernel_params* p, int64_
   size_t need = 0;
   GPX_TRY(gpx_svgp_predict_workspace_size(M, m, &need));
   if (ws_bytes < need) return fail(c, GPX_INVALID_ARG, "svgp predict workspace too small");
-  gpx::SweepBuffers b;
-  GPX_TRY(carve_sweep(c, Mpad, 1, m, ws, ws_bytes, &b));
-  double* ss2 = reinterpret_cast<double*>(((uintptr_t)(b.rec_idx + (m + 255) / 256 + 1) + 255) & ~(uintptr_t)255);
+  const gpx::SweepWorkspace w = gpx::sweep_carve(ws, gpx::sweep_layout(Mpad, 1, m));
+  const gpx::SweepBuffers& b = w.b;
+  double* ss2 = w.after_main;  // (over the pruned part of the sweep's layout, which this call does not use)
   GPX_USE_DEVICE(c);
   for (int64_t s = 0; s < m; s += b.chunk) {
     const int64_t mc = (m - s) < b.chunk ? (m - s) : b.chunk;

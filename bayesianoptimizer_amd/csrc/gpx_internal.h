@@ -6,12 +6,11 @@
 #include <string>
 #include <vector>
 #include "../../include/gpx.h"
+#include "gpx_sweep_layout.h"  // NB, TILE, TT, WG, the PRUNE_* sizes and the sweep's workspace layout
 
 namespace gpx {
 
-constexpr int NB = 64;              // Cholesky / TRTRI block (64x64 diagonal blocks)
-constexpr int TILE = GPX_TILE;      // padding granule and sweep tile (128)
-constexpr int WG = 256;             // threads per workgroup (4 waves of 64)
+static_assert(TILE == GPX_TILE, "the padding granule of the C ABI");
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
@@ -152,23 +151,41 @@ struct MultiOutput {
   double* acc_mu = nullptr;
   double* acc_var = nullptr;
 };
+// What every launch of the sweep reads: the fitted model, and the candidates of one chunk, super-chunk or round.
+struct SweepModel {
+  Context* c;
+  const gpx_kernel_params& p;
+  int n, npad;
+  const double* X; int64_t ldx;
+  const double* W; int64_t ldw;
+  const double* alpha; int nrhs;
+};
+struct SweepCands {
+  const double* Xs;
+  int64_t ldxs, m, index_offset;  // (the global index of candidate 0)
+  SweepCands first(int64_t count) const { return {Xs, ldxs, count, index_offset}; }  // the leading `count` of them
+};
+// Per-candidate outputs of launch_sweep_chunk: the posterior's (mode 0: y_mean / y_scale per output, nullptr = identity)
+// or the acquisition's optional scores (mode 1).
+struct SweepOut {
+  double* scores = nullptr;
+  const double* y_mean = nullptr;
+  const double* y_scale = nullptr;
+  double* mean = nullptr;
+  int64_t ldmean = 0;
+  double* var = nullptr;
+};
 // mode 0: posterior (write mean/var); mode 1: acquisition (records + optional scores); mo != nullptr: accumulate one
 // output of a multi-output objective instead (mode ignored), scored afterwards by launch_multi_score
-hipError_t launch_sweep_chunk(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X, int64_t ldx,
-                              const double* W, int64_t ldw, const double* alpha, int nrhs, const double* Xs,
-                              int64_t ldxs, int64_t m_chunk, const SweepBuffers& b, int mode,
-                              const gpx_acq_params* a, const double* y_mean, const double* y_scale,
-                              double* mean_out, int64_t ldmean, double* var_out, double* scores_out,
-                              int64_t rec_offset, int64_t index_offset, const MultiOutput* mo = nullptr);
+hipError_t launch_sweep_chunk(const SweepModel& M, const SweepCands& q, const SweepBuffers& b, int mode,
+                              const gpx_acq_params* a, const SweepOut& out = SweepOut(), int64_t rec_offset = 0,
+                              const MultiOutput* mo = nullptr);
 
 // ---- pruned acquisition sweep (gpx_sweep.hip) ----------------------------------------------
 // The product's row tiles run in stages [R_s, R_{s+1}); after each stage but the last, candidates whose score upper
 // bound (variance bound from the row tiles done so far) lies below the incumbent are dropped, and the surviving K*
 // columns are gathered into a compact buffer once they are at most half of the active ones.  All state is on the device.
-constexpr int PRUNE_MIN_NPAD = 384;     // below: the fused sweep, or one or two row tiles (nothing to stage)
-constexpr int PRUNE_DEFAULT_NPAD = 384; // sweep_prune = 1 prunes from this padded n on
-constexpr int PRUNE_SEED = 1024;        // leading candidates of a call scored in full: the first incumbent
-constexpr int PRUNE_MAX_STAGES = 8;
+constexpr int PRUNE_DEFAULT_NPAD = 384; // sweep_prune = 1 prunes from this padded n on (>= PRUNE_MIN_NPAD)
 struct PruneDesc {  // the active column set of one stage (written by the launch before it, read by its launches)
   int buf;     // 0: the chunk's K*, 1 / 2: the compact buffers
   int col0;    // first column in the buffer (buf 0 only: the columns after the seed block)
@@ -178,6 +195,7 @@ struct PruneDesc {  // the active column set of one stage (written by the launch
                // round's part of the head phase's survivor list (lazy form)
   int pad[3];
 };
+static_assert(sizeof(PruneDesc) == PRUNE_DESC_BYTES, "the layout's descriptor slots");
 struct PruneState {  // device pointers into the sweep workspace
   double* cbuf[2];   // compact K* buffers (npad rows)
   int64_t ldc[2];    // C/2 and C/4 columns (rounded up to the tile)
@@ -187,8 +205,6 @@ struct PruneState {  // device pointers into the sweep workspace
   unsigned long long* tau;  // the incumbent, as an order-preserving key (atomic max)
   int64_t* stats;    // {candidates computed to the last row tile, 128 x 128 product tiles executed}
 };
-size_t sweep_prune_bytes(int64_t npad, int64_t m);
-void sweep_prune_carve(void* base, int64_t npad, int64_t C, PruneState* ps);
 // The top-k form of the pruned sweep (gpx_acquire_topk_f64): device pointers into the call's top-k workspace.
 // Every launch that scores candidates in full appends their (score, global index) to the scored list, and
 // topk_pool_kernel, enqueued behind it, merges the list into the pool of the k best pairs so far and sets the incumbent
@@ -205,8 +221,6 @@ struct TopkSweep {
   void* sort_ws;
   size_t sort_bytes;
 };
-size_t topk_sweep_bytes(int64_t npad, int64_t m, int64_t k);
-void topk_sweep_carve(void* base, int64_t npad, int64_t m, int64_t k, TopkSweep* tk);
 // the pool's pairs to the caller's arrays (pruned path) / the composed path's local indices to global ones
 hipError_t launch_topk_result(Context* c, const TopkSweep& tk, double* val_out, int64_t* idx_out);
 hipError_t launch_index_shift(Context* c, int64_t* idx, int64_t k, int64_t offset);
@@ -216,13 +230,10 @@ bool sweep_prune_ok(const Context* c, const gpx_kernel_params& p, int npad);
 // One chunk of gpx_acquire_argmax_f64 through the staged product; first: the call's first chunk (resets the incumbent
 // and the counters, scores the seed block in full).  host_stats[1], [2] gain the seed block's share.  tk: the top-k form
 // (gpx_acquire_topk_f64): same launches, the incumbent is the k-th best exact score instead of the best.
-hipError_t launch_sweep_chunk_pruned(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X,
-                                     int64_t ldx, const double* W, int64_t ldw, const double* alpha, const double* Xs,
-                                     int64_t ldxs, int64_t m_chunk, const SweepBuffers& b, const PruneState& ps,
-                                     const gpx_acq_params* a, int64_t rec_offset, int64_t index_offset, bool first,
+hipError_t launch_sweep_chunk_pruned(const SweepModel& M, const SweepCands& q, const SweepBuffers& b,
+                                     const PruneState& ps, const gpx_acq_params* a, int64_t rec_offset, bool first,
                                      int64_t* host_stats, const TopkSweep* tk = nullptr);
 // The lazy form (launch_sweep_super_pruned): K* in full height only for the survivors of the first row tile.
-constexpr int PRUNE_HEAD_ROWS = 128;  // K* rows the head phase stores: the product's first row tile
 struct PruneHead {    // device pointers into the sweep workspace, after the compact buffers
   int64_t super;      // candidates per super-chunk (sweep_super_size); the pitch of the three arrays below
   int2* survivors;    // the head phase's survivor list: {super-chunk column, slot}; super + 128 entries
@@ -231,25 +242,50 @@ struct PruneHead {    // device pointers into the sweep workspace, after the com
   double* ss_part;    // (npad/128) x super
   double* rec_val;    // records of the call
   int64_t* rec_idx;
+  double* prep;       // the mean bound's scratch: SweepLayout::mu_prep, a view of the chunk's K*
 };
-int64_t sweep_super_size(int64_t npad, int64_t m);
-void sweep_prune_carve_head(const PruneState& ps, int64_t npad, int64_t C, int64_t MA, int64_t m, PruneHead* ph);
+// Every pointer a sweep call has into its workspace, from the one layout (gpx_sweep_layout.h).  The parts the layout
+// leaves out (bytes = 0) are null.
+struct SweepWorkspace {
+  SweepBuffers b;
+  PruneState ps;
+  PruneHead ph;
+  TopkSweep tk;
+  double *acc_mu, *acc_var;  // the multi-output accumulators (MultiOutput)
+  double* after_main;  // SweepLayout::after_main (the SVGP predictive keeps its second partials there)
+};
+inline SweepWorkspace sweep_carve(void* ws, const SweepLayout& L, int64_t k = 0) {
+  char* base = reinterpret_cast<char*>(up256(reinterpret_cast<uintptr_t>(ws)));
+  auto at = [&](SweepRegion id) { return L.r[id].bytes ? base + L.r[id].at : nullptr; };
+  auto dbl = [&](SweepRegion id) { return reinterpret_cast<double*>(at(id)); };
+  auto i64 = [&](SweepRegion id) { return reinterpret_cast<int64_t*>(at(id)); };
+  auto i2 = [&](SweepRegion id) { return reinterpret_cast<int2*>(at(id)); };
+  SweepWorkspace w;
+  w.b = {dbl(SR_KSTAR), dbl(SR_MU_PART), dbl(SR_SS_PART), dbl(SR_REC_VAL), i64(SR_REC_IDX), L.C};
+  w.ps = {{dbl(SR_CBUF0), dbl(SR_CBUF1)}, {prune_ld(L.C, 0), prune_ld(L.C, 1)}, {i2(SR_LIST0), i2(SR_LIST1)},
+          reinterpret_cast<PruneDesc*>(at(SR_DESC)), reinterpret_cast<int*>(at(SR_COUNT)),
+          reinterpret_cast<unsigned long long*>(at(SR_TAU)), i64(SR_STATS)};
+  w.ph = {L.MA, i2(SR_SURVIVORS), dbl(SR_HEAD), dbl(SR_HEAD_MU_PART), dbl(SR_HEAD_SS_PART), dbl(SR_LAZY_REC_VAL),
+          i64(SR_LAZY_REC_IDX), L.mu_prep.bytes ? reinterpret_cast<double*>(base + L.mu_prep.at) : nullptr};
+  w.tk = {(int)k, reinterpret_cast<int*>(at(SR_TOPK_HEAD)), dbl(SR_POOL_VAL), i64(SR_POOL_IDX), dbl(SR_LIST_VAL),
+          i64(SR_LIST_IDX), dbl(SR_SCORES), at(SR_SORT_WS), L.r[SR_SORT_WS].bytes};
+  w.acc_mu = dbl(SR_ACC_MU);
+  w.acc_var = dbl(SR_ACC_VAR);
+  w.after_main = reinterpret_cast<double*>(base + L.after_main);
+  return w;
+}
 // the configurations of the MFMA K* build (fp64 covariance, d <= 16); the others keep launch_sweep_chunk_pruned
 bool sweep_lazy_ok(const gpx_kernel_params& p);
 // One super-chunk of gpx_acquire_argmax_f64; first: the call's first (resets the incumbent and the counters, scores the
 // seed block in full).  *recs: the records written so far, advanced.  host_stats as above.
-hipError_t launch_sweep_super_pruned(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X,
-                                     int64_t ldx, const double* W, int64_t ldw, const double* alpha, const double* Xs,
-                                     int64_t ldxs, int64_t m_super, const SweepBuffers& b, const PruneState& ps,
-                                     const PruneHead& ph, const gpx_acq_params* a, int64_t* recs, int64_t index_offset,
+hipError_t launch_sweep_super_pruned(const SweepModel& M, const SweepCands& q, const SweepBuffers& b,
+                                     const PruneState& ps, const PruneHead& ph, const gpx_acq_params* a, int64_t* recs,
                                      bool first, int64_t* host_stats, const TopkSweep* tk = nullptr);
 // K(X, Xs) through the sweep's K* build (gpx_debug_kstar_f64): list = nullptr the full-store build of columns 0 .. m-1,
 // else the gather build of columns list[0 .. *count - 1] (m: the most the list can hold).  out: npad rows of pitch ldout.
-hipError_t launch_debug_kstar(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X, int64_t ldx,
-                              const double* Xs, int64_t ldxs, int64_t m, const int* list, const int* count,
-                              double* out, int64_t ldout, double* mu_scratch, const double* alpha = nullptr,
-                              double* mu_part = nullptr, int64_t ldmu = 0);
-// (alpha != nullptr, gpx_debug_kstar_mu_f64: the build's mean partials too.  Full build: mu_part[jb * ldout + c], no
+hipError_t launch_debug_kstar(const SweepModel& M, const SweepCands& q, const int* list, const int* count, double* out,
+                              int64_t ldout, double* mu_scratch, double* mu_part = nullptr, int64_t ldmu = 0);
+// (M.alpha != nullptr, gpx_debug_kstar_mu_f64: the build's mean partials too.  Full build: mu_part[jb * ldout + c], no
 // scratch; gather build: mu_part[jb * ldmu + list[s]], the partials KSTAR_FULL gives that candidate, other entries kept.)
 // One stage of the staged product in a named tile shape (gpx_debug_stage_product_f64): row tiles I0 .. I0 + nrows - 1
 // over slots 0 .. ncols - 1 of kstar (pitch ldk), shape 0 wide / 1 narrow, list (device, ncols entries, optional) the
@@ -262,12 +298,9 @@ hipError_t launch_debug_stage_product(Context* c, int npad, const double* W, int
 // mu_approx[c] +- mu_slack[c] holds the exact path's mean of candidate c.  prep: mu_prep_doubles(npad, d) doubles,
 // 256-byte aligned; its first int64 ends up as the count of 256-candidate workgroups on the unfactorised path.
 bool sweep_mu_bound_ok(const gpx_kernel_params& p);
-size_t mu_prep_doubles(int64_t npad, int d);
-hipError_t launch_mu_bound(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X, int64_t ldx,
-                           const double* alpha, const double* Xs, int64_t ldxs, int64_t m_chunk, double* prep,
-                           double* mu_approx, double* mu_slack);
-hipError_t launch_multi_score(Context* c, const MultiOutput& mo, const gpx_acq_params& a, int64_t m_chunk,
-                              double* scores_out, double* rec_val, int64_t* rec_idx, int64_t index_offset);
+hipError_t launch_mu_bound(const SweepModel& M, const SweepCands& q, double* prep, double* mu_approx, double* mu_slack);
+hipError_t launch_multi_score(Context* c, const SweepCands& q, const MultiOutput& mo, const gpx_acq_params& a,
+                              double* scores_out, double* rec_val, int64_t* rec_idx);
 hipError_t launch_argmax_final(Context* c, const double* vals, const int64_t* idx, int64_t count, double* best_val,
                                int64_t* best_idx);
 // the cross-GPU exchange (gpx_comm.cpp): pack the device record into {double value; int64 index}, and reduce
@@ -331,8 +364,5 @@ size_t mll_workspace_bytes(int64_t npad);
 hipError_t launch_mll(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X, int64_t ldx,
                       const double* Y, int64_t ldy, int nrhs, const double* L, int64_t ldl, const double* W,
                       int64_t ldw, const double* alpha, double* out, double* part);
-
-int64_t sweep_chunk_size(int64_t npad, int64_t m);
-size_t sweep_workspace_bytes(int64_t npad, int64_t nrhs, int64_t m);
 
 }  // namespace gpx

@@ -14,20 +14,20 @@
 //                    GPyTorch/BoTorch variance floors, Standardize untransform, analytic acquisition, and a
 //                    256-candidate block argmax record (max value, then lowest index; NaN never wins).
 // launch_argmax_final reduces the records of the whole sweep in one workgroup.
-//
 // gpx_acquire_argmax_f64 without scores_out takes the PRUNED form of launch 2 (launch_sweep_chunk_pruned):
 // the row tiles run in stages (trmm_stage_kernel; after the first trmm_stage_dual_kernel, whose workgroups take a
-// 128 x 32 tile when the stage has fewer 128 x 128 tiles than the device has CUs); after each stage finalize_kernel mode 4 bounds every active
-// candidate's score from the partials it has, drops those that cannot reach the best score computed in full so far,
-// and prune_compact_kernel gathers the surviving K* columns; finalize scores the survivors of the last stage.  The
-// (value, index) pair has the bits of the full sweep.  Where the MFMA K* build applies, the pruned form is lazy
-// (launch_sweep_super_pruned): K* rows 0 .. 127 and the mean partials for every candidate of a super-chunk, the first
-// stage and its bound pass as one launch each, and full-height K* columns rebuilt from the survivor list for the rest.
-// gpx_acquire_topk_f64 is the same pruned sweep with the k-th best exact score as its incumbent (topk_pool_kernel).
+// 128 x 32 tile when the stage has fewer 128 x 128 tiles than the device has CUs); after each stage finalize_kernel
+// mode 4 drops the candidates whose score bound cannot reach the best score computed in full so far, and
+// prune_compact_kernel gathers the surviving K* columns; the (value, index) pair has the bits of the full sweep.  Where
+// the MFMA K* build applies the pruned form is lazy (launch_sweep_super_pruned): K* rows 0 .. 127 for every candidate,
+// full-height columns rebuilt from the survivor list.  Both share launch_seed_block and launch_stages;
+// gpx_acquire_topk_f64 is the same sweep with the k-th best exact score as its incumbent (topk_pool_kernel).
+// The workspace is described once, in gpx_sweep_layout.h (sweep_carve, gpx_internal.h, turns it into pointers).
 #include "gpx_internal.h"
 #include "gpx_device.h"
 #include "gpx_trmm_asm.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace gpx {
 
@@ -511,7 +511,7 @@ constexpr double MUF_LOG2E = 1.44269504088896340735992468100189;
 //  Only DMAX = 8 is built.  At DMAX = 16 the limit admits Y_c < 3.6 only, which unit-cube candidates do not meet; at
 //  DMAX = 4 the form was built and tested (with runs of 16), but its looser bound let three more candidates of 45,000
 //  through the head in a d = 4 call whose sweep_stats tests/test_gpu_sweep_narrow.py pins, so d <= 4 keeps the fp64 form.
-constexpr bool mu_fp32_form(int DMAX) { return DMAX == 8; }
+// (mu_fp32_form(DMAX), gpx_sweep_layout.h: DMAX == 8)
 constexpr double MUF32_EPS1_MAX = 0x1p-18;
 constexpr int MUF32_RUN = 8;  // rows a lane sums in fp32 before the run goes to the fp64 sums (8 or 16; see (g32))
 typedef float f4 __attribute__((ext_vector_type(4)));  // v_mfma_f32_16x16x4_f32's accumulator
@@ -520,7 +520,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));  // v_mfma_f32_16x16x4_f32
 // records (MuFact) and the row blocks' sums and maxima (MuStat).
 constexpr int MUF_FALLBACK = 0;  // int64: workgroups of the last call that took mu_bound_kernel's path
 constexpr int MUF_FP64FORM = 20;  // int64: workgroups of the last call that took mu_fact_kernel (the fp64 factorised form)
-constexpr int MUF_M2 = 1, MUF_SCALE = 2, MUF_L1 = 3, MUF_CEN = 4, MUF_HEAD = 32;
+constexpr int MUF_M2 = 1, MUF_SCALE = 2, MUF_L1 = 3, MUF_CEN = 4;  // (MUF_HEAD: gpx_sweep_layout.h)
 
 // Per row block of 64 training rows: kstar_mfma_kernel's prologue (scaled rows, centre = mean of the valid rows, centred
 // rows, their norms), alpha with zeros for the padded rows, and sum |alpha| of the block.  Layout of a block's record:
@@ -547,11 +547,11 @@ template <int DMAX>
 struct MuStat {
   static constexpr int SUM = 0, M2 = DMAX, AM = DMAX + 1, L1 = DMAX + 2, STRIDE = DMAX + 4;
 };
-size_t mu_prep_doubles(int64_t npad, int d) {
-  const int D = d <= 4 ? 4 : d <= 8 ? 8 : 16;
-  const int f32 = mu_fp32_form(D) ? (NB * D + NB) / 2 : 0;  // MuFact32
-  return MUF_HEAD + (size_t)(npad / NB) * ((NB * D + 2 * NB + D + 2) + (NB * D + NB / 2) + (D + 4) + f32);
-}
+// mu_prep_doubles (gpx_sweep_layout.h) is the sum of a row block's records
+template <int D>
+constexpr bool mu_prep_matches_layout =
+    mu_prep_block_doubles(D) == MuPrep<D>::STRIDE + MuFact<D>::STRIDE + MuStat<D>::STRIDE + MuFact32<D>::STRIDE_D;
+static_assert(mu_prep_matches_layout<4> && mu_prep_matches_layout<8> && mu_prep_matches_layout<16>, "mu_prep");
 template <int DMAX>
 __device__ __forceinline__ double* mu_stat(double* prep, int npad, int jb) {
   return prep + MUF_HEAD + (int64_t)(npad / NB) * (MuPrep<DMAX>::STRIDE + MuFact<DMAX>::STRIDE) +
@@ -1120,7 +1120,7 @@ __global__ void __launch_bounds__(WG) mu_fact_kernel(gpx_kernel_params p, int n,
 }
 
 // ---- 2. triangular product + column sums of squares ------------------------------------------------------
-constexpr int TT = 128;  // trmm tile (rows of V x candidates)
+// (TT = 128, gpx_sweep_layout.h: the trmm tile, rows of V x candidates)
 using TrmmTile = MfmaTile<TT, TT, 16, true, true>;  // its accumulator layout (row_of / col_of) and LDS size
 static_assert(TrmmTile::LDS_DOUBLES * 8 == trmm_asm::LDS_BYTES, "hand-placed tile uses MfmaTile's LDS image");
 
@@ -1959,129 +1959,6 @@ __global__ void __launch_bounds__(WG) index_shift_kernel(int64_t* __restrict__ i
 }
 
 // ---- host side -------------------------------------------------------------------------------------------
-int64_t sweep_chunk_size(int64_t npad, int64_t m) {
-  // K* chunk of at most ~1 GiB, multiple of 256 candidates (tools/chunk_sweep.sh at n = 4096: 256 MiB / 8192
-  // candidates -> 3.74e6, 512 MiB -> 3.78e6, 1 GiB / 32768 -> 3.81e6, 2 GiB / 65536 -> 3.73e6 candidates/s: fewer
-  // launch tails and K* / finalize launches until K* outgrows what the Infinity Cache keeps warm for the trmm
-  // re-reads).  The byte budget alone sets small-n chunks (tools/small_n_rates.py, 2^22 candidates: a 32768 cap
-  // left n = 64 / 256 launch-bound at 3.4e8 / 2.5e8 candidates/s, 1.15e9 / 4.4e8 without it).
-  int64_t cap = ((int64_t)1 << 30) / 8 / npad;
-  cap = (cap / 256) * 256;
-  if (cap < 256) cap = 256;
-  if (cap > ((int64_t)1 << 20)) cap = (int64_t)1 << 20;
-  int64_t need = ((m + 255) / 256) * 256;
-  if (need < 256) need = 256;
-  return need < cap ? need : cap;
-}
-
-size_t sweep_workspace_bytes(int64_t npad, int64_t nrhs, int64_t m) {
-  const int64_t C = sweep_chunk_size(npad, m);
-  const int64_t nrec = (m + 255) / 256 + 1;
-  size_t b = 0;
-  b += (size_t)npad * C * 8;                 // kstar
-  b += (size_t)(npad / NB) * nrhs * C * 8;   // mu_part
-  b += (size_t)(npad / TT) * C * 8;          // ss_part
-  b += (size_t)nrec * 16;                    // records
-  if (nrhs == 1) b += sweep_prune_bytes(npad, m);
-  return b + 256;
-}
-
-// The pruned sweep's part of the workspace, after the records: descriptors, counts, incumbent and counters (256 bytes
-// each), the two index lists, and the compact K* buffers of C/2 and C/4 columns (a compaction at least halves the
-// active columns, so they alternate: DESIGN §3).
-static int64_t prune_ld(int64_t C, int which) {
-  const int64_t cols = which == 0 ? C / 2 : C / 4;
-  return ((cols + TT - 1) / TT) * TT;
-}
-// The head phase's super-chunk: as many candidates as a byte budget over its per-candidate arrays holds (PRUNE_HEAD_ROWS
-// rows of K*, the mean partials of every 64-row block, the variance partials of every row tile), at most 2^20 and the
-// call, a multiple of 256.  1.75 GiB is 2^20 candidates at padded n = 4096; the budget bounds the arrays at any n.
-int64_t sweep_super_size(int64_t npad, int64_t m) {
-  const int64_t per = 8 * (PRUNE_HEAD_ROWS + npad / NB + npad / TT);
-  int64_t cap = ((((int64_t)7 << 28) / per) / 256) * 256;
-  if (cap > ((int64_t)1 << 20)) cap = (int64_t)1 << 20;
-  const int64_t C = sweep_chunk_size(npad, m);
-  if (cap < C) cap = C;  // (never at the sizes the library accepts: a column of K* outweighs the per-candidate arrays)
-  int64_t need = ((m + 255) / 256) * 256;
-  if (need < 256) need = 256;
-  return need < cap ? need : cap;
-}
-// Records of the lazy pruned sweep: per super-chunk the seed block's and one 256-candidate block per 256 columns of every
-// tail round it can need.
-static int64_t sweep_lazy_records(int64_t npad, int64_t m) {
-  const int64_t C = sweep_chunk_size(npad, m), MA = sweep_super_size(npad, m);
-  const int64_t supers = (m + MA - 1) / MA + 1, rounds = (MA + C - 1) / C;  // (+ 1: the call's short first one)
-  return PRUNE_SEED / WG + supers * rounds * (C / WG);
-}
-size_t sweep_prune_bytes(int64_t npad, int64_t m) {
-  if (npad < PRUNE_MIN_NPAD) return 0;
-  const int64_t C = sweep_chunk_size(npad, m), MA = sweep_super_size(npad, m);
-  static_assert(sizeof(PruneDesc) * PRUNE_MAX_STAGES <= 256 && sizeof(int) * PRUNE_MAX_STAGES <= 256, "header slots");
-  size_t b = 256 + 3 * 256 + 2 * (size_t)C * sizeof(int2) + (size_t)npad * (prune_ld(C, 0) + prune_ld(C, 1)) * 8;
-  // the head phase (launch_sweep_super_pruned): survivor list (+ one tile of padding slots), head rows, partials, records
-  b += (size_t)(MA + TT) * sizeof(int2);
-  b += (size_t)(PRUNE_HEAD_ROWS + npad / NB + npad / TT) * MA * 8;
-  b += (size_t)sweep_lazy_records(npad, m) * 16;
-  return b;
-}
-void sweep_prune_carve(void* base, int64_t npad, int64_t C, PruneState* ps) {
-  char* q = reinterpret_cast<char*>(((uintptr_t)base + 255) & ~(uintptr_t)255);
-  ps->desc = reinterpret_cast<PruneDesc*>(q);
-  ps->count = reinterpret_cast<int*>(q + 256);
-  ps->tau = reinterpret_cast<unsigned long long*>(q + 512);
-  ps->stats = reinterpret_cast<int64_t*>(q + 512 + 64);
-  q += 768;
-  for (int i = 0; i < 2; ++i) {
-    ps->list[i] = reinterpret_cast<int2*>(q);
-    q += (size_t)C * sizeof(int2);
-  }
-  for (int i = 0; i < 2; ++i) {
-    ps->ldc[i] = prune_ld(C, i);
-    ps->cbuf[i] = reinterpret_cast<double*>(q);
-    q += (size_t)npad * ps->ldc[i] * 8;
-  }
-}
-void sweep_prune_carve_head(const PruneState& ps, int64_t npad, int64_t C, int64_t MA, int64_t m, PruneHead* ph) {
-  char* q = reinterpret_cast<char*>(ps.cbuf[1] + (size_t)npad * ps.ldc[1]);
-  ph->super = MA;
-  ph->survivors = reinterpret_cast<int2*>(q);
-  q += (size_t)(MA + TT) * sizeof(int2);
-  ph->head = reinterpret_cast<double*>(q);
-  ph->mu_part = ph->head + (size_t)PRUNE_HEAD_ROWS * MA;
-  ph->ss_part = ph->mu_part + (size_t)(npad / NB) * MA;
-  ph->rec_val = ph->ss_part + (size_t)(npad / TT) * MA;
-  ph->rec_idx = reinterpret_cast<int64_t*>(ph->rec_val + sweep_lazy_records(npad, m));
-}
-
-// The top-k part of gpx_acquire_topk_f64's workspace, behind the sweep workspace: header (256 bytes), pool (k pairs),
-// scored list (a pair per candidate of a chunk: no launch scores more in full), then what the composed path needs: m
-// scores and gpx_topk_f64's workspace.  Every part rounded up to 256 bytes.
-static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-size_t topk_sweep_bytes(int64_t npad, int64_t m, int64_t k) {
-  const int64_t C = sweep_chunk_size(npad, m);
-  return 256 + 256 + 2 * up256((size_t)k * 8) + 2 * up256((size_t)C * 8) + up256((size_t)m * 8) +
-         topk_workspace_bytes(m);
-}
-void topk_sweep_carve(void* base, int64_t npad, int64_t m, int64_t k, TopkSweep* tk) {
-  const int64_t C = sweep_chunk_size(npad, m);
-  char* q = reinterpret_cast<char*>(((uintptr_t)base + 255) & ~(uintptr_t)255);
-  tk->k = (int)k;
-  tk->head = reinterpret_cast<int*>(q);
-  q += 256;
-  tk->pool_val = reinterpret_cast<double*>(q);
-  q += up256((size_t)k * 8);
-  tk->pool_idx = reinterpret_cast<int64_t*>(q);
-  q += up256((size_t)k * 8);
-  tk->list_val = reinterpret_cast<double*>(q);
-  q += up256((size_t)C * 8);
-  tk->list_idx = reinterpret_cast<int64_t*>(q);
-  q += up256((size_t)C * 8);
-  tk->scores = reinterpret_cast<double*>(q);
-  q += up256((size_t)m * 8);
-  tk->sort_ws = q;
-  tk->sort_bytes = topk_workspace_bytes(m);
-}
-
 // finalize_kernel mode 1's view of a scoring launch: the argmax form raises the incumbent itself, the top-k form feeds
 // the scored list and leaves the incumbent to topk_pool_kernel
 static PruneSel score_sel(PruneSel sel, const PruneState& ps, const TopkSweep* tk) {
@@ -2125,82 +2002,89 @@ bool sweep_prune_ok(const Context* c, const gpx_kernel_params& p, int npad) {
   return npad >= (c->sweep_prune != 1 ? PRUNE_MIN_NPAD : PRUNE_DEFAULT_NPAD);  // (-2: forced, exact head means)
 }
 
-// K* and the partial means of one chunk (launch 1 of the file comment)
-static void launch_kstar(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X, int64_t ldx,
-                         const double* alpha, int nrhs, const double* Xs, int64_t ldxs, int64_t m_chunk,
-                         const SweepBuffers& b, int mode = KSTAR_FULL, const KstarAux& aux = KstarAux{},
-                         int rows = 0) {
-  if (rows == 0) rows = npad;  // (KSTAR_FULL over the leading `rows` rows only: the head phase)
-  LaunchTimer tm(c, GPX_TIMER_KSTAR);
-  const int64_t C = b.chunk;
-  // (KSTAR_GATHER: m_chunk is the most columns the round can have; the kernel reads the count itself)
-  dim3 g((unsigned)((m_chunk + WG - 1) / WG), (mode == KSTAR_MU ? npad - PRUNE_HEAD_ROWS : rows) / NB);
-#define GPX_KSTAR_K(D, F, K)                                                                                     \
-  (nrhs == 1 ? kstar_kernel<D, F, K, true><<<g, WG, 0, c->stream>>>(p, n, X, ldx, alpha, nrhs, Xs, ldxs, m_chunk, C, \
-                                                                    b.kstar, b.mu_part)                            \
-             : kstar_kernel<D, F, K, false><<<g, WG, 0, c->stream>>>(p, n, X, ldx, alpha, nrhs, Xs, ldxs, m_chunk, \
-                                                                     C, b.kstar, b.mu_part))
-#define GPX_KSTAR_F(D, F)                                                                                          \
-  (p.kind == GPX_KERNEL_RBF        ? GPX_KSTAR_K(D, F, GPX_KERNEL_RBF)                                             \
-   : p.kind == GPX_KERNEL_MATERN52 ? GPX_KSTAR_K(D, F, GPX_KERNEL_MATERN52)                                        \
-                                   : GPX_KSTAR_K(D, F, GPX_KERNEL_SCALE_LINEAR_MATERN52))
-#define GPX_KSTAR_MM(D, K, R, M)                                                                                   \
-  kstar_mfma_kernel<D, K, R, M><<<g, WG, 0, c->stream>>>(p, n, X, ldx, alpha, nrhs, Xs, ldxs, m_chunk, C, b.kstar,    \
-                                                         b.mu_part, aux)
-#define GPX_KSTAR_M(D, K)                                                                                          \
-  (nrhs != 1               ? GPX_KSTAR_MM(D, K, false, KSTAR_FULL)                                                  \
-   : mode == KSTAR_FULL    ? GPX_KSTAR_MM(D, K, true, KSTAR_FULL)                                                   \
-   : mode == KSTAR_MU      ? GPX_KSTAR_MM(D, K, true, KSTAR_MU)                                                     \
-                           : GPX_KSTAR_MM(D, K, true, KSTAR_GATHER))
-#define GPX_KSTAR_MK(D)                                                                                            \
-  (p.kind == GPX_KERNEL_RBF        ? GPX_KSTAR_M(D, GPX_KERNEL_RBF)                                                \
-   : p.kind == GPX_KERNEL_MATERN52 ? GPX_KSTAR_M(D, GPX_KERNEL_MATERN52)                                           \
-                                   : GPX_KSTAR_M(D, GPX_KERNEL_SCALE_LINEAR_MATERN52))
-#define GPX_KSTAR(D) (p.cov_fp32 ? GPX_KSTAR_F(D, true) : GPX_KSTAR_MK(D))
-  if (p.d <= 4)
-    GPX_KSTAR(4);
-  else if (p.d <= 8)
-    GPX_KSTAR(8);
-  else if (p.d <= 16)
-    GPX_KSTAR(16);
-  else  // d > 16: the difference form (the MFMA kernel's candidate tile would not fit 64 KB of LDS)
-    p.cov_fp32 ? GPX_KSTAR_F(32, true) : GPX_KSTAR_F(32, false);
-#undef GPX_KSTAR_MK
-#undef GPX_KSTAR_M
-#undef GPX_KSTAR_MM
-#undef GPX_KSTAR
-#undef GPX_KSTAR_F
-#undef GPX_KSTAR_K
+// p.d and p.kind as template arguments: f gets DMAX (4, 8, 16 or 32) resp. the kernel kind as a std::integral_constant.
+// A combination without a kernel (the MFMA build and the fused sweep at DMAX = 32, ...) is left out by the callers with
+// `if constexpr`, so only the kernels they name are built.
+template <int V>
+using Const = std::integral_constant<int, V>;
+template <class F>
+static void with_dmax(int d, F&& f) {
+  d <= 4 ? f(Const<4>{}) : d <= 8 ? f(Const<8>{}) : d <= 16 ? f(Const<16>{}) : f(Const<32>{});
+}
+template <class F>
+static void with_kind(int kind, F&& f) {
+  kind == GPX_KERNEL_RBF        ? f(Const<GPX_KERNEL_RBF>{})
+  : kind == GPX_KERNEL_MATERN52 ? f(Const<GPX_KERNEL_MATERN52>{})
+                                : f(Const<GPX_KERNEL_SCALE_LINEAR_MATERN52>{});
 }
 
-// The head phase's mean bound of m_chunk candidates (mu_colsum_kernel, mu_rowstat_kernel and mu_prep_kernel, then
+// K* and the partial means of one chunk (launch 1 of the file comment)
+static void launch_kstar(const SweepModel& M, const SweepCands& q, const SweepBuffers& b, int mode = KSTAR_FULL,
+                         const KstarAux& aux = KstarAux{}, int rows = 0) {
+  if (rows == 0) rows = M.npad;  // (KSTAR_FULL over the leading `rows` rows only: the head phase)
+  LaunchTimer tm(M.c, GPX_TIMER_KSTAR);
+  const gpx_kernel_params& p = M.p;
+  const int64_t C = b.chunk;
+  hipStream_t stream = M.c->stream;
+  // (KSTAR_GATHER: q.m is the most columns the round can have; the kernel reads the count itself)
+  const dim3 g((unsigned)((q.m + WG - 1) / WG), (mode == KSTAR_MU ? M.npad - PRUNE_HEAD_ROWS : rows) / NB);
+  with_dmax(p.d, [&](auto D) {
+    constexpr int DM = decltype(D)::value;
+    auto diff = [&](auto F32) {  // the difference form
+      with_kind(p.kind, [&](auto K) {
+        auto rhs = [&](auto ONE) {
+          kstar_kernel<DM, decltype(F32)::value, decltype(K)::value, decltype(ONE)::value><<<g, WG, 0, stream>>>(
+              p, M.n, M.X, M.ldx, M.alpha, M.nrhs, q.Xs, q.ldxs, q.m, C, b.kstar, b.mu_part);
+        };
+        M.nrhs == 1 ? rhs(std::true_type{}) : rhs(std::false_type{});
+      });
+    };
+    if (p.cov_fp32) {
+      diff(std::true_type{});
+    } else if constexpr (DM == 32) {  // d > 16: the MFMA kernel's candidate tile would not fit 64 KB of LDS
+      diff(std::false_type{});
+    } else {
+      with_kind(p.kind, [&](auto K) {
+        auto mfma = [&](auto ONE, auto MODE) {
+          kstar_mfma_kernel<DM, decltype(K)::value, decltype(ONE)::value, decltype(MODE)::value>
+              <<<g, WG, 0, stream>>>(p, M.n, M.X, M.ldx, M.alpha, M.nrhs, q.Xs, q.ldxs, q.m, C, b.kstar, b.mu_part, aux);
+        };
+        M.nrhs != 1          ? mfma(std::false_type{}, Const<KSTAR_FULL>{})
+        : mode == KSTAR_FULL ? mfma(std::true_type{}, Const<KSTAR_FULL>{})
+        : mode == KSTAR_MU   ? mfma(std::true_type{}, Const<KSTAR_MU>{})
+                             : mfma(std::true_type{}, Const<KSTAR_GATHER>{});
+      });
+    }
+  });
+}
+
+// The head phase's mean bound of q.m candidates (mu_colsum_kernel, mu_rowstat_kernel and mu_prep_kernel, then
 // mu_fact32_kernel for the workgroups inside the fp32 form's limit (4 < d <= 8), mu_fact_kernel for the other eligible ones
 // and mu_bound_kernel for the rest); prep: mu_prep_doubles(npad, d) doubles of scratch.
 bool sweep_mu_bound_ok(const gpx_kernel_params& p) { return p.kind == GPX_KERNEL_RBF && !p.cov_fp32 && p.d <= 16; }
 
-hipError_t launch_mu_bound(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X, int64_t ldx,
-                           const double* alpha, const double* Xs, int64_t ldxs, int64_t m_chunk, double* prep,
-                           double* mu_approx, double* mu_slack) {
-  LaunchTimer tm(c, GPX_TIMER_KSTAR);
-  const unsigned nwg = (unsigned)((m_chunk + WG - 1) / WG);
-  // FIRST classifies every workgroup and, for 4 < d <= 8, computes those on the fp32 form; the two kernels behind it run the
-  // workgroups it flagged -2 and -1, the others returning at once.
-#define GPX_MU_BOUND(D, FIRST)                                                                            \
-  (mu_colsum_kernel<D><<<npad / NB, WG, 0, c->stream>>>(p, n, npad, X, ldx, prep),                         \
-   mu_rowstat_kernel<D><<<npad / NB, NB, 0, c->stream>>>(p, n, npad, X, ldx, alpha, prep),                 \
-   mu_prep_kernel<D><<<npad / NB, WG, 0, c->stream>>>(p, n, npad, X, ldx, alpha, prep), FIRST,             \
-   mu_fact_kernel<D><<<nwg, WG, 0, c->stream>>>(p, n, npad, prep, Xs, ldxs, m_chunk, mu_approx, mu_slack), \
-   mu_bound_kernel<D><<<nwg, WG, 0, c->stream>>>(p, n, prep, Xs, ldxs, m_chunk, mu_approx, mu_slack))
-#define GPX_MU_CLASS(D) mu_class_kernel<D><<<nwg, WG, 0, c->stream>>>(p, n, prep, Xs, ldxs, m_chunk, mu_slack)
-  if (p.d <= 4)
-    GPX_MU_BOUND(4, GPX_MU_CLASS(4));
-  else if (p.d <= 8)
-    GPX_MU_BOUND(8, (mu_fact32_kernel<8><<<nwg, WG, 0, c->stream>>>(p, n, npad, prep, Xs, ldxs, m_chunk, mu_approx,
-                                                                     mu_slack)));
-  else
-    GPX_MU_BOUND(16, GPX_MU_CLASS(16));
-#undef GPX_MU_CLASS
-#undef GPX_MU_BOUND
+hipError_t launch_mu_bound(const SweepModel& M, const SweepCands& q, double* prep, double* mu_approx, double* mu_slack) {
+  LaunchTimer tm(M.c, GPX_TIMER_KSTAR);
+  const gpx_kernel_params& p = M.p;
+  const int n = M.n, npad = M.npad;
+  hipStream_t stream = M.c->stream;
+  const unsigned nwg = (unsigned)((q.m + WG - 1) / WG);
+  with_dmax(p.d, [&](auto D) {
+    constexpr int DM = decltype(D)::value;
+    if constexpr (DM <= 16) {  // (sweep_mu_bound_ok)
+      mu_colsum_kernel<DM><<<npad / NB, WG, 0, stream>>>(p, n, npad, M.X, M.ldx, prep);
+      mu_rowstat_kernel<DM><<<npad / NB, NB, 0, stream>>>(p, n, npad, M.X, M.ldx, M.alpha, prep);
+      mu_prep_kernel<DM><<<npad / NB, WG, 0, stream>>>(p, n, npad, M.X, M.ldx, M.alpha, prep);
+      // the first kernel over the candidates classifies every workgroup and, for 4 < d <= 8, computes those on the fp32
+      // form; the two kernels behind it run the workgroups it flagged -2 and -1, the others returning at once
+      if constexpr (mu_fp32_form(DM))
+        mu_fact32_kernel<DM><<<nwg, WG, 0, stream>>>(p, n, npad, prep, q.Xs, q.ldxs, q.m, mu_approx, mu_slack);
+      else
+        mu_class_kernel<DM><<<nwg, WG, 0, stream>>>(p, n, prep, q.Xs, q.ldxs, q.m, mu_slack);
+      mu_fact_kernel<DM><<<nwg, WG, 0, stream>>>(p, n, npad, prep, q.Xs, q.ldxs, q.m, mu_approx, mu_slack);
+      mu_bound_kernel<DM><<<nwg, WG, 0, stream>>>(p, n, prep, q.Xs, q.ldxs, q.m, mu_approx, mu_slack);
+    }
+  });
   return hipGetLastError();
 }
 
@@ -2227,45 +2111,40 @@ static FinalizeArgs finalize_args(const gpx_kernel_params& p, const gpx_acq_para
   return fa;
 }
 
-hipError_t launch_sweep_chunk(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X, int64_t ldx,
-                              const double* W, int64_t ldw, const double* alpha, int nrhs, const double* Xs,
-                              int64_t ldxs, int64_t m_chunk, const SweepBuffers& b, int mode,
-                              const gpx_acq_params* a, const double* y_mean, const double* y_scale,
-                              double* mean_out, int64_t ldmean, double* var_out, double* scores_out,
-                              int64_t rec_offset, int64_t index_offset, const MultiOutput* mo) {
+hipError_t launch_sweep_chunk(const SweepModel& M, const SweepCands& q, const SweepBuffers& b, int mode,
+                              const gpx_acq_params* a, const SweepOut& out, int64_t rec_offset, const MultiOutput* mo) {
+  Context* c = M.c;
+  const gpx_kernel_params& p = M.p;
   const int64_t C = b.chunk;
-  int nJB = npad / NB, nI = npad / TT;
-  const int ncb = (int)((m_chunk + WG - 1) / WG);  // 256-candidate blocks actually used in this chunk
-  if (sweep_fused_ok(c, p, npad, nrhs)) {
+  int nJB = M.npad / NB, nI = M.npad / TT;
+  const int ncb = (int)((q.m + WG - 1) / WG);  // 256-candidate blocks actually used in this chunk
+  if (sweep_fused_ok(c, p, M.npad, M.nrhs)) {
     LaunchTimer tm(c, GPX_TIMER_TRMM);
-    const int nwg = (int)((m_chunk + 63) / 64);
-#define GPX_SMALL_K(NP, D, K)                                                                                       \
-  (nrhs == 1 ? sweep_small_kernel<NP, D, K, 1><<<nwg, WG, 0, c->stream>>>(p, n, X, ldx, alpha, nrhs, W, ldw, Xs, ldxs,  \
-                                                                           m_chunk, C, b.mu_part, b.ss_part)          \
-             : sweep_small_kernel<NP, D, K, GPX_MAX_RHS><<<nwg, WG, 0, c->stream>>>(                                  \
-                   p, n, X, ldx, alpha, nrhs, W, ldw, Xs, ldxs, m_chunk, C, b.mu_part, b.ss_part))
-#define GPX_SMALL_D(NP, D)                                                                                          \
-  (p.kind == GPX_KERNEL_RBF        ? GPX_SMALL_K(NP, D, GPX_KERNEL_RBF)                                             \
-   : p.kind == GPX_KERNEL_MATERN52 ? GPX_SMALL_K(NP, D, GPX_KERNEL_MATERN52)                                        \
-                                   : GPX_SMALL_K(NP, D, GPX_KERNEL_SCALE_LINEAR_MATERN52))
-#define GPX_SMALL(NP) (p.d <= 4 ? GPX_SMALL_D(NP, 4) : p.d <= 8 ? GPX_SMALL_D(NP, 8) : GPX_SMALL_D(NP, 16))
-    if (npad == 128)
-      GPX_SMALL(128);
-    else
-      GPX_SMALL(256);
-#undef GPX_SMALL
-#undef GPX_SMALL_D
-#undef GPX_SMALL_K
+    const int nwg = (int)((q.m + 63) / 64);
+    auto small = [&](auto NP, auto D, auto K, auto NR) {
+      sweep_small_kernel<decltype(NP)::value, decltype(D)::value, decltype(K)::value, decltype(NR)::value>
+          <<<nwg, WG, 0, c->stream>>>(p, M.n, M.X, M.ldx, M.alpha, M.nrhs, M.W, M.ldw, q.Xs, q.ldxs, q.m, C, b.mu_part,
+                                      b.ss_part);
+    };
+    auto rows = [&](auto NP) {
+      with_dmax(p.d, [&](auto D) {
+        if constexpr (decltype(D)::value <= 16)  // (sweep_fused_ok)
+          with_kind(p.kind, [&](auto K) {
+            M.nrhs == 1 ? small(NP, D, K, Const<1>{}) : small(NP, D, K, Const<GPX_MAX_RHS>{});
+          });
+      });
+    };
+    M.npad == 128 ? rows(Const<128>{}) : rows(Const<256>{});
     nJB = nI = 1;
   } else {
-    launch_kstar(c, p, n, npad, X, ldx, alpha, nrhs, Xs, ldxs, m_chunk, b);
+    launch_kstar(M, q, b);
     LaunchTimer tm(c, GPX_TIMER_TRMM);
-    const int ncbt = (int)((m_chunk + TT - 1) / TT);
-    trmm_sumsq_kernel<<<ncbt * nI, WG, 0, c->stream>>>(W, ldw, b.kstar, C, nI, ncbt, b.ss_part, 0);
+    const int ncbt = (int)((q.m + TT - 1) / TT);
+    trmm_sumsq_kernel<<<ncbt * nI, WG, 0, c->stream>>>(M.W, M.ldw, b.kstar, C, nI, ncbt, b.ss_part, 0);
   }
   {
     LaunchTimer tm(c, GPX_TIMER_ACQ);
-    FinalizeArgs fa = finalize_args(p, a, nrhs, y_mean, y_scale);
+    FinalizeArgs fa = finalize_args(p, a, M.nrhs, out.y_mean, out.y_scale);
     if (mo) {  // one output of a multi-output objective: accumulate, score later (launch_multi_score)
       mode = 2;
       fa.y_mean[0] = mo->y_mean;
@@ -2275,16 +2154,15 @@ hipError_t launch_sweep_chunk(Context* c, const gpx_kernel_params& p, int n, int
       fa.acc_mu = mo->acc_mu;
       fa.acc_var = mo->acc_var;
     }
-    finalize_kernel<<<ncb, WG, 0, c->stream>>>(fa, mode, Xs, ldxs, m_chunk, C, nrhs, nJB, nI, b.mu_part,
-                                                   b.ss_part, mean_out, ldmean, var_out, scores_out,
-                                                   b.rec_val + rec_offset, b.rec_idx + rec_offset,
-                                                   index_offset, PruneSel{});
+    finalize_kernel<<<ncb, WG, 0, c->stream>>>(fa, mode, q.Xs, q.ldxs, q.m, C, M.nrhs, nJB, nI, b.mu_part, b.ss_part,
+                                               out.mean, out.ldmean, out.var, out.scores, b.rec_val + rec_offset,
+                                               b.rec_idx + rec_offset, q.index_offset, PruneSel{});
   }
   return hipGetLastError();
 }
 
-hipError_t launch_multi_score(Context* c, const MultiOutput& mo, const gpx_acq_params& a, int64_t m_chunk,
-                              double* scores_out, double* rec_val, int64_t* rec_idx, int64_t index_offset) {
+hipError_t launch_multi_score(Context* c, const SweepCands& q, const MultiOutput& mo, const gpx_acq_params& a,
+                              double* scores_out, double* rec_val, int64_t* rec_idx) {
   LaunchTimer tm(c, GPX_TIMER_ACQ);
   FinalizeArgs fa{};
   fa.acq_kind = a.kind;
@@ -2292,9 +2170,9 @@ hipError_t launch_multi_score(Context* c, const MultiOutput& mo, const gpx_acq_p
   fa.beta = a.beta;
   fa.acc_mu = mo.acc_mu;
   fa.acc_var = mo.acc_var;
-  const int ncb = (int)((m_chunk + WG - 1) / WG);
-  finalize_kernel<<<ncb, WG, 0, c->stream>>>(fa, 3, nullptr, 0, m_chunk, 0, 1, 0, 0, nullptr, nullptr, nullptr, 0,
-                                             nullptr, scores_out, rec_val, rec_idx, index_offset, PruneSel{});
+  const int ncb = (int)((q.m + WG - 1) / WG);
+  finalize_kernel<<<ncb, WG, 0, c->stream>>>(fa, 3, nullptr, 0, q.m, 0, 1, 0, 0, nullptr, nullptr, nullptr, 0, nullptr,
+                                             scores_out, rec_val, rec_idx, q.index_offset, PruneSel{});
   return hipGetLastError();
 }
 
@@ -2332,87 +2210,134 @@ static void launch_tail_stage(Context* c, const double* W, int64_t ldw, int64_t 
   trmm_stage_dual_kernel<<<(unsigned)(wide > narrow ? wide : narrow), WG, 0, c->stream>>>(W, ldw, C, nI, ss_part, st);
 }
 
-hipError_t launch_sweep_chunk_pruned(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X,
-                                     int64_t ldx, const double* W, int64_t ldw, const double* alpha, const double* Xs,
-                                     int64_t ldxs, int64_t m_chunk, const SweepBuffers& b, const PruneState& ps,
-                                     const gpx_acq_params* a, int64_t rec_offset, int64_t index_offset, bool first,
-                                     int64_t* host_stats, const TopkSweep* tk) {
+// ---- the staged driver: what the chunked and the lazy form of the pruned sweep share --------------------------------
+// The columns of a chunk or super-chunk of m candidates: the seed block (the call's first incumbent: its leading
+// PRUNE_SEED candidates through the full product and finalize; later candidates start from the best score of
+// everything scored before them), and the staged columns behind it.
+struct SeedPlan {
+  int seed, seed_blocks;  // candidates of the seed block (0: not the call's first), their 256-candidate blocks
+  int col0, ncols;        // the staged columns: from the tile behind the seed block on (a short chunk: none)
+};
+static SeedPlan seed_plan(bool first, int64_t m, int64_t C) {
+  SeedPlan sp;
+  sp.seed = first ? (int)(m < PRUNE_SEED ? m : PRUNE_SEED) : 0;
+  if (sp.seed > C) sp.seed = (int)C;
+  sp.seed_blocks = (sp.seed + WG - 1) / WG;
+  sp.col0 = ((sp.seed + TT - 1) / TT) * TT;
+  sp.ncols = m > sp.col0 ? (int)(m - sp.col0) : 0;
+  return sp;
+}
+
+static PruneBufs prune_bufs(const double* kstar, int64_t ld0, const PruneState& ps, const int2* list2 = nullptr) {
+  return PruneBufs{kstar, ps.cbuf[0], ps.cbuf[1], ld0, ps.ldc[0], ps.ldc[1], ps.list[0], ps.list[1], list2};
+}
+
+// prune_init_kernel, then the seed block where the plan has one: K* of its columns (build_kstar: the lazy form; the
+// chunked form built the whole chunk's before), the full product in narrow tiles, finalize mode 1, pool.
+static void launch_seed_block(const SweepModel& M, const SweepCands& q, const SweepBuffers& b, const PruneState& ps,
+                              const FinalizeArgs& fa, const SeedPlan& sp, int R1, bool one_stage, bool first,
+                              bool build_kstar, double* rec_val, int64_t* rec_idx, int64_t* host_stats,
+                              const TopkSweep* tk) {
+  Context* c = M.c;
   const int64_t C = b.chunk;
-  const int nJB = npad / NB, nI = npad / TT;
-  int R[PRUNE_MAX_STAGES];
-  const int S = prune_stage_bounds(nI, R);
-  launch_kstar(c, p, n, npad, X, ldx, alpha, 1, Xs, ldxs, m_chunk, b);
-  const FinalizeArgs fa = finalize_args(p, a, 1, nullptr, nullptr);
-  // The call's first incumbent: its leading PRUNE_SEED candidates through the full product and finalize (a chunk's
-  // later candidates start from the best score of everything scored before them).
-  const int seed = first ? (int)(m_chunk < PRUNE_SEED ? m_chunk : PRUNE_SEED) : 0;
-  const int seed_blocks = (seed + WG - 1) / WG;
-  const int col0 = ((seed + TT - 1) / TT) * TT;  // seed < PRUNE_SEED: the whole chunk, no staged columns
-  const int ncols = m_chunk > seed ? (int)(m_chunk - col0) : 0;
-  const int tiles = (ncols + TT - 1) / TT, blocks = (ncols + WG - 1) / WG;
-  PruneBufs pb;
-  pb.kstar = b.kstar;
-  pb.c1 = ps.cbuf[0];
-  pb.c2 = ps.cbuf[1];
-  pb.ld0 = C;
-  pb.ld1 = ps.ldc[0];
-  pb.ld2 = ps.ldc[1];
-  pb.list0 = ps.list[0];
-  pb.list1 = ps.list[1];
-  pb.list2 = nullptr;
+  const int nJB = M.npad / NB, nI = M.npad / TT;
+  auto product = [&] {
+    const int ncbt = (sp.seed + TT - 1) / TT;
+    trmm_sumsq_narrow_kernel<<<4 * ncbt * nI, WG, 0, c->stream>>>(M.W, M.ldw, b.kstar, C, nI, ncbt, b.ss_part);
+    host_stats[1] += sp.seed;
+    host_stats[2] += (int64_t)ncbt * nI;
+  };
   {
     LaunchTimer tm(c, GPX_TIMER_TRMM);
-    prune_init_kernel<<<1, 64, 0, c->stream>>>(ps.desc, ps.count, ps.tau, ps.stats, col0, ncols, R[1], S == 1, first,
-                                               tk ? tk->head : nullptr);
-    if (seed) {
-      const int ncbt = (seed + TT - 1) / TT;
-      trmm_sumsq_narrow_kernel<<<4 * ncbt * nI, WG, 0, c->stream>>>(W, ldw, b.kstar, C, nI, ncbt, b.ss_part);
-      host_stats[1] += seed;
-      host_stats[2] += (int64_t)ncbt * nI;
-    }
+    prune_init_kernel<<<1, 64, 0, c->stream>>>(ps.desc, ps.count, ps.tau, ps.stats, sp.col0, sp.ncols, R1, one_stage,
+                                               first, tk ? tk->head : nullptr);
+    if (sp.seed && !build_kstar) product();
   }
-  if (seed) {
-    LaunchTimer tm(c, GPX_TIMER_ACQ);
-    finalize_kernel<<<seed_blocks, WG, 0, c->stream>>>(fa, 1, Xs, ldxs, seed, C, 1, nJB, nI, b.mu_part, b.ss_part,
-                                                       nullptr, 0, nullptr, nullptr, b.rec_val + rec_offset,
-                                                       b.rec_idx + rec_offset, index_offset,
-                                                       score_sel(PruneSel{}, ps, tk));
-    launch_topk_pool(c, ps, tk, C);
+  if (!sp.seed) return;
+  if (build_kstar) {
+    launch_kstar(M, q.first(sp.seed), b);
+    LaunchTimer tm(c, GPX_TIMER_TRMM);
+    product();
   }
-  if (ncols == 0) return hipGetLastError();
+  LaunchTimer tm(c, GPX_TIMER_ACQ);
+  finalize_kernel<<<sp.seed_blocks, WG, 0, c->stream>>>(fa, 1, q.Xs, q.ldxs, sp.seed, C, 1, nJB, nI, b.mu_part,
+                                                        b.ss_part, nullptr, 0, nullptr, nullptr, rec_val, rec_idx,
+                                                        q.index_offset, score_sel(PruneSel{}, ps, tk));
+  launch_topk_pool(c, ps, tk, C);
+}
+
+// The staged product of one column set: per stage s the row tiles R[s] .. R[s+1] - 1 of the active columns, after every
+// stage but the last the bound pass (finalize mode 4) and the compaction; then finalize mode 1 over what is left, pool.
+struct StagePlan {
+  PruneBufs pb;          // the K* source and its pitch, the compact buffers, the index lists
+  double* mu_part;       // the partial arrays of the columns' own places, and their pitch
+  double* ss_part;
+  int64_t pitch;
+  const int* R;          // stage bounds R[0] < .. < R[ns] = nI
+  int ns;
+  int desc0;             // descriptor and count of stage 0 (ps.desc + desc0, ps.count + desc0)
+  bool wide_first;       // stage 0 is one launch of the wide trmm_stage_kernel; else it goes through launch_tail_stage
+  int cap;               // the most columns the set can have
+  double* rec_val;       // the record cursor
+  int64_t* rec_idx;
+};
+static void launch_stages(const SweepModel& M, const SweepCands& q, const PruneState& ps, const FinalizeArgs& fa,
+                          const StagePlan& sg, int64_t C, const TopkSweep* tk) {
+  Context* c = M.c;
+  const int nJB = M.npad / NB, nI = M.npad / TT;
+  const int tiles = (sg.cap + TT - 1) / TT, blocks = (sg.cap + WG - 1) / WG;
+  PruneDesc* desc = ps.desc + sg.desc0;
+  int* count = ps.count + sg.desc0;
   PruneSel sel{};
   sel.list0 = ps.list[0];
   sel.list1 = ps.list[1];
+  sel.list2 = sg.pb.list2;
   sel.tau = ps.tau;
   {
     LaunchTimer tm(c, GPX_TIMER_TRMM);
     constexpr int ROWS = 32;  // K* rows a compaction workgroup copies
-    const dim3 gc((ncols / 2 + TT + WG - 1) / WG, npad / ROWS);
-    for (int s = 0; s < S; ++s) {
-      const PruneStage st{pb, ps.desc + s, R[s], R[s + 1] - R[s], 0};
-      if (s == 0)
-        trmm_stage_kernel<<<tiles * st.nrows, WG, 0, c->stream>>>(W, ldw, C, nI, b.ss_part, st);
+    const dim3 gc((sg.cap / 2 + TT + WG - 1) / WG, M.npad / ROWS);
+    for (int s = 0; s < sg.ns; ++s) {
+      const PruneStage st{sg.pb, desc + s, sg.R[s], sg.R[s + 1] - sg.R[s], 0};
+      if (s == 0 && sg.wide_first)
+        trmm_stage_kernel<<<tiles * st.nrows, WG, 0, c->stream>>>(M.W, M.ldw, sg.pitch, nI, sg.ss_part, st);
       else
-        launch_tail_stage(c, W, ldw, C, nI, b.ss_part, st, tiles);
-      if (s == S - 1) break;
-      sel.desc = ps.desc + s;
-      sel.count = ps.count + s;
-      finalize_kernel<<<blocks, WG, 0, c->stream>>>(fa, 4, Xs, ldxs, m_chunk, C, 1, nJB, R[s + 1], b.mu_part,
-                                                    b.ss_part, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
-                                                    index_offset, sel);
-      prune_compact_kernel<<<gc, WG, 0, c->stream>>>(pb, ps.desc + s, ps.desc + s + 1, ps.count + s, ROWS,
-                                                     R[s + 2] - R[s + 1], s + 2 == S, ps.stats);
+        launch_tail_stage(c, M.W, M.ldw, sg.pitch, nI, sg.ss_part, st, tiles);
+      if (s == sg.ns - 1) break;
+      sel.desc = desc + s;
+      sel.count = count + s;
+      finalize_kernel<<<blocks, WG, 0, c->stream>>>(fa, 4, q.Xs, q.ldxs, q.m, sg.pitch, 1, nJB, sg.R[s + 1], sg.mu_part,
+                                                    sg.ss_part, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
+                                                    q.index_offset, sel);
+      prune_compact_kernel<<<gc, WG, 0, c->stream>>>(sg.pb, desc + s, desc + s + 1, count + s, ROWS,
+                                                     sg.R[s + 2] - sg.R[s + 1], s + 2 == sg.ns, ps.stats);
     }
   }
-  {
-    LaunchTimer tm(c, GPX_TIMER_ACQ);
-    sel.desc = ps.desc + S - 1;
-    finalize_kernel<<<blocks, WG, 0, c->stream>>>(fa, 1, Xs, ldxs, m_chunk, C, 1, nJB, nI, b.mu_part, b.ss_part,
-                                                  nullptr, 0, nullptr, nullptr, b.rec_val + rec_offset + seed_blocks,
-                                                  b.rec_idx + rec_offset + seed_blocks, index_offset,
-                                                  score_sel(sel, ps, tk));
-    launch_topk_pool(c, ps, tk, C);
-  }
+  LaunchTimer tm(c, GPX_TIMER_ACQ);
+  sel.desc = desc + sg.ns - 1;
+  finalize_kernel<<<blocks, WG, 0, c->stream>>>(fa, 1, q.Xs, q.ldxs, q.m, sg.pitch, 1, nJB, nI, sg.mu_part, sg.ss_part,
+                                                nullptr, 0, nullptr, nullptr, sg.rec_val, sg.rec_idx, q.index_offset,
+                                                score_sel(sel, ps, tk));
+  launch_topk_pool(c, ps, tk, C);
+}
+
+hipError_t launch_sweep_chunk_pruned(const SweepModel& M, const SweepCands& q, const SweepBuffers& b,
+                                     const PruneState& ps, const gpx_acq_params* a, int64_t rec_offset, bool first,
+                                     int64_t* host_stats, const TopkSweep* tk) {
+  const int64_t C = b.chunk;
+  int R[PRUNE_MAX_STAGES];
+  const int S = prune_stage_bounds(M.npad / TT, R);
+  launch_kstar(M, q, b);
+  const FinalizeArgs fa = finalize_args(M.p, a, 1, nullptr, nullptr);
+  const SeedPlan sp = seed_plan(first, q.m, C);  // (a seed block short of PRUNE_SEED: the whole chunk, no staged columns)
+  double* rec_val = b.rec_val + rec_offset;
+  int64_t* rec_idx = b.rec_idx + rec_offset;
+  launch_seed_block(M, q, b, ps, fa, sp, R[1], S == 1, first, false, rec_val, rec_idx, host_stats, tk);
+  if (sp.ncols == 0) return hipGetLastError();
+  launch_stages(M, q, ps, fa,
+                StagePlan{prune_bufs(b.kstar, C, ps), b.mu_part, b.ss_part, C, R, S, 0, true, sp.ncols,
+                          rec_val + sp.seed_blocks, rec_idx + sp.seed_blocks},
+                C, tk);
   return hipGetLastError();
 }
 
@@ -2424,109 +2349,67 @@ hipError_t launch_sweep_chunk_pruned(Context* c, const gpx_kernel_params& p, int
 //         row blocks (every mean partial); the first stage of the product and its bound pass as one launch each; the
 //         survivors land in ph.survivors.
 //  tail   rounds of at most C survivors: KSTAR_GATHER rebuilds their full-height columns into the chunk buffer (the bits
-//         of the full build) and, after a mean bound, their exact mean partials into ph.mu_part, then the staged pipeline of launch_sweep_chunk_pruned from row tile 1 on, the partials
+//         of the full build) and, after a mean bound, their exact mean partials into ph.mu_part, then the staged pipeline
+//         of launch_sweep_chunk_pruned (launch_stages) from row tile 1 on, the partials
 //         going to the columns' own places in ph.ss_part.  The host cannot know the survivor count, so the worst-case
 //         number of rounds is enqueued and the workgroups of an empty round return at once; the rounds after the first
 //         therefore take fewer, coarser stages (the stage grouping does not change a column's partials).
 // *recs: records used so far (in ph.rec_val / ph.rec_idx).
 bool sweep_lazy_ok(const gpx_kernel_params& p) { return !p.cov_fp32 && p.d <= 16; }
 
-hipError_t launch_sweep_super_pruned(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X,
-                                     int64_t ldx, const double* W, int64_t ldw, const double* alpha, const double* Xs,
-                                     int64_t ldxs, int64_t m_super, const SweepBuffers& b, const PruneState& ps,
-                                     const PruneHead& ph, const gpx_acq_params* a, int64_t* recs, int64_t index_offset,
+hipError_t launch_sweep_super_pruned(const SweepModel& M, const SweepCands& q, const SweepBuffers& b,
+                                     const PruneState& ps, const PruneHead& ph, const gpx_acq_params* a, int64_t* recs,
                                      bool first, int64_t* host_stats, const TopkSweep* tk) {
-  const bool mu_bound = c->sweep_prune != -2 && sweep_mu_bound_ok(p);
+  Context* c = M.c;
+  const bool mu_bound = c->sweep_prune != -2 && sweep_mu_bound_ok(M.p);
   const int64_t C = b.chunk, MA = ph.super;
-  const int nJB = npad / NB, nI = npad / TT;
+  const int nJB = M.npad / NB, nI = M.npad / TT;
   int R[PRUNE_MAX_STAGES];
   const int S = prune_stage_bounds(nI, R);  // (nI >= 3: S >= 3, R[1] = 1 = the head's row tile)
   static_assert(PRUNE_HEAD_ROWS == TT, "the head phase is the product's first row tile");
-  const FinalizeArgs fa = finalize_args(p, a, 1, nullptr, nullptr);
-  int seed = first ? (int)(m_super < PRUNE_SEED ? m_super : PRUNE_SEED) : 0;
-  if (seed > C) seed = (int)C;
-  const int seed_blocks = (seed + WG - 1) / WG;
-  const int col0 = ((seed + TT - 1) / TT) * TT;
-  const int ncols = m_super > col0 ? (int)(m_super - col0) : 0;
-  const int tiles = (ncols + TT - 1) / TT, blocks = (ncols + WG - 1) / WG;
-  {
-    LaunchTimer tm(c, GPX_TIMER_TRMM);
-    prune_init_kernel<<<1, 64, 0, c->stream>>>(ps.desc, ps.count, ps.tau, ps.stats, col0, ncols, R[1], 0, first,
-                                               tk ? tk->head : nullptr);
-  }
-  if (seed) {
-    launch_kstar(c, p, n, npad, X, ldx, alpha, 1, Xs, ldxs, seed, b);
-    {
-      LaunchTimer tm(c, GPX_TIMER_TRMM);
-      const int ncbt = (seed + TT - 1) / TT;
-      trmm_sumsq_narrow_kernel<<<4 * ncbt * nI, WG, 0, c->stream>>>(W, ldw, b.kstar, C, nI, ncbt, b.ss_part);
-      host_stats[1] += seed;
-      host_stats[2] += (int64_t)ncbt * nI;
-    }
-    LaunchTimer tm(c, GPX_TIMER_ACQ);
-    finalize_kernel<<<seed_blocks, WG, 0, c->stream>>>(fa, 1, Xs, ldxs, seed, C, 1, nJB, nI, b.mu_part, b.ss_part,
-                                                       nullptr, 0, nullptr, nullptr, ph.rec_val + *recs,
-                                                       ph.rec_idx + *recs, index_offset,
-                                                       score_sel(PruneSel{}, ps, tk));
-    launch_topk_pool(c, ps, tk, C);
-    *recs += seed_blocks;
-  }
-  if (ncols == 0) return hipGetLastError();
+  const FinalizeArgs fa = finalize_args(M.p, a, 1, nullptr, nullptr);
+  const SeedPlan sp = seed_plan(first, q.m, C);
+  launch_seed_block(M, q, b, ps, fa, sp, R[1], false, first, true, ph.rec_val + *recs, ph.rec_idx + *recs, host_stats,
+                    tk);
+  *recs += sp.seed_blocks;
+  if (sp.ncols == 0) return hipGetLastError();
   // head: the columns of the whole super-chunk (the seed block's again: the head kernel has no column offset)
   {
     SweepBuffers hb = b;
     hb.kstar = ph.head;
     hb.mu_part = ph.mu_part;
     hb.chunk = MA;
-    KstarAux aux{};
-    aux.jb0 = PRUNE_HEAD_ROWS / NB;
-    launch_kstar(c, p, n, npad, X, ldx, alpha, 1, Xs, ldxs, m_super, hb, KSTAR_FULL, KstarAux{}, PRUNE_HEAD_ROWS);
+    launch_kstar(M, q, hb, KSTAR_FULL, KstarAux{}, PRUNE_HEAD_ROWS);
     if (mu_bound) {
       // the mean's bound instead of the mean.  Its two values per candidate go to the mean partials' rows of blocks 2
       // and 3 (the head rows' launch wrote blocks 0 and 1; nothing writes the others before the gather), the row
-      // blocks' records to the chunk's K* buffer, idle between the seed block's scoring and the first gather
-      // (mu_prep_doubles <= 38 npad + 32 doubles: 35.1 per row at DMAX = 16, 23.4 at DMAX = 8 with the fp32 form's
-      // records; the buffer holds npad x C >= 256 npad).
+      // blocks' records to ph.prep (the layout's view of the chunk's K* buffer, idle between the seed block's scoring
+      // and the first gather).
       static_assert(PRUNE_MIN_NPAD / NB >= 4, "mean partial rows 2 and 3 exist");
-      (void)launch_mu_bound(c, p, n, npad, X, ldx, alpha, Xs, ldxs, m_super, b.kstar, ph.mu_part + 2 * MA,
-                            ph.mu_part + 3 * MA);  // (the launch error is read at the end)
+      (void)launch_mu_bound(M, q, ph.prep, ph.mu_part + 2 * MA, ph.mu_part + 3 * MA);  // (the error is read at the end)
     } else {
-      launch_kstar(c, p, n, npad, X, ldx, alpha, 1, Xs, ldxs, m_super, hb, KSTAR_MU, aux);
+      KstarAux aux{};
+      aux.jb0 = PRUNE_HEAD_ROWS / NB;
+      launch_kstar(M, q, hb, KSTAR_MU, aux);
     }
   }
-  PruneBufs pb;
-  pb.kstar = ph.head;
-  pb.c1 = ps.cbuf[0];
-  pb.c2 = ps.cbuf[1];
-  pb.ld0 = MA;
-  pb.ld1 = ps.ldc[0];
-  pb.ld2 = ps.ldc[1];
-  pb.list0 = ps.list[0];
-  pb.list1 = ps.list[1];
-  pb.list2 = nullptr;
-  PruneSel sel{};
-  sel.tau = ps.tau;
   {
     LaunchTimer tm(c, GPX_TIMER_TRMM);
-    const PruneStage st{pb, ps.desc, 0, R[1], 0};
-    trmm_stage_kernel<<<tiles * st.nrows, WG, 0, c->stream>>>(W, ldw, MA, nI, ph.ss_part, st);
+    const PruneStage st{prune_bufs(ph.head, MA, ps), ps.desc, 0, R[1], 0};
+    trmm_stage_kernel<<<(sp.ncols + TT - 1) / TT * st.nrows, WG, 0, c->stream>>>(M.W, M.ldw, MA, nI, ph.ss_part, st);
+    PruneSel sel{};
+    sel.tau = ps.tau;
     sel.desc = ps.desc;
     sel.count = ps.count;
     sel.list0 = ph.survivors;  // (the descriptor's list is -1: the survivors go to list0)
-    sel.list1 = nullptr;
     sel.mu_bound = mu_bound ? ph.mu_part + 2 * MA : nullptr;
-    finalize_kernel<<<blocks, WG, 0, c->stream>>>(fa, 4, Xs, ldxs, m_super, MA, 1, nJB, R[1], ph.mu_part, ph.ss_part,
-                                                  nullptr, 0, nullptr, nullptr, nullptr, nullptr, index_offset, sel);
-    sel.mu_bound = nullptr;  // (the tail's passes read the survivors' exact partials, written by their gather)
+    finalize_kernel<<<(sp.ncols + WG - 1) / WG, WG, 0, c->stream>>>(fa, 4, q.Xs, q.ldxs, q.m, MA, 1, nJB, R[1],
+                                                                    ph.mu_part, ph.ss_part, nullptr, 0, nullptr, nullptr,
+                                                                    nullptr, nullptr, q.index_offset, sel);
   }
-  // tail
-  pb.kstar = b.kstar;
-  pb.ld0 = C;
-  sel.list0 = ps.list[0];
-  sel.list1 = ps.list[1];
-  constexpr int ROWS = 32;  // K* rows a compaction workgroup copies
-  for (int64_t r0 = 0; r0 < ncols; r0 += C) {
-    const int cap = (int)(ncols - r0 < C ? ncols - r0 : C);  // the most columns this round can have
+  // tail (its passes read the survivors' exact partials, written by their gather)
+  for (int64_t r0 = 0; r0 < sp.ncols; r0 += C) {
+    const int cap = (int)(sp.ncols - r0 < C ? sp.ncols - r0 : C);  // the most columns this round can have
     // stage boundaries Rr[0] = 1 < .. < Rr[ns] = nI: round 0 the doubling ones, later rounds 1 < 4 < nI
     int Rr[PRUNE_MAX_STAGES], ns = 0;
     if (r0 == 0) {
@@ -2551,32 +2434,12 @@ hipError_t launch_sweep_super_pruned(Context* c, const gpx_kernel_params& p, int
     aux.last = ns == 1;
     aux.mu_out = mu_bound ? ph.mu_part : nullptr;
     aux.ldmu = MA;
-    launch_kstar(c, p, n, npad, X, ldx, alpha, 1, Xs, ldxs, cap, b, KSTAR_GATHER, aux);
-    pb.list2 = sel.list2 = ph.survivors + r0;
-    const int rtiles = (cap + TT - 1) / TT, rblocks = (cap + WG - 1) / WG;
-    {
-      LaunchTimer tm(c, GPX_TIMER_TRMM);
-      const dim3 gc((cap / 2 + TT + WG - 1) / WG, npad / ROWS);
-      for (int s = 0; s < ns; ++s) {
-        const PruneStage st{pb, ps.desc + 1 + s, Rr[s], Rr[s + 1] - Rr[s], 0};
-        launch_tail_stage(c, W, ldw, MA, nI, ph.ss_part, st, rtiles);
-        if (s == ns - 1) break;
-        sel.desc = ps.desc + 1 + s;
-        sel.count = ps.count + 1 + s;
-        finalize_kernel<<<rblocks, WG, 0, c->stream>>>(fa, 4, Xs, ldxs, m_super, MA, 1, nJB, Rr[s + 1], ph.mu_part,
-                                                       ph.ss_part, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
-                                                       index_offset, sel);
-        prune_compact_kernel<<<gc, WG, 0, c->stream>>>(pb, ps.desc + 1 + s, ps.desc + 2 + s, ps.count + 1 + s, ROWS,
-                                                       Rr[s + 2] - Rr[s + 1], s + 2 == ns, ps.stats);
-      }
-    }
-    LaunchTimer tm(c, GPX_TIMER_ACQ);
-    sel.desc = ps.desc + ns;
-    finalize_kernel<<<rblocks, WG, 0, c->stream>>>(fa, 1, Xs, ldxs, m_super, MA, 1, nJB, nI, ph.mu_part, ph.ss_part,
-                                                   nullptr, 0, nullptr, nullptr, ph.rec_val + *recs,
-                                                   ph.rec_idx + *recs, index_offset, score_sel(sel, ps, tk));
-    launch_topk_pool(c, ps, tk, C);
-    *recs += rblocks;
+    launch_kstar(M, q.first(cap), b, KSTAR_GATHER, aux);
+    launch_stages(M, q, ps, fa,
+                  StagePlan{prune_bufs(b.kstar, C, ps, ph.survivors + r0), ph.mu_part, ph.ss_part, MA, Rr, ns, 1, false,
+                            cap, ph.rec_val + *recs, ph.rec_idx + *recs},
+                  C, tk);
+    *recs += (cap + WG - 1) / WG;
   }
   return hipGetLastError();
 }
@@ -2620,40 +2483,33 @@ hipError_t launch_debug_stage_product(Context* c, int npad, const double* W, int
   return hipGetLastError();
 }
 
-hipError_t launch_debug_kstar(Context* c, const gpx_kernel_params& p, int n, int npad, const double* X, int64_t ldx,
-                              const double* Xs, int64_t ldxs, int64_t m, const int* list, const int* count,
-                              double* out, int64_t ldout, double* mu_scratch, const double* alpha_in,
-                              double* mu_part, int64_t ldmu) {
+hipError_t launch_debug_kstar(const SweepModel& M, const SweepCands& q, const int* list, const int* count, double* out,
+                              int64_t ldout, double* mu_scratch, double* mu_part, int64_t ldmu) {
   SweepBuffers b{};
   b.kstar = out;
   b.chunk = ldout;
   b.mu_part = mu_scratch;  // (npad/64) x ldout mean partials of a zero alpha, then the zero alpha
-  if (!list && alpha_in) {  // the full build's own mean partials (pitch ldout)
+  if (!list && M.alpha) {  // the full build's own mean partials (pitch ldout)
     b.mu_part = mu_part;
-    launch_kstar(c, p, n, npad, X, ldx, alpha_in, 1, Xs, ldxs, m, b);
+    launch_kstar(M, q, b);
   } else if (!list) {
-    double* alpha = mu_scratch + (size_t)(npad / NB) * ldout;
-    hipError_t e = hipMemsetAsync(alpha, 0, (size_t)npad * 8, c->stream);
+    double* alpha = mu_scratch + (size_t)(M.npad / NB) * ldout;
+    hipError_t e = hipMemsetAsync(alpha, 0, (size_t)M.npad * 8, M.c->stream);
     if (e != hipSuccess) return e;
-    launch_kstar(c, p, n, npad, X, ldx, alpha, 1, Xs, ldxs, m, b);
-  } else if (alpha_in) {  // the gather build scatters the listed candidates' partials to mu_part[jb * ldmu + list[s]]
+    launch_kstar(SweepModel{M.c, M.p, M.n, M.npad, M.X, M.ldx, nullptr, 0, alpha, 1}, q, b);
+  } else {  // the gather build (no mean: alpha unread; else it scatters the listed candidates' partials to
+            // mu_part[jb * ldmu + list[s]])
     KstarAux aux{};
     aux.list = list;
     aux.lstride = 1;
     aux.count = count;
     aux.first = 0;
-    aux.cap = (int)m;
-    aux.mu_out = mu_part;
-    aux.ldmu = ldmu;
-    launch_kstar(c, p, n, npad, X, ldx, alpha_in, 1, Xs, ldxs, m, b, KSTAR_GATHER, aux);
-  } else {
-    KstarAux aux{};
-    aux.list = list;
-    aux.lstride = 1;
-    aux.count = count;
-    aux.first = 0;
-    aux.cap = (int)m;
-    launch_kstar(c, p, n, npad, X, ldx, nullptr, 1, Xs, ldxs, m, b, KSTAR_GATHER, aux);  // (no mean: alpha unread)
+    aux.cap = (int)q.m;
+    if (M.alpha) {
+      aux.mu_out = mu_part;
+      aux.ldmu = ldmu;
+    }
+    launch_kstar(M, q, b, KSTAR_GATHER, aux);
   }
   return hipGetLastError();
 }
@@ -2702,22 +2558,12 @@ hipError_t launch_svgp_chunk(Context* c, const gpx_kernel_params& p, double min_
   {
     LaunchTimer tm(c, GPX_TIMER_KSTAR);
     dim3 g(ncb, nJB);
-#define GPX_KSTAR_K(D, K) \
-  kstar_kernel<D, false, K, true><<<g, WG, 0, c->stream>>>(p, M, Z, ldz, alpha, 1, Xs, ldxs, m_chunk, C, b.kstar, b.mu_part)
-#define GPX_KSTAR(D)                                                                         \
-  (p.kind == GPX_KERNEL_RBF        ? GPX_KSTAR_K(D, GPX_KERNEL_RBF)                          \
-   : p.kind == GPX_KERNEL_MATERN52 ? GPX_KSTAR_K(D, GPX_KERNEL_MATERN52)                     \
-                                   : GPX_KSTAR_K(D, GPX_KERNEL_SCALE_LINEAR_MATERN52))
-    if (p.d <= 4)
-      GPX_KSTAR(4);
-    else if (p.d <= 8)
-      GPX_KSTAR(8);
-    else if (p.d <= 16)
-      GPX_KSTAR(16);
-    else
-      GPX_KSTAR(32);
-#undef GPX_KSTAR
-#undef GPX_KSTAR_K
+    with_dmax(p.d, [&](auto D) {
+      with_kind(p.kind, [&](auto K) {
+        kstar_kernel<decltype(D)::value, false, decltype(K)::value, true><<<g, WG, 0, c->stream>>>(
+            p, M, Z, ldz, alpha, 1, Xs, ldxs, m_chunk, C, b.kstar, b.mu_part);
+      });
+    });
   }
   {
     LaunchTimer tm(c, GPX_TIMER_TRMM);

@@ -266,6 +266,53 @@ def test_workspace_of_exactly_the_reported_size(engine):
     assert (int(bv.view(torch.int64).item()), int(bi.item())) == want[:2]
 
 
+@pytest.mark.parametrize("offset", [0, 8])
+@pytest.mark.parametrize("call", ["topk", "multi", "posterior", "posterior_fused"])
+def test_workspace_of_exactly_the_reported_size_every_sweep_call(engine, monkeypatch, call, offset):
+    """(h) for the other calls that carve the sweep's layout: gpx_acquire_topk_f64 (k = 5), gpx_acquire_argmax_multi_f64
+    (T = 2) and gpx_posterior_f64 (nrhs = 3; also the fused n = 200), each through the engine's own call with its
+    workspace replaced by exactly the reported bytes of 0xFF, 256-aligned or 8 bytes into the allocation, a 4 KiB guard
+    of 0xFF behind them.  Padded n = 384: three row tiles, the smallest pruned size.  One byte less is rejected; the
+    results have the bits of the engine's call with its own workspace; the guard is intact."""
+    n, d, m, guard = (200 if call == "posterior_fused" else 384), 3, 3000, 4096
+    X, y = O.synthetic_problem(n, d, 21)
+    Y = np.stack([y, np.sin(3 * X).sum(1), np.cos(2 * X).sum(1)], 1)
+    kp = KernelParams("rbf", botorch_default_lengthscale(d), noise=1e-4)
+    Xs = t(candidates(m, d))
+    lib, nbytes = engine.lib, ctypes.c_size_t()
+    if call == "topk":
+        st = engine.fit(t(X), t(y), kp)
+        assert lib.gpx_acquire_topk_workspace_size(n, m, 5, ctypes.byref(nbytes)) == _capi.GPX_OK
+        run = lambda: engine.acquire_topk(st, Xs, 5, best_f=float(y.max()))
+    elif call == "multi":
+        sts = engine.fit_outputs(t(X), t(Y[:, :2]), [kp, kp.replace(outputscale=1.5)])
+        assert lib.gpx_sweep_multi_workspace_size(n, m, ctypes.byref(nbytes)) == _capi.GPX_OK
+        run = lambda: engine.acquire_multi(sts, Xs, "ucb", weights=[0.5, 1.0])
+    else:
+        st = engine.fit(t(X), t(Y), kp)
+        assert lib.gpx_sweep_workspace_size(n, 3, m, ctypes.byref(nbytes)) == _capi.GPX_OK
+        run = lambda: engine.posterior(st, Xs)
+    nb = nbytes.value
+    want = [a.clone() for a in run()]
+    big = torch.empty(offset + nb + guard, dtype=torch.uint8, device=DEV)
+    assert big.data_ptr() % 256 == 0
+    asked = []
+    for size in (nb - 1, nb):
+        big.fill_(0xFF)
+        monkeypatch.setattr(engine, "workspace", lambda key, need: (asked.append(need), big[offset:offset + size])[1])
+        if size < nb:
+            with pytest.raises(_capi.GPXError, match="workspace too small"):
+                run()
+        else:
+            got = run()
+    torch.cuda.synchronize()
+    assert asked == [nb, nb]  # the engine asks for what the size function reports, and passes on what it is given
+    assert bool((big[:offset] == 0xFF).all()) and bool((big[offset + nb:] == 0xFF).all())
+    assert len(got) == len(want) == 2
+    for a, b in zip(got, want):
+        assert torch.equal(a.view(torch.int64), b.view(torch.int64))
+
+
 def test_pruning_engaged_on_the_lazy_path(engine):
     """The n = 640 problem of test_gpu_sweep_prune.test_pruning_engaged, where the oracle rules out over 90 % of the
     candidates after the first row tile: at most a quarter may reach the last tile, and fewer tiles run than in full."""
