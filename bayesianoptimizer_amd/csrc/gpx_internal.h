@@ -4,6 +4,7 @@
 #include <cstdint>
 #include <cstddef>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "../../include/gpx.h"
 #include "gpx_sweep_layout.h"  // NB, TILE, TT, WG, the PRUNE_* sizes and the sweep's workspace layout
@@ -13,6 +14,22 @@ namespace gpx {
 static_assert(TILE == GPX_TILE, "the padding granule of the C ABI");
 
 typedef double d4 __attribute__((ext_vector_type(4)));
+
+// p.d and p.kind as template arguments: f gets DMAX (4, 8, 16 or 32) resp. the kernel kind as a std::integral_constant.
+// A combination without a kernel (the MFMA build and the fused sweep at DMAX = 32, ...) is left out by the callers with
+// `if constexpr`, so only the kernels they name are built.
+template <int V>
+using Const = std::integral_constant<int, V>;
+template <class F>
+inline void with_dmax(int d, F&& f) {
+  d <= 4 ? f(Const<4>{}) : d <= 8 ? f(Const<8>{}) : d <= 16 ? f(Const<16>{}) : f(Const<32>{});
+}
+template <class F>
+inline void with_kind(int kind, F&& f) {
+  kind == GPX_KERNEL_RBF        ? f(Const<GPX_KERNEL_RBF>{})
+  : kind == GPX_KERNEL_MATERN52 ? f(Const<GPX_KERNEL_MATERN52>{})
+                                : f(Const<GPX_KERNEL_SCALE_LINEAR_MATERN52>{});
+}
 
 // ---- context -----------------------------------------------------------------------------------
 struct PendingTimer {
@@ -294,7 +311,7 @@ size_t debug_stage_product_bytes(int64_t ncols);
 hipError_t launch_debug_stage_product(Context* c, int npad, const double* W, int64_t ldw, const double* kstar,
                                       int64_t ldk, int ncols, const int* list, int I0, int nrows, int shape, double* ss,
                                       int64_t ldss, void* ws);
-// The lazy pruned sweep's bound of the posterior mean (gpx_sweep.hip 1b; RBF, fp64 covariance, d <= 16):
+// The lazy pruned sweep's bound of the posterior mean (gpx_mubound.hip; RBF, fp64 covariance, d <= 16):
 // mu_approx[c] +- mu_slack[c] holds the exact path's mean of candidate c.  prep: mu_prep_doubles(npad, d) doubles,
 // 256-byte aligned; its first int64 ends up as the count of 256-candidate workgroups on the unfactorised path.
 bool sweep_mu_bound_ok(const gpx_kernel_params& p);

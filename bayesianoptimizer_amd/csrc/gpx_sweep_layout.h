@@ -20,8 +20,8 @@ constexpr int PRUNE_HEAD_ROWS = 128;  // K* rows the head phase stores: the prod
 constexpr int PRUNE_DESC_BYTES = 32;  // sizeof(PruneDesc)
 static_assert(PRUNE_DESC_BYTES * PRUNE_MAX_STAGES <= 256 && 4 * PRUNE_MAX_STAGES <= 256, "header slots");
 
-// The mean bound's scratch (gpx_sweep.hip 1b): MUF_HEAD doubles of call-wide values, then per 64-row block the records
-// MuPrep, MuFact, MuStat and, where the fp32 form is built, MuFact32 (gpx_sweep.hip checks the sum against the structs).
+// The mean bound's scratch (gpx_mubound.hip): MUF_HEAD doubles of call-wide values, then per 64-row block the records
+// MuPrep, MuFact, MuStat and, where the fp32 form is built, MuFact32 (gpx_mubound.hip checks the sum against the structs).
 constexpr int MUF_HEAD = 32;
 constexpr bool mu_fp32_form(int DMAX) { return DMAX == 8; }
 constexpr int mu_prep_block_doubles(int D) {

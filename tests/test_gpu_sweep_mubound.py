@@ -1,4 +1,4 @@
-"""The lazy pruned sweep's bound of the posterior mean (gpx_sweep.hip 1b).
+"""The lazy pruned sweep's bound of the posterior mean (gpx_mubound.hip).
 
 The head phase no longer computes every candidate's exact mean: mu_bound_kernel gives mu_approx and mu_slack with
 |mu_approx - mu| <= mu_slack, mu being the value the exact path computes, and the survivors get their exact mean
@@ -7,29 +7,19 @@ full build's partials from gpx_debug_kstar_mu_f64, summed in sum_partials' order
 the device's fp64 exp, the gathered partials byte for byte, and (best_val, best_idx) bit for bit with sweep_prune = 2
 against 0 (full sweep) and -2 (exact head means).
 """
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
-from bayesianoptimizer_amd import GPEngine, KernelParams, botorch_default_lengthscale, _capi
+from bayesianoptimizer_amd import GPEngine, KernelParams, botorch_default_lengthscale
 from oracle import gp_oracle as O
+from tests.mu_bound_util import DEV, kstar_mu, mu_bound, mu_exact, t
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
-EPS1, EPS2 = 2.0 ** -20, 2.0 ** -120  # MUB_EPS1, MUB_EPS2 of gpx_sweep.hip
+EPS1, EPS2 = 2.0 ** -20, 2.0 ** -120  # MUB_EPS1, MUB_EPS2 of gpx_mubound.hip
 CHUNK640 = 209_664
 _fits = {}
 _cands = {}
-
-
-def t(a):
-    return torch.tensor(np.asarray(a, dtype=np.float64), device=DEV)
-
-
-def ptr(a):
-    return ctypes.c_void_p(a.data_ptr()) if a is not None else None
 
 
 def fitted(engine, n, d=4):
@@ -45,45 +35,6 @@ def candidates(m, d=4):
     if (m, d) not in _cands:
         _cands[(m, d)] = O.sobol_candidates(m, d, 22)
     return _cands[(m, d)]
-
-
-def kstar_mu(engine, kp, X, alpha, Xs, m, list_=None, count=None, mu_part=None, ldmu=0):
-    """gpx_debug_kstar_mu_f64 -> (K*, mean partials)."""
-    lib, n, d = engine.lib, X.shape[0], X.shape[1]
-    npad = int(lib.gpx_padded_n(n))
-    ld = (m + 255) // 256 * 256
-    out = torch.full((npad, ld), float("nan"), dtype=torch.float64, device=DEV)
-    if mu_part is None:
-        mu_part = torch.full((npad // 64, ld), float("nan"), dtype=torch.float64, device=DEV)
-    pc = kp.to_c(d)
-    st = lib.gpx_debug_kstar_mu_f64(engine.handle, ctypes.byref(pc), n, ptr(X), X.stride(0), ptr(alpha), ptr(Xs), m,
-                                    Xs.stride(0), ptr(list_), ptr(count), ptr(out), ld, ptr(mu_part), ldmu)
-    _capi.check(st, engine.handle)
-    torch.cuda.synchronize()
-    return out, mu_part
-
-
-def mu_exact(mu_part, m):
-    """The partials summed as sum_partials does: ascending row block, one accumulator."""
-    s = torch.zeros(m, dtype=torch.float64, device=DEV)
-    for jb in range(mu_part.shape[0]):
-        s = s + mu_part[jb, :m]
-    return s
-
-
-def mu_bound(engine, kp, X, alpha, Xs):
-    lib, n, d, m = engine.lib, X.shape[0], X.shape[1], Xs.shape[0]
-    nbytes = ctypes.c_size_t()
-    assert lib.gpx_debug_mu_bound_workspace_size(n, ctypes.byref(nbytes)) == _capi.GPX_OK
-    ws = torch.full((nbytes.value,), 0xFF, dtype=torch.uint8, device=DEV)
-    ma = torch.full((m,), float("nan"), dtype=torch.float64, device=DEV)
-    sl = torch.full((m,), float("nan"), dtype=torch.float64, device=DEV)
-    pc = kp.to_c(d)
-    st = lib.gpx_debug_mu_bound_f64(engine.handle, ctypes.byref(pc), n, ptr(X), X.stride(0), ptr(alpha), ptr(Xs), m,
-                                    Xs.stride(0), ptr(ma), ptr(sl), ptr(ws), ws.numel())
-    _capi.check(st, engine.handle)
-    torch.cuda.synchronize()
-    return ma, sl
 
 
 # ---- the bound holds and is not vacuous ---------------------------------------------------------------------------
@@ -117,7 +68,7 @@ def test_bound_holds_and_is_not_vacuous(engine, n, d):
     for name, alpha in cases.items():
         _, part = kstar_mu(engine, kp, Xd, alpha, Xsd, m)
         mu = mu_exact(part, m)
-        ma, sl = mu_bound(engine, kp, Xd, alpha, Xsd)
+        ma, sl = mu_bound(engine, kp, Xd, alpha, Xsd)[:2]
         err = (ma - mu).abs()
         worst = float((err[finite] / sl[finite].clamp_min(1e-300)).max())
         print(f"n={n} d={d} alpha {name}: max |mu_approx - mu| / mu_slack = {worst:.3g}, "
@@ -156,7 +107,7 @@ def test_fast_exponential_against_the_device_exp(engine):
         m = x.shape[0]
         K, _ = kstar_mu(engine, kp, X, alpha, x, m)
         E = K[0, :m]
-        et, sl = mu_bound(engine, kp, X, alpha, x)
+        et, sl = mu_bound(engine, kp, X, alpha, x)[:2]
         bound = EPS1 * et + EPS2
         ratio = float(((et - E).abs() / bound).max())
         worst = max(worst, ratio)

@@ -1,4 +1,4 @@
-"""The factorised form of the pruned sweep's head mean bound (gpx_sweep.hip 1b: mu_fact_kernel).
+"""The factorised form of the pruned sweep's head mean bound (gpx_mubound.hip: mu_fact_kernel).
 
 With one centre for every row block, exp(-r2 / 2) = exp(-|a|^2 / 2) exp(-|b|^2 / 2) exp(a.b): the row factor goes into
 alpha, the candidate factor is applied once, and an entry costs one conversion, one v_exp_f32 and two fp32 FMAs.  A
@@ -8,30 +8,20 @@ gpx_debug_kstar_mu_f64, summed in sum_partials' order), the slack's size, which 
 the old path, an int64 at the start of the debug entry's 256-byte-aligned workspace), and (best_val, best_idx) bit for
 bit against sweep_prune = 0.
 """
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
-from bayesianoptimizer_amd import KernelParams, botorch_default_lengthscale, _capi
+from bayesianoptimizer_amd import KernelParams, botorch_default_lengthscale
 from oracle import gp_oracle as O
+from tests.mu_bound_util import DEV, kstar_mu, mu_bound, mu_exact, t
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
-Y_LIMIT = 16.0  # MUF_Y_LIMIT of gpx_sweep.hip
+Y_LIMIT = 16.0  # MUF_Y_LIMIT of gpx_mubound.hip
 LOG2E = 1.4426950408889634
 WG = 256
 _fits = {}
 _cands = {}
-
-
-def t(a):
-    return torch.tensor(np.asarray(a, dtype=np.float64), device=DEV)
-
-
-def ptr(a):
-    return ctypes.c_void_p(a.data_ptr()) if a is not None else None
 
 
 def fitted(engine, n, d=4):
@@ -47,47 +37,6 @@ def candidates(m, d=4):
     if (m, d) not in _cands:
         _cands[(m, d)] = O.sobol_candidates(m, d, 22)
     return _cands[(m, d)]
-
-
-def kstar_mu(engine, kp, X, alpha, Xs, m):
-    """gpx_debug_kstar_mu_f64 -> the full build's mean partials."""
-    lib, n, d = engine.lib, X.shape[0], X.shape[1]
-    npad = int(lib.gpx_padded_n(n))
-    ld = (m + 255) // 256 * 256
-    out = torch.full((npad, ld), float("nan"), dtype=torch.float64, device=DEV)
-    mu_part = torch.full((npad // 64, ld), float("nan"), dtype=torch.float64, device=DEV)
-    pc = kp.to_c(d)
-    st = lib.gpx_debug_kstar_mu_f64(engine.handle, ctypes.byref(pc), n, ptr(X), X.stride(0), ptr(alpha), ptr(Xs), m,
-                                    Xs.stride(0), None, None, ptr(out), ld, ptr(mu_part), 0)
-    _capi.check(st, engine.handle)
-    torch.cuda.synchronize()
-    return mu_part
-
-
-def mu_exact(mu_part, m):
-    """The partials summed as sum_partials does: ascending row block, one accumulator."""
-    s = torch.zeros(m, dtype=torch.float64, device=DEV)
-    for jb in range(mu_part.shape[0]):
-        s = s + mu_part[jb, :m]
-    return s
-
-
-def mu_bound(engine, kp, X, alpha, Xs):
-    """gpx_debug_mu_bound_f64 -> (mu_approx, mu_slack, workgroups that took the unfactorised path)."""
-    lib, n, d, m = engine.lib, X.shape[0], X.shape[1], Xs.shape[0]
-    nbytes = ctypes.c_size_t()
-    assert lib.gpx_debug_mu_bound_workspace_size(n, ctypes.byref(nbytes)) == _capi.GPX_OK
-    ws = torch.full((nbytes.value,), 0xFF, dtype=torch.uint8, device=DEV)
-    ma = torch.full((m,), float("nan"), dtype=torch.float64, device=DEV)
-    sl = torch.full((m,), float("nan"), dtype=torch.float64, device=DEV)
-    pc = kp.to_c(d)
-    st = lib.gpx_debug_mu_bound_f64(engine.handle, ctypes.byref(pc), n, ptr(X), X.stride(0), ptr(alpha), ptr(Xs), m,
-                                    Xs.stride(0), ptr(ma), ptr(sl), ptr(ws), ws.numel())
-    _capi.check(st, engine.handle)
-    torch.cuda.synchronize()
-    off = (-ws.data_ptr()) % 256
-    fallback = int(ws[off:off + 8].view(torch.int64).item())
-    return ma, sl, fallback
 
 
 def geometry(X, ls):
@@ -143,8 +92,8 @@ def alpha_cases(st, n, rng):
 
 def check_bound(engine, kp, Xd, alpha, Xsd, finite, label):
     m = Xsd.shape[0]
-    mu = mu_exact(kstar_mu(engine, kp, Xd, alpha, Xsd, m), m)
-    ma, sl, fallback = mu_bound(engine, kp, Xd, alpha, Xsd)
+    mu = mu_exact(kstar_mu(engine, kp, Xd, alpha, Xsd, m)[1], m)
+    ma, sl, fallback, _ = mu_bound(engine, kp, Xd, alpha, Xsd)
     err = (ma - mu).abs()
     worst = float((err[finite] / sl[finite].clamp_min(1e-300)).max())
     print(f"{label}: max |mu_approx - mu| / mu_slack = {worst:.3g}, max slack {float(sl[finite].max()):.3g}, "

@@ -1,4 +1,5 @@
-"""Which form of the head mean bound each workgroup of 256 candidates takes (gpx_debug_mu_bound_f64's two counters): one
+"""Which form of the head mean bound (csrc/gpx_mubound.hip) each workgroup of 256 candidates takes
+(gpx_debug_mu_bound_f64's two counters, written by mu_classify): one
 JSON line per problem with the workgroups on mu_bound_kernel, on the fp64 factorised form and on the fp32 one, and the
 largest Y_c of the candidates.  Problems: the bench step (n = 4096, d = 8, seed 0, 2^20 Sobol candidates), the seed-1000
 problem and n = 1024."""

@@ -1,4 +1,4 @@
-// Probe: the rounding of v_mfma_f32_16x16x4_f32 as mu_fact32_kernel uses it (gpx_sweep.hip 1b, (g32)): a chain of KS = 1
+// Probe: the rounding of v_mfma_f32_16x16x4_f32 as mu_fact32_kernel uses it (gpx_mubound.hip, (g32)): a chain of KS = 1
 // or 2 instructions on a zero accumulator, so a dot product of d = 4 KS fp32 pairs.  The proof assumes no more than the
 // standard model, |yhat - sum a_i b_i| <= gamma_d sum |a_i b_i| with gamma_d = d v / (1 - d v), v = 2^-24.  This runs the
 // chain on adversarial fp32 inputs, compares with the exact dot product of the same fp32 inputs (every product of two
