@@ -219,6 +219,11 @@ _PROTOS = {
                                                POINTER(c_void_p), POINTER(c_int64), POINTER(c_void_p),
                                                POINTER(c_double), POINTER(c_double), POINTER(c_double), _p, c_int64,
                                                c_int64, POINTER(AcqParamsC), c_int64, _p, _p, _p, _p, c_size_t]),
+    "gpx_acquire_topk_multi_workspace_size": (c_int32, [c_int64, c_int64, c_int64, POINTER(c_size_t)]),
+    "gpx_acquire_topk_multi_f64": (c_int32, [_h, POINTER(KernelParamsC), c_int64, c_int64, _p, c_int64,
+                                             POINTER(c_void_p), POINTER(c_int64), POINTER(c_void_p),
+                                             POINTER(c_double), POINTER(c_double), POINTER(c_double), _p, c_int64,
+                                             c_int64, POINTER(AcqParamsC), c_int64, c_int64, _p, _p, _p, c_size_t]),
     "gpx_argmax_combine_f64": (c_int32, [_h, _p, _p, c_int64, _p, _p]),
     "gpx_comm_unique_id": (c_int32, [c_void_p]),
     "gpx_comm_init": (c_int32, [_h, c_void_p, c_int32, c_int32, POINTER(c_void_p)]),

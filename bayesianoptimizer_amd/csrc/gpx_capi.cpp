@@ -1324,15 +1324,18 @@ gpx_status gpx_sweep_multi_workspace_size(int64_t n, int64_t m, size_t* bytes) {
   return GPX_OK;
 }
 
-gpx_status gpx_acquire_argmax_multi_f64(gpx_handle h, const gpx_kernel_params* p, int64_t T, int64_t n, const double* X,
-                                        int64_t ldx, const double* const* W_host, const int64_t* ldw_host,
-                                        const double* const* alpha_host, const double* weights_host,
-                                        const double* y_mean_host, const double* y_scale_host, const double* Xs,
-                                        int64_t m, int64_t ldxs, const gpx_acq_params* a, int64_t index_offset,
-                                        double* best_val, int64_t* best_idx, double* scores_out, void* ws,
-                                        size_t ws_bytes) {
+// gpx_acquire_argmax_multi_f64 (k = 0: best_val / best_idx, optional scores_out) and gpx_acquire_topk_multi_f64 (k >= 1:
+// val_out / idx_out, the top-k regions behind the multi-output sweep's workspace) share validation and the full sweep.
+static gpx_status acquire_multi_impl(gpx_handle h, const gpx_kernel_params* p, int64_t T, int64_t n, const double* X,
+                                     int64_t ldx, const double* const* W_host, const int64_t* ldw_host,
+                                     const double* const* alpha_host, const double* weights_host,
+                                     const double* y_mean_host, const double* y_scale_host, const double* Xs,
+                                     int64_t m, int64_t ldxs, const gpx_acq_params* a, int64_t index_offset,
+                                     double* best_val, int64_t* best_idx, double* scores_out, void* ws,
+                                     size_t ws_bytes, int64_t k, double* val_out, int64_t* idx_out) {
   Context* c = reinterpret_cast<Context*>(h);
   if (!c) return GPX_INVALID_ARG;
+  const bool topk = val_out || idx_out || k != 0;
   if (T < 1 || T > 64) return fail(c, GPX_INVALID_ARG, "T (outputs) must be in [1, 64]");
   GPX_NONNULL(c, p);
   GPX_NONNULL(c, weights_host);
@@ -1345,18 +1348,58 @@ gpx_status gpx_acquire_argmax_multi_f64(gpx_handle h, const gpx_kernel_params* p
   }
   GPX_TRY(check_sweep_sizes(c, p, n, m));
   GPX_TRY(check_acq(c, a, index_offset, false));
+  if (topk && (k < 1 || k > m || k > GPX_TOPK_SWEEP_MAX))
+    return fail(c, GPX_INVALID_ARG, "k must be in [1, min(m, GPX_TOPK_SWEEP_MAX)]");
   GPX_TRY(check_sweep_arrays(c, {{X, "X"}, {W_host, "W_host"}, {ldw_host, "ldw_host"}, {alpha_host, "alpha_host"},
-                                 {Xs, "Xs"}, {best_val, "best_val"}, {best_idx, "best_idx"}, {ws, "ws"}}, p, ldx, ldxs));
+                                 {Xs, "Xs"}, {topk ? val_out : best_val, topk ? "val_out" : "best_val"},
+                                 {topk ? (void*)idx_out : (void*)best_idx, topk ? "idx_out" : "best_idx"}, {ws, "ws"}},
+                             p, ldx, ldxs));
   const int64_t npad = padded(n);
   for (int64_t t = 0; t < T; ++t) {
     if (!W_host[t] || !alpha_host[t]) return fail(c, GPX_INVALID_ARG, "W / alpha of output " + std::to_string(t) + " is NULL");
     GPX_TRY(check_ld(c, ldw_host[t], npad, "W", true));
   }
   gpx::SweepWorkspace w;
-  GPX_TRY(carve_sweep(c, gpx::sweep_layout(npad, 1, m, 0, true), ws, ws_bytes, "multi-output sweep workspace too small",
-                      &w));
+  if (topk) {
+    const gpx::TopkMultiLayout TL = gpx::topk_multi_layout(npad, m, k, gpx::topk_workspace_bytes(m));
+    if (ws_bytes < TL.total) return fail(c, GPX_INVALID_ARG, "acquire_topk_multi workspace too small");
+    w = gpx::topk_multi_carve(ws, TL, k);
+  } else {
+    GPX_TRY(carve_sweep(c, gpx::sweep_layout(npad, 1, m, 0, true), ws, ws_bytes,
+                        "multi-output sweep workspace too small", &w));
+  }
   const gpx::SweepBuffers& b = w.b;
   GPX_USE_DEVICE(c);
+  if (topk) {
+    // the pruned form where gpx_acquire_topk_f64 would take its lazy one for every output; else the full sweep into the
+    // call's own score array, then the sort
+    bool prune = true;
+    for (int64_t t = 0; t < T; ++t) prune = prune && gpx::sweep_prune_ok(c, p[t], (int)npad) && gpx::sweep_lazy_ok(p[t]);
+    const auto tiles = [&](int64_t mc) { return (mc + 127) / 128 * (npad / 128); };
+    c->sweep_stats[0] = m;
+    c->sweep_stats[1] = prune ? 0 : m;
+    c->sweep_stats[2] = c->sweep_stats[3] = 0;
+    // [3]: the tiles of the full multi-output sweep, every unfused output's share
+    for (int64_t t = 0; t < T; ++t)
+      if (!gpx::sweep_fused_ok(c, p[t], (int)npad, 1)) c->sweep_stats[3] += m / b.chunk * tiles(b.chunk) + tiles(m % b.chunk);
+    c->sweep_stats_dev = prune ? w.ps.stats : nullptr;
+    if (prune) {
+      gpx::MultiModel outs[64];  // (T <= 64)
+      for (int64_t t = 0; t < T; ++t)
+        outs[t] = {p + t, W_host[t], ldw_host[t], alpha_host[t], weights_host[t],
+                   y_mean_host ? y_mean_host[t] : 0.0, y_scale_host ? y_scale_host[t] : 1.0};
+      for (int64_t s = 0; s < m; s += b.chunk) {
+        const int64_t mc = gpx::sweep_span_size(false, s, m, b.chunk, 0);
+        GPX_TRY(hip_check(c, gpx::launch_topk_multi_chunk(c, (int)T, outs, (int)n, (int)npad, X, ldx,
+                                                          {Xs + s * ldxs, ldxs, mc, index_offset + s}, w, *a, s == 0,
+                                                          c->sweep_stats),
+                          "acquire_topk (multi-output)"));
+      }
+      return hip_check(c, gpx::launch_topk_result(c, w.tk, val_out, idx_out), "topk result");
+    }
+    c->sweep_stats[2] = c->sweep_stats[3];
+    scores_out = w.tk.scores;
+  }
   gpx::MultiOutput mo;
   mo.acc_mu = w.acc_mu;
   mo.acc_var = w.acc_var;
@@ -1377,7 +1420,40 @@ gpx_status gpx_acquire_argmax_multi_f64(gpx_handle h, const gpx_kernel_params* p
                       "acquire (multi-output score)"));
     rec += (mc + 255) / 256;
   }
+  if (topk) {
+    GPX_TRY(hip_check(c, gpx::launch_topk(c, w.tk.scores, m, k, idx_out, val_out, w.tk.sort_ws, w.tk.sort_bytes), "topk"));
+    return hip_check(c, gpx::launch_index_shift(c, idx_out, k, index_offset), "topk indices");
+  }
   return hip_check(c, gpx::launch_argmax_final(c, b.rec_val, b.rec_idx, rec, best_val, best_idx), "argmax");
+}
+
+gpx_status gpx_acquire_argmax_multi_f64(gpx_handle h, const gpx_kernel_params* p, int64_t T, int64_t n, const double* X,
+                                        int64_t ldx, const double* const* W_host, const int64_t* ldw_host,
+                                        const double* const* alpha_host, const double* weights_host,
+                                        const double* y_mean_host, const double* y_scale_host, const double* Xs,
+                                        int64_t m, int64_t ldxs, const gpx_acq_params* a, int64_t index_offset,
+                                        double* best_val, int64_t* best_idx, double* scores_out, void* ws,
+                                        size_t ws_bytes) {
+  return acquire_multi_impl(h, p, T, n, X, ldx, W_host, ldw_host, alpha_host, weights_host, y_mean_host, y_scale_host,
+                            Xs, m, ldxs, a, index_offset, best_val, best_idx, scores_out, ws, ws_bytes, 0, nullptr,
+                            nullptr);
+}
+
+gpx_status gpx_acquire_topk_multi_workspace_size(int64_t n, int64_t m, int64_t k, size_t* bytes) {
+  if (!bytes || n < 1 || m < 1 || k < 1 || k > m || k > GPX_TOPK_SWEEP_MAX) return GPX_INVALID_ARG;
+  *bytes = gpx::topk_multi_layout(padded(n), m, k, gpx::topk_workspace_bytes(m)).total;
+  return GPX_OK;
+}
+
+gpx_status gpx_acquire_topk_multi_f64(gpx_handle h, const gpx_kernel_params* p, int64_t T, int64_t n, const double* X,
+                                      int64_t ldx, const double* const* W_host, const int64_t* ldw_host,
+                                      const double* const* alpha_host, const double* weights_host,
+                                      const double* y_mean_host, const double* y_scale_host, const double* Xs,
+                                      int64_t m, int64_t ldxs, const gpx_acq_params* a, int64_t index_offset, int64_t k,
+                                      double* val_out, int64_t* idx_out, void* ws, size_t ws_bytes) {
+  if (h && k == 0) return fail(reinterpret_cast<Context*>(h), GPX_INVALID_ARG, "k must be >= 1");
+  return acquire_multi_impl(h, p, T, n, X, ldx, W_host, ldw_host, alpha_host, weights_host, y_mean_host, y_scale_host,
+                            Xs, m, ldxs, a, index_offset, nullptr, nullptr, nullptr, ws, ws_bytes, k, val_out, idx_out);
 }
 
 gpx_status gpx_argmax_combine_f64(gpx_handle h, const double* vals, const int64_t* idx, int64_t count,

@@ -291,8 +291,32 @@ inline SweepWorkspace sweep_carve(void* ws, const SweepLayout& L, int64_t k = 0)
   w.after_main = reinterpret_cast<double*>(base + L.after_main);
   return w;
 }
+// gpx_acquire_topk_multi_f64: the multi-output sweep's pointers, and the top-k part from the regions behind its total
+inline SweepWorkspace topk_multi_carve(void* ws, const TopkMultiLayout& T, int64_t k) {
+  SweepWorkspace w = sweep_carve(ws, T.sweep);
+  char* base = reinterpret_cast<char*>(up256(reinterpret_cast<uintptr_t>(ws)));
+  auto at = [&](TopkMultiRegion id) { return T.r[id].bytes ? base + T.r[id].at : nullptr; };
+  auto dbl = [&](TopkMultiRegion id) { return reinterpret_cast<double*>(at(id)); };
+  auto i64 = [&](TopkMultiRegion id) { return reinterpret_cast<int64_t*>(at(id)); };
+  w.tk = {(int)k, reinterpret_cast<int*>(at(TM_TOPK_HEAD)), dbl(TM_POOL_VAL), i64(TM_POOL_IDX), dbl(TM_LIST_VAL),
+          i64(TM_LIST_IDX), dbl(TM_SCORES), at(TM_SORT_WS), T.r[TM_SORT_WS].bytes};
+  return w;
+}
 // the configurations of the MFMA K* build (fp64 covariance, d <= 16); the others keep launch_sweep_chunk_pruned
 bool sweep_lazy_ok(const gpx_kernel_params& p);
+// One chunk of gpx_acquire_topk_multi_f64's pruned form: the seed block of the call's first chunk through
+// the full multi-output path, then per output the first row tile of the staged columns (exact objective mean, upper
+// bound of its variance), one bound-and-select launch against the pool's k-th score, and per output the survivors'
+// full product; their exact scores are merged into the pool.  host_stats[1], [2] gain the seed block's share.
+struct MultiModel {  // one output of the objective
+  const gpx_kernel_params* p;
+  const double* W; int64_t ldw;
+  const double* alpha;
+  double weight, y_mean, y_scale;
+};
+hipError_t launch_topk_multi_chunk(Context* c, int T, const MultiModel* outs, int n, int npad, const double* X,
+                                   int64_t ldx, const SweepCands& q, const SweepWorkspace& w, const gpx_acq_params& a,
+                                   bool first, int64_t* host_stats);
 // One super-chunk of gpx_acquire_argmax_f64; first: the call's first (resets the incumbent and the counters, scores the
 // seed block in full).  *recs: the records written so far, advanced.  host_stats as above.
 hipError_t launch_sweep_super_pruned(const SweepModel& M, const SweepCands& q, const SweepBuffers& b,

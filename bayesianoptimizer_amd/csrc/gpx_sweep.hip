@@ -21,7 +21,9 @@
 // prune_compact_kernel gathers the surviving K* columns; the (value, index) pair has the bits of the full sweep.  Where
 // the MFMA K* build applies the pruned form is lazy (launch_sweep_super_pruned): K* rows 0 .. 127 for every candidate,
 // full-height columns rebuilt from the survivor list.  Both share launch_seed_block and launch_stages;
-// gpx_acquire_topk_f64 is the same sweep with the k-th best exact score as its incumbent (topk_pool_kernel).
+// gpx_acquire_topk_f64 is the same sweep with the k-th best exact score as its incumbent (topk_pool_kernel), and
+// gpx_acquire_topk_multi_f64 (launch_topk_multi_chunk) its form for a linear objective over independent outputs: one
+// head tile per output, the variance bounds summed in the accumulators before one bound pass.
 // Workspace: gpx_sweep_layout.h (sweep_carve, gpx_internal.h, turns it into pointers); head mean bound: gpx_mubound.hip.
 #include "gpx_internal.h"
 #include "gpx_device.h"
@@ -852,6 +854,13 @@ struct PruneSel {
 };
 constexpr double PRUNE_EPS = 1e-9;  // margin of the bound test over acq_score's rounding
 
+// The accumulated objective's moments at column c (what mode 2 summed over the outputs), BoTorch's floor on the scored
+// variance: mode 3's operands, and the bound pass's of the multi-output top-k form (multi_bound_select_kernel).
+__device__ __forceinline__ void objective_moments(const FinalizeArgs& fa, int64_t c, double& mu, double& var) {
+  mu = fa.acc_mu[c];
+  var = fmax(fa.acc_var[c], 1e-12);
+}
+
 // mode 0: posterior (mean / variance out); 1: acquisition + 256-candidate block argmax; 2: one output of a multi-output
 // objective into the accumulators; 3: acquisition + block argmax of the accumulated objective (no partials read);
 // 4: bound and select of the pruned sweep: mode 1's score from the first nI row tiles' partials only, an upper bound of
@@ -883,8 +892,7 @@ __global__ void __launch_bounds__(WG) finalize_kernel(FinalizeArgs fa, int mode,
   if (valid) {
     double mu, var;
     if (mode == 3) {
-      mu = fa.acc_mu[c];
-      var = fmax(fa.acc_var[c], 1e-12);
+      objective_moments(fa, c, mu, var);
     } else {
       // prior variance k(x, x)
       double kd = p.outputscale;
@@ -977,6 +985,36 @@ __global__ void __launch_bounds__(WG) finalize_kernel(FinalizeArgs fa, int mode,
     rec_idx[blockIdx.x] = bi;
     if (ps.tau) atomicMax(ps.tau, tau_key(bv));
   }
+}
+
+// Bound and select of the multi-output top-k form (gpx_acquire_topk_multi_f64): after the head phase the accumulators
+// hold the exact objective mean and, from the first row tile of every output, an upper bound of its variance, so mode
+// 3's score of them bounds the candidate's exact score (every acquisition is non-decreasing in the variance).  Slot t
+// of *desc (chunk column col0 + t) survives unless the bound lies below the incumbent by more than the margin, as in
+// mode 4 (a NaN bound survives): one ballot and one atomic add per wave, any slot order.
+__global__ void __launch_bounds__(WG) multi_bound_select_kernel(FinalizeArgs fa, const PruneDesc* __restrict__ desc,
+                                                                const unsigned long long* __restrict__ tau_key_in,
+                                                                int2* __restrict__ survivors, int* __restrict__ count) {
+  const PruneDesc d = *desc;
+  if ((int64_t)blockIdx.x * WG >= d.ncols) return;
+  const int t = blockIdx.x * WG + threadIdx.x;
+  const bool valid = t < d.ncols;
+  const int64_t c = valid ? d.col0 + t : 0;
+  double score = -INFINITY;
+  if (valid) {
+    double mu, var;
+    objective_moments(fa, c, mu, var);
+    score = acq_score(fa.acq_kind, mu, var, fa.best_f, fa.beta);
+  }
+  const double tau = tau_value(*tau_key_in);
+  const bool keep = valid && !(score + PRUNE_EPS * (fabs(score) + fabs(tau) + 1.0) < tau);
+  const unsigned long long mask = __ballot(keep);
+  if (mask == 0) return;
+  const int lane = threadIdx.x & 63;
+  int base = 0;
+  if (lane == 0) base = atomicAdd(count, __popcll(mask));
+  base = __shfl(base, 0);
+  if (keep) survivors[base + __popcll(mask & ((1ull << lane) - 1))] = make_int2((int)c, t);
 }
 
 // The pruned sweep's per-chunk reset (one thread): the first stage's column set (the chunk's columns from col0 on, in
@@ -1652,6 +1690,121 @@ hipError_t launch_sweep_super_pruned(const SweepModel& M, const SweepCands& q, c
                   C, tk);
     *recs += (cap + WG - 1) / WG;
   }
+  return hipGetLastError();
+}
+
+// The pruned top-k sweep of a linear objective over T independent outputs (gpx_acquire_topk_multi_f64), one
+// chunk.  One K*, mu_part and ss_part buffer serves the outputs in turn, always in ascending t, so the accumulators of a
+// candidate scored in full form in the full multi-output sweep's order.
+//  seed   (the call's first chunk) the leading PRUNE_SEED candidates through launch_sweep_chunk with the accumulators,
+//         mode 3 into the scored list, pool: the pool's k-th score is the incumbent.
+//  head   per output: K* rows 0 .. 127 (KSTAR_FULL) and the other row blocks' mean partials (KSTAR_MU), row tile 0 of
+//         the product, mode 2 over that tile's partial alone: exact mean, upper bound of the variance.  Then
+//         multi_bound_select_kernel: the survivors go to ph.survivors, their count to ps.count[0].
+//  tail   per output: KSTAR_GATHER rebuilds the survivors' columns (mean partials scattered to the columns' own places),
+//         every row tile through launch_tail_stage, mode 2 through the round's descriptor with all nI partials.  Then
+//         mode 3 through the descriptor into the scored list, pool.  The grids are sized for every staged column;
+//         workgroups beyond the survivors return at once.
+hipError_t launch_topk_multi_chunk(Context* c, int T, const MultiModel* outs, int n, int npad, const double* X,
+                                   int64_t ldx, const SweepCands& q, const SweepWorkspace& w, const gpx_acq_params& a,
+                                   bool first, int64_t* host_stats) {
+  const SweepBuffers& b = w.b;
+  const PruneState& ps = w.ps;
+  const TopkSweep* tk = &w.tk;
+  const int64_t C = b.chunk;
+  const int nJB = npad / NB, nI = npad / TT;
+  const SeedPlan sp = seed_plan(first, q.m, C);
+  auto model = [&](int t) {
+    return SweepModel{c, *outs[t].p, n, npad, X, ldx, outs[t].W, outs[t].ldw, outs[t].alpha, 1};
+  };
+  auto accumulate = [&](int t) {  // mode 2 of output t
+    FinalizeArgs fa = finalize_args(*outs[t].p, &a, 1, nullptr, nullptr);
+    fa.y_mean[0] = outs[t].y_mean;
+    fa.y_scale[0] = outs[t].y_scale;
+    fa.weight = outs[t].weight;
+    fa.first = t == 0;
+    fa.acc_mu = w.acc_mu;
+    fa.acc_var = w.acc_var;
+    return fa;
+  };
+  FinalizeArgs fs{};  // mode 3 and the bound pass
+  fs.acq_kind = a.kind;
+  fs.best_f = a.best_f;
+  fs.beta = a.beta;
+  fs.acc_mu = w.acc_mu;
+  fs.acc_var = w.acc_var;
+  auto score = [&](int64_t cols, const PruneSel& sel) {  // mode 3 into the scored list, then the pool
+    LaunchTimer tm(c, GPX_TIMER_ACQ);
+    finalize_kernel<<<(unsigned)((cols + WG - 1) / WG), WG, 0, c->stream>>>(
+        fs, 3, nullptr, 0, cols, 0, 1, 0, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, b.rec_val, b.rec_idx,
+        q.index_offset, score_sel(sel, ps, tk));
+    launch_topk_pool(c, ps, tk, C);
+  };
+  // (rows0 = T: the head runs one row tile per output over the staged columns' tiles)
+  prune_init_kernel<<<1, 64, 0, c->stream>>>(ps.desc, ps.count, ps.tau, ps.stats, sp.col0, sp.ncols, T, 0, first,
+                                             tk->head);
+  if (sp.seed) {
+    MultiOutput mo;
+    mo.acc_mu = w.acc_mu;
+    mo.acc_var = w.acc_var;
+    for (int t = 0; t < T; ++t) {
+      mo.weight = outs[t].weight;
+      mo.y_mean = outs[t].y_mean;
+      mo.y_scale = outs[t].y_scale;
+      mo.first = t == 0;
+      (void)launch_sweep_chunk(model(t), q.first(sp.seed), b, 1, &a, SweepOut(), 0, &mo);  // (the error is read below)
+    }
+    host_stats[1] += sp.seed;
+    host_stats[2] += (int64_t)T * ((sp.seed + TT - 1) / TT) * nI;
+    score(sp.seed, PruneSel{});
+  }
+  if (sp.ncols == 0) return hipGetLastError();
+  const int tiles = (sp.ncols + TT - 1) / TT, blocks = (sp.ncols + WG - 1) / WG;
+  PruneSel sel{};
+  sel.desc = ps.desc;
+  for (int t = 0; t < T; ++t) {
+    const SweepModel M = model(t);
+    launch_kstar(M, q, b, KSTAR_FULL, KstarAux{}, PRUNE_HEAD_ROWS);
+    KstarAux aux{};
+    aux.jb0 = PRUNE_HEAD_ROWS / NB;
+    launch_kstar(M, q, b, KSTAR_MU, aux);
+    LaunchTimer tm(c, GPX_TIMER_TRMM);
+    const PruneStage st{prune_bufs(b.kstar, C, ps), ps.desc, 0, 1, 0};
+    trmm_stage_kernel<<<tiles, WG, 0, c->stream>>>(M.W, M.ldw, C, nI, b.ss_part, st);
+    finalize_kernel<<<blocks, WG, 0, c->stream>>>(accumulate(t), 2, q.Xs, q.ldxs, q.m, C, 1, nJB, 1, b.mu_part, b.ss_part,
+                                                  nullptr, 0, nullptr, nullptr, nullptr, nullptr, q.index_offset, sel);
+  }
+  {
+    LaunchTimer tm(c, GPX_TIMER_ACQ);
+    multi_bound_select_kernel<<<blocks, WG, 0, c->stream>>>(fs, ps.desc, ps.tau, w.ph.survivors, ps.count);
+  }
+  sel.desc = ps.desc + 1;
+  sel.list2 = w.ph.survivors;
+  for (int t = 0; t < T; ++t) {
+    const SweepModel M = model(t);
+    KstarAux aux{};
+    aux.list = reinterpret_cast<const int*>(w.ph.survivors);
+    aux.lstride = 2;
+    aux.count = ps.count;
+    aux.first = 0;
+    aux.cap = sp.ncols;
+    aux.pad = reinterpret_cast<int*>(w.ph.survivors);
+    aux.desc = ps.desc + 1;
+    aux.rcount = ps.count + 1;
+    aux.stats = ps.stats;
+    aux.rows0 = nI;
+    aux.last = t == T - 1;  // (the survivors count as computed to the end once, with the last output)
+    aux.mu_out = b.mu_part;
+    aux.ldmu = C;
+    launch_kstar(M, q.first(sp.ncols), b, KSTAR_GATHER, aux);
+    LaunchTimer tm(c, GPX_TIMER_TRMM);
+    const PruneStage st{prune_bufs(b.kstar, C, ps, w.ph.survivors), ps.desc + 1, 0, nI, 0};
+    launch_tail_stage(c, M.W, M.ldw, C, nI, b.ss_part, st, tiles);
+    finalize_kernel<<<blocks, WG, 0, c->stream>>>(accumulate(t), 2, q.Xs, q.ldxs, q.m, C, 1, nJB, nI, b.mu_part,
+                                                  b.ss_part, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
+                                                  q.index_offset, sel);
+  }
+  score(sp.ncols, sel);
   return hipGetLastError();
 }
 

@@ -194,4 +194,46 @@ inline SweepLayout sweep_layout(int64_t npad, int64_t nrhs, int64_t m, int64_t k
   return L;
 }
 
+// gpx_acquire_topk_multi_f64's workspace: the multi-output sweep's (sweep_layout with multi: the chunk's K*, partials
+// and records, the pruned part's descriptors, counts, incumbent, counters and survivor list, the two accumulators), and
+// behind its total the top-k regions, each 256-aligned.  The offsets count from the same 256-aligned base as the
+// sweep's; the extra part starts at the first aligned offset behind the accumulators, so it does not depend on the
+// caller's pointer.  tests/host/topk_multi_layout_check.cpp checks it against a second statement.
+enum TopkMultiRegion {
+  TM_TOPK_HEAD,  // 256 bytes: entries in the scored list and in the pool
+  TM_POOL_VAL,   // k doubles
+  TM_POOL_IDX,   // k int64
+  TM_LIST_VAL,   // the scored list: C pairs
+  TM_LIST_IDX,
+  TM_SCORES,     // the composed path's m scores
+  TM_SORT_WS,    // and its sort workspace (topk_workspace_bytes)
+  TM_REGIONS
+};
+struct TopkMultiLayout {
+  SweepLayout sweep;  // the multi-output sweep's regions (sweep.total: gpx_sweep_multi_workspace_size)
+  SweepLayout::Region r[TM_REGIONS];
+  size_t total = 0;   // gpx_acquire_topk_multi_workspace_size
+};
+inline TopkMultiLayout topk_multi_layout(int64_t npad, int64_t m, int64_t k, size_t sort_bytes) {
+  TopkMultiLayout T;
+  T.sweep = sweep_layout(npad, 1, m, 0, true);
+  const SweepLayout::Region& last = T.sweep.r[SR_ACC_VAR];
+  size_t at = up256(last.at + last.bytes), reported = T.sweep.total + 256;  // (one more alignment step)
+  auto take = [&](TopkMultiRegion id, size_t bytes) {
+    T.r[id].at = at;
+    T.r[id].bytes = bytes;
+    at += bytes;
+    reported += bytes;
+  };
+  take(TM_TOPK_HEAD, 256);
+  take(TM_POOL_VAL, up256((size_t)k * 8));
+  take(TM_POOL_IDX, up256((size_t)k * 8));
+  take(TM_LIST_VAL, up256((size_t)T.sweep.C * 8));
+  take(TM_LIST_IDX, up256((size_t)T.sweep.C * 8));
+  take(TM_SCORES, up256((size_t)m * 8));
+  take(TM_SORT_WS, up256(sort_bytes));
+  T.total = reported;
+  return T;
+}
+
 }  // namespace gpx

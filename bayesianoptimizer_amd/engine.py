@@ -615,9 +615,9 @@ class GPEngine:
         return val, idx
 
     def sweep_stats(self):
-        """Work counters of the last `acquire` / `acquire_topk` call (synchronises the stream): (candidates seen,
-        candidates whose variance product was computed to its last row tile, 128x128 product tiles executed, tiles of
-        the full sweep)."""
+        """Work counters of the last `acquire` / `acquire_topk` / `acquire_topk_multi` call (synchronises the stream):
+        (candidates seen, candidates whose variance product was computed to its last row tile (of every output),
+        128x128 product tiles executed (summed over the outputs), tiles of the full sweep)."""
         out = (ctypes.c_int64 * 4)()
         self._check(self.lib.gpx_sweep_stats(self.handle, out))
         return tuple(int(v) for v in out)
@@ -630,6 +630,26 @@ class GPEngine:
         (gpx_acquire_argmax_multi_f64: mean sum_t w_t (y_mean_t + y_scale_t mu_t), variance sum_t w_t^2 y_scale_t^2
         var_t) and return device scalars (best_value, best_index) (+ scores).  ``kind="variance"`` with unit weights is
         the variance-sum pool-scan score (optimization/Bayesian7.py:671)."""
+        Xs, m, T, st0, ap, pcs, keep, wp, ldw, ap_, cw, cym, cys = self._multi_setup(
+            states, Xs, kind, best_f, beta, weights, y_mean, y_scale)
+        best_val = torch.empty((1,), dtype=torch.float64, device=self.device)
+        best_idx = torch.empty((1,), dtype=torch.int64, device=self.device)
+        scores = torch.empty((m,), dtype=torch.float64, device=self.device) if return_scores else None
+        nbytes = ctypes.c_size_t()
+        self._check(self.lib.gpx_sweep_multi_workspace_size(st0.n, m, ctypes.byref(nbytes)))
+        ws = self.workspace("sweep_multi", nbytes.value)
+        X = st0.X
+        self._bind_stream()
+        self._check(self.lib.gpx_acquire_argmax_multi_f64(
+            self.handle, pcs, T, st0.n, _ptr(X), X.stride(0), wp, ldw, ap_, cw, cym, cys, _ptr(Xs),
+            m, Xs.stride(0), ctypes.byref(ap), int(index_offset), _ptr(best_val), _ptr(best_idx), _ptr(scores),
+            _ptr(ws), ws.numel()))
+        if return_scores:
+            return best_val, best_idx, scores
+        return best_val, best_idx
+
+    def _multi_setup(self, states, Xs, kind, best_f, beta, weights, y_mean, y_scale):
+        """Validation and the host arrays shared by ``acquire_multi`` and ``acquire_topk_multi``."""
         Xs = self._as_f64(Xs, "Xs")
         T = len(states)
         if T < 1:
@@ -653,25 +673,35 @@ class GPEngine:
         ap = AcqParamsC()
         ap.kind, ap.best_f, ap.beta, ap.y_mean, ap.y_scale = kid, float(best_f), float(beta), 0.0, 1.0
         pcs = (KernelParamsC * T)(*[st.params.to_c(d) for st in states])
-        best_val = torch.empty((1,), dtype=torch.float64, device=self.device)
-        best_idx = torch.empty((1,), dtype=torch.int64, device=self.device)
-        scores = torch.empty((m,), dtype=torch.float64, device=self.device) if return_scores else None
-        nbytes = ctypes.c_size_t()
-        self._check(self.lib.gpx_sweep_multi_workspace_size(states[0].n, m, ctypes.byref(nbytes)))
-        ws = self.workspace("sweep_multi", nbytes.value)
-        X = st0.X
-        alphas = [st.alpha[:, 0].contiguous() for st in states]  # keeps the columns alive across the call
+        alphas = [st.alpha[:, 0].contiguous() for st in states]  # the caller keeps the columns alive across the call
         wp = (ctypes.c_void_p * T)(*[st.W.data_ptr() for st in states])
         ldw = (ctypes.c_int64 * T)(*[st.W.stride(0) for st in states])
         ap_ = (ctypes.c_void_p * T)(*[a.data_ptr() for a in alphas])
+        return (Xs, m, T, st0, ap, pcs, alphas, wp, ldw, ap_, (ctypes.c_double * T)(*w), (ctypes.c_double * T)(*ym),
+                (ctypes.c_double * T)(*ys))
+
+    def acquire_topk_multi(self, states: Sequence[GPState], Xs, k: int, kind: Union[str, int] = "logei",
+                           best_f: float = 0.0, beta: float = 4.0, weights: Optional[Sequence[float]] = None,
+                           y_mean: Optional[Sequence[float]] = None, y_scale: Optional[Sequence[float]] = None,
+                           index_offset: int = 0):
+        """The k best candidates of ``acquire_multi``'s objective as device tensors (values[k], indices[k]): what
+        ``acquire_multi(return_scores=True)`` followed by ``topk(scores, k)`` gives (descending, ties -> lower index
+        first), through the pruned multi-output sweep where it applies (gpx_acquire_topk_multi_f64;
+        1 <= k <= min(m, GPX_TOPK_SWEEP_MAX)).  ``sweep_stats()`` reports for it."""
+        Xs, m, T, st0, ap, pcs, keep, wp, ldw, ap_, cw, cym, cys = self._multi_setup(
+            states, Xs, kind, best_f, beta, weights, y_mean, y_scale)
+        k = int(k)
+        nbytes = ctypes.c_size_t()
+        self._check(self.lib.gpx_acquire_topk_multi_workspace_size(st0.n, m, k, ctypes.byref(nbytes)))
+        val = torch.empty((k,), dtype=torch.float64, device=self.device)
+        idx = torch.empty((k,), dtype=torch.int64, device=self.device)
+        ws = self.workspace("sweep_multi", nbytes.value)
+        X = st0.X
         self._bind_stream()
-        self._check(self.lib.gpx_acquire_argmax_multi_f64(
-            self.handle, pcs, T, st0.n, _ptr(X), X.stride(0), wp, ldw, ap_, (ctypes.c_double * T)(*w), (ctypes.c_double * T)(*ym), (ctypes.c_double * T)(*ys), _ptr(Xs),
-            m, Xs.stride(0), ctypes.byref(ap), int(index_offset), _ptr(best_val), _ptr(best_idx), _ptr(scores),
-            _ptr(ws), ws.numel()))
-        if return_scores:
-            return best_val, best_idx, scores
-        return best_val, best_idx
+        self._check(self.lib.gpx_acquire_topk_multi_f64(
+            self.handle, pcs, T, st0.n, _ptr(X), X.stride(0), wp, ldw, ap_, cw, cym, cys, _ptr(Xs), m, Xs.stride(0),
+            ctypes.byref(ap), int(index_offset), k, _ptr(val), _ptr(idx), _ptr(ws), ws.numel()))
+        return val, idx
 
     def moments_grad(self, state: GPState, Xs, q: int = 1, alpha: Optional[torch.Tensor] = None):
         """Posterior mean / q-batch covariance of candidates Xs (m x d, consecutive q-batches) and their derivatives

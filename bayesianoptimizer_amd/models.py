@@ -302,13 +302,21 @@ class ExactGP:
         """The k best candidates of ``sweep_objective`` as (values[k], indices[k]), descending, ties -> lower index
         first; indices are index_offset + the row of X.  Outputs that share the factor take one
         ``GPEngine.acquire_topk`` with the combined alpha (the pruned sweep with the k-th best exact score as its
-        incumbent) when the engine has it and k <= GPX_TOPK_SWEEP_MAX; everything else composes the full sweep with
-        scores and ``topk``."""
+        incumbent) when the engine has it and k <= GPX_TOPK_SWEEP_MAX, independent outputs one
+        ``GPEngine.acquire_topk_multi`` (the pruned multi-output sweep: per-output variance bounds summed before the
+        bound pass) under the same conditions; everything else composes the full sweep with scores and ``topk``."""
         from ._capi import GPX_TOPK_SWEEP_MAX
 
         if not self.fitted:
             self.fit()
         k = int(k)
+        if self.independent and hasattr(self.engine, "acquire_topk_multi") and 1 <= k <= GPX_TOPK_SWEEP_MAX:
+            ym, ys = self._untransform()
+            w = [float(v) for v in weights]
+            if len(w) != self.num_outputs:
+                raise ValueError(f"expected {self.num_outputs} objective weights, got {len(w)}")
+            return self.engine.acquire_topk_multi(self.states, X, k, kind, best_f=best_f, beta=beta, weights=w,
+                                                  y_mean=ym, y_scale=ys, index_offset=index_offset)
         if not self.independent and hasattr(self.engine, "acquire_topk") and 1 <= k <= GPX_TOPK_SWEEP_MAX:
             ym, ys = self._untransform()
             w = [float(v) for v in weights]

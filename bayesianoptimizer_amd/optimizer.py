@@ -491,8 +491,8 @@ class BayesianOptimizer:
     def _analytic_sweep(self, k: int) -> torch.Tensor:
         """Sobol grid scored on the objective sum_t w_t f_t of the modelled outputs (ExactGP.sweep_objective: the
         combined alpha of one shared factorisation, or the multi-output sweep over independent outputs), best k by
-        ExactGP.sweep_objective_topk: the pruned top-k sweep for a shared factorisation, else the full sweep and
-        gpx_topk_f64."""
+        ExactGP.sweep_objective_topk: the pruned top-k sweep (gpx_acquire_topk_f64 for a shared factorisation,
+        gpx_acquire_topk_multi_f64 over independent outputs), else the full sweep and gpx_topk_f64."""
         gp = self.gp_model
         grid = self._tensor(self._sobol_grid(self.config.raw_samples))
         w = self._acq_weights()

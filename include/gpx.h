@@ -324,7 +324,8 @@ gpx_status gpx_acquire_argmax_f64(gpx_handle h, const gpx_kernel_params* p, int6
                                   const double* Xs, int64_t m, int64_t ldxs, const gpx_acq_params* a,
                                   int64_t index_offset, double* best_val, int64_t* best_idx,
                                   double* scores_out, void* ws, size_t ws_bytes);
-/* Work counters of the handle's last sweep, a gpx_acquire_argmax_f64 or gpx_acquire_topk_f64 call (synchronises the
+/* Work counters of the handle's last sweep, a gpx_acquire_argmax_f64, gpx_acquire_topk_f64 or
+ * gpx_acquire_topk_multi_f64 call (the last one's meanings: at its declaration below) (synchronises the
  * handle's stream; the workspace of that call must still be allocated): out_host[0] candidates seen, [1] candidates
  * whose last 128-row tile of the variance product was computed, [2] 128 x 128 product tiles executed, [3] the tiles the
  * full sweep executes (0 / 0 on the fused small-n path, which has no tiles). */
@@ -371,6 +372,36 @@ gpx_status gpx_acquire_argmax_multi_f64(gpx_handle h, const gpx_kernel_params* p
                                         int64_t m, int64_t ldxs, const gpx_acq_params* a, int64_t index_offset,
                                         double* best_val, int64_t* best_idx, double* scores_out, void* ws,
                                         size_t ws_bytes);
+
+/* The k best candidates of the multi-output sweep above without the full sweep: val_out / idx_out (device, k each) hold
+ * exactly what gpx_acquire_argmax_multi_f64 with scores_out = S followed by gpx_topk_f64(S, m, k) and the index shift
+ * gives (descending, equal scores with the lower index first, NaN as -inf, -0 as +0, the bits of the full sweep's
+ * scores); k = 1 is gpx_acquire_argmax_multi_f64's pair after that keying, and T = 1 with w = 1 gives
+ * gpx_acquire_topk_f64's bits.  Arguments and validation as gpx_acquire_argmax_multi_f64, plus
+ * 1 <= k <= min(m, GPX_TOPK_SWEEP_MAX).
+ * The pruned form runs where GPX_OPT_SWEEP_PRUNE admits it (unfused path, padded n at or above its threshold) and every
+ * output has the fp64 covariance build and d <= 16.  The objective's variance sum_t w_t^2 y_scale[t]^2 var_t has
+ * non-negative terms and each var_t can only shrink as row tiles of its product are added, so the variance summed from
+ * the first 128-row tile of every output is an upper bound of the exact one (in floating point too: rounded sums, fmax
+ * and products with a non-negative constant are monotone); the mean is computed exactly, and every acquisition is
+ * non-decreasing in the variance.  A candidate whose bound lies below the k-th best score computed in full so far is
+ * dropped; the others get the full product of every output.  Elsewhere (GPX_OPT_SWEEP_PRUNE = 0, padded n < 384, the
+ * fused small-n sweep, cov_fp32, d > 16) the call runs the full multi-output sweep into a score array of its own
+ * workspace and gpx_topk_f64's sort.  Asynchronous on the handle's stream, no allocation, no host synchronisation, the
+ * same bits on every call.
+ * gpx_sweep_stats after this call: [0] candidates seen, [1] candidates whose product was computed to the last row tile
+ * for every output, [2] 128 x 128 product tiles executed, summed over the outputs, [3] the tiles of the full
+ * multi-output sweep (T times the single sweep's; the fused path has none).
+ * gpx_acquire_topk_multi_workspace_size: gpx_sweep_multi_workspace_size(n, m) plus the top-k part of
+ * gpx_acquire_topk_workspace_size. */
+gpx_status gpx_acquire_topk_multi_workspace_size(int64_t n, int64_t m, int64_t k, size_t* bytes);
+gpx_status gpx_acquire_topk_multi_f64(gpx_handle h, const gpx_kernel_params* p, int64_t T, int64_t n, const double* X,
+                                      int64_t ldx, const double* const* W_host, const int64_t* ldw_host,
+                                      const double* const* alpha_host, const double* weights_host,
+                                      const double* y_mean_host, const double* y_scale_host, const double* Xs,
+                                      int64_t m, int64_t ldxs, const gpx_acq_params* a, int64_t index_offset, int64_t k,
+                                      double* val_out /* k, device */, int64_t* idx_out /* k, device */, void* ws,
+                                      size_t ws_bytes);
 
 /* Deterministic (value, index) reduction of `count` device records: max value, then lowest index; NaN
  * never wins.  Used after the cross-GPU all-gather of per-rank records. */
