@@ -201,8 +201,10 @@ __global__ void __launch_bounds__(WG) kstar_kernel(gpx_kernel_params p, int n, c
 //  KSTAR_GATHER  the pruned sweep's tail: column s of the output is candidate list[first + s] for s below the round's
 //                column count min(*count - first, cap) (clamped at 0), zero up to the end of the workgroup's 256 columns;
 //                mean partials only on request (aux.mu_out: KSTAR_FULL's bits, stored at the listed candidate's own
-//                place); workgroups beyond the count return at once.  Workgroup (0, 0) also writes the round's
-//                first descriptor and resets its survivor counts (read by later launches only).
+//                place).  The grid is one-dimensional and bounded (tail_grid): its workgroups stride over the live
+//                (column block, row block) units, column block fastest, so an empty round costs that bounded grid
+//                of workgroups that read the count and return.  Workgroup 0 also writes the round's first descriptor
+//                and resets its survivor counts (read by later launches only), once, before its first unit.
 constexpr int KSTAR_FULL = 0, KSTAR_MU = 1, KSTAR_GATHER = 2;
 struct KstarAux {
   int jb0;           // MU: first row block of the launch
@@ -210,6 +212,7 @@ struct KstarAux {
   int lstride;
   const int* count;  // GATHER: entries in the list (device)
   int first, cap;    // GATHER: this round's entries first .. first + cap - 1
+  int nrb;           // GATHER: row blocks of the launch (set by launch_kstar)
   int* pad;          // GATHER, optional: the list again, to mark the last tile's padding slots with -1
   PruneDesc* desc;   // GATHER, optional: the round's first descriptor
   int* rcount;       // its stages' survivor counts (PRUNE_MAX_STAGES - 1 of them)
@@ -219,12 +222,14 @@ struct KstarAux {
   int64_t ldmu;      //   mu_out[jb * ldmu + candidate]; alpha is read only then
 };
 
+// One workgroup's unit of kstar_mfma_kernel: row block jb x the 256 columns from c0 on.  GATHER: nr columns in the
+// round, ntl tiles.
 template <int DMAX, int KIND, bool ONE_RHS, int MODE>
-__global__ void __launch_bounds__(WG) kstar_mfma_kernel(gpx_kernel_params p, int n, const double* __restrict__ X,
-                                                        int64_t ldx, const double* __restrict__ alpha, int nrhs,
-                                                        const double* __restrict__ Xs, int64_t ldxs, int64_t m_chunk,
-                                                        int64_t C, double* __restrict__ kstar,
-                                                        double* __restrict__ mu_part, KstarAux aux) {
+__device__ __forceinline__ void kstar_mfma_unit(const gpx_kernel_params& p, int n, const double* __restrict__ X,
+                                                int64_t ldx, const double* __restrict__ alpha, int nrhs,
+                                                const double* __restrict__ Xs, int64_t ldxs, int64_t m_chunk,
+                                                int64_t C, double* __restrict__ kstar, double* __restrict__ mu_part,
+                                                const KstarAux& aux, int jb, int64_t c0, int nr, int ntl) {
   constexpr bool lin = (KIND == GPX_KERNEL_SCALE_LINEAR_MATERN52);
   constexpr bool gather = MODE == KSTAR_GATHER;
   constexpr int KS = DMAX / 4;
@@ -232,30 +237,16 @@ __global__ void __launch_bounds__(WG) kstar_mfma_kernel(gpx_kernel_params p, int
   __shared__ double sa[NB][DMAX + 1], sb[WG][DMAX + 1], ra[lin ? NB : 1][DMAX + 1], rb[lin ? WG : 1][DMAX + 1];
   __shared__ double na[NB], nb[WG], cen[DMAX], sal[NB][NRQ];
   __shared__ int sidx[gather ? WG : 1];
-  const int jb = MODE == KSTAR_MU ? (int)blockIdx.y + aux.jb0 : (int)blockIdx.y, j0 = jb * NB, d = p.d, t = threadIdx.x;
-  const int64_t c0 = (int64_t)blockIdx.x * WG;
+  const int j0 = jb * NB, d = p.d;
+  int t = threadIdx.x;
+  // (GATHER runs this body in a loop: an opaque thread index keeps the compiler from hoisting every address that
+  // depends on it out of the loop, which cost the d = 8 instance its fourth wave per SIMD)
+  if constexpr (gather) asm volatile("" : "+v"(t));
   const int nv = n - j0 < NB ? n - j0 : NB;  // valid training rows of the block (<= 0: all padding)
   if constexpr (gather) {
-    const int left = *aux.count - aux.first;
-    const int nr = left < 0 ? 0 : left < aux.cap ? left : aux.cap;
-    const int ntl = (nr + 127) / 128;
-    if (blockIdx.x == 0 && blockIdx.y == 0 && t == 0 && aux.desc) {
-      PruneDesc o;
-      o.buf = 0;
-      o.col0 = 0;
-      o.ncols = nr;
-      o.ntiles = ntl;
-      o.list = 2;
-      o.pad[0] = o.pad[1] = o.pad[2] = 0;
-      *aux.desc = o;
-      for (int s = 0; s < PRUNE_MAX_STAGES - 1; ++s) aux.rcount[s] = 0;
-      aux.stats[1] += (int64_t)ntl * aux.rows0;
-      if (aux.last) aux.stats[0] += nr;
-    }
-    if (c0 >= nr) return;
     const int slot = (int)c0 + t;
     sidx[t] = slot < nr ? aux.list[(int64_t)(aux.first + slot) * aux.lstride] : -1;
-    if (aux.pad && blockIdx.y == 0 && slot >= nr && slot < ntl * 128)
+    if (aux.pad && jb == 0 && slot >= nr && slot < ntl * 128)
       aux.pad[(int64_t)(aux.first + slot) * aux.lstride] = -1;
     __syncthreads();
   }
@@ -376,6 +367,42 @@ __global__ void __launch_bounds__(WG) kstar_mfma_kernel(gpx_kernel_params p, int
       v += __shfl_xor(v, 32);
       if (kq == 0 && q < nrhs) mu_part[((int64_t)jb * nrhs + q) * C + c0 + 64 * w + 16 * cb + m] = v;
     }
+}
+
+template <int DMAX, int KIND, bool ONE_RHS, int MODE>
+__global__ void __launch_bounds__(WG) kstar_mfma_kernel(gpx_kernel_params p, int n, const double* __restrict__ X,
+                                                        int64_t ldx, const double* __restrict__ alpha, int nrhs,
+                                                        const double* __restrict__ Xs, int64_t ldxs, int64_t m_chunk,
+                                                        int64_t C, double* __restrict__ kstar,
+                                                        double* __restrict__ mu_part, KstarAux aux) {
+  if constexpr (MODE != KSTAR_GATHER) {
+    const int jb = MODE == KSTAR_MU ? (int)blockIdx.y + aux.jb0 : (int)blockIdx.y;
+    kstar_mfma_unit<DMAX, KIND, ONE_RHS, MODE>(p, n, X, ldx, alpha, nrhs, Xs, ldxs, m_chunk, C, kstar, mu_part, aux, jb,
+                                               (int64_t)blockIdx.x * WG, 0, 0);
+  } else {
+    const int left = *aux.count - aux.first;
+    const int nr = left < 0 ? 0 : left < aux.cap ? left : aux.cap;
+    const int ntl = (nr + 127) / 128;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && aux.desc) {
+      PruneDesc o;
+      o.buf = 0;
+      o.col0 = 0;
+      o.ncols = nr;
+      o.ntiles = ntl;
+      o.list = 2;
+      o.pad[0] = o.pad[1] = o.pad[2] = 0;
+      *aux.desc = o;
+      for (int s = 0; s < PRUNE_MAX_STAGES - 1; ++s) aux.rcount[s] = 0;
+      aux.stats[1] += (int64_t)ntl * aux.rows0;
+      if (aux.last) aux.stats[0] += nr;
+    }
+    const int ncb = (nr + WG - 1) / WG, units = ncb * aux.nrb;
+    for (int u = blockIdx.x; u < units; u += gridDim.x) {
+      if (u != (int)blockIdx.x) __syncthreads();  // the unit before this one has read its LDS image to the end
+      kstar_mfma_unit<DMAX, KIND, ONE_RHS, MODE>(p, n, X, ldx, alpha, nrhs, Xs, ldxs, m_chunk, C, kstar, mu_part, aux,
+                                                 u / ncb, (int64_t)(u % ncb) * WG, nr, ntl);
+    }
+  }
 }
 
 // ---- 2. triangular product + column sums of squares ------------------------------------------------------
@@ -1047,17 +1074,20 @@ __global__ void prune_init_kernel(PruneDesc* __restrict__ desc, int* __restrict_
 // with zero columns whose list entry is -1), else the next stage keeps the buffer and the columns it has: the copy
 // traffic stays below the K* it replaces, and an unprunable chunk pays only the bound passes.  Every workgroup takes
 // the same decision from what earlier launches wrote; thread 0 of workgroup (0, 0) writes the next descriptor (read by
-// later launches only) and the counters.  Workgroup (x, y): slots 256 x .., rows rows_per_wg * y ...
+// later launches only) and the counters.  The grid is one-dimensional and bounded (tail_grid; at least a workgroup per
+// 256 slots of the set's capacity), and the workgroups divide the live work among themselves: with nx blocks of 256
+// slots to move, each block's npad rows are split evenly over gridDim.x / nx workgroups (down to min_rows rows each),
+// so a small set is copied by as many workgroups as a large one and an empty launch costs its bounded grid.
 __global__ void __launch_bounds__(WG) prune_compact_kernel(PruneBufs pb, const PruneDesc* __restrict__ din,
                                                            PruneDesc* __restrict__ dout,
-                                                           const int* __restrict__ count, int rows_per_wg,
+                                                           const int* __restrict__ count, int npad, int min_rows,
                                                            int next_rows, int last, int64_t* __restrict__ stats) {
   const PruneDesc d = *din;
   const int surv = *count;
   const bool compact = 2 * (int64_t)surv <= d.ncols;
   const int ntl = (surv + TT - 1) / TT;
   const int out_list = d.list == 0 ? 1 : 0;
-  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
     PruneDesc o = d;
     if (compact) {
       o.buf = d.buf == 1 ? 2 : 1;
@@ -1070,20 +1100,24 @@ __global__ void __launch_bounds__(WG) prune_compact_kernel(PruneBufs pb, const P
     stats[1] += (int64_t)o.ntiles * next_rows;
     if (last) stats[0] += o.ncols;
   }
-  if (!compact) return;
-  const int slot = blockIdx.x * WG + threadIdx.x;
-  if (slot >= ntl * TT) return;
+  if (!compact || ntl == 0) return;
   int2* list = out_list ? pb.list1 : pb.list0;
   const double* src = d.buf == 0 ? pb.kstar : d.buf == 1 ? pb.c1 : pb.c2;
   const int64_t lds = d.buf == 0 ? pb.ld0 : d.buf == 1 ? pb.ld1 : pb.ld2;
   double* dst = d.buf == 1 ? pb.c2 : pb.c1;
   const int64_t ldd = d.buf == 1 ? pb.ld2 : pb.ld1;
+  const int nx = (ntl * TT + WG - 1) / WG;
+  int per = (int)gridDim.x / nx;  // workgroups per block of slots (the grid has one per block at least)
+  per = per > npad / min_rows ? npad / min_rows : per;
+  const int slot = ((int)blockIdx.x / per) * WG + threadIdx.x, y = (int)blockIdx.x % per;
+  if (slot >= ntl * TT) return;
   const bool real = slot < surv;
-  if (!real && blockIdx.y == 0) list[slot] = make_int2(-1, 0);
+  if (!real && y == 0) list[slot] = make_int2(-1, 0);
   const int64_t sc = real ? d.col0 + list[slot].y : 0;
-  const int r0 = blockIdx.y * rows_per_wg;
+  const int r1 = (int)((int64_t)(y + 1) * npad / per);
 #pragma unroll 8
-  for (int r = r0; r < r0 + rows_per_wg; ++r) dst[(int64_t)r * ldd + slot] = real ? src[(int64_t)r * lds + sc] : 0.0;
+  for (int r = (int)((int64_t)y * npad / per); r < r1; ++r)
+    dst[(int64_t)r * ldd + slot] = real ? src[(int64_t)r * lds + sc] : 0.0;
 }
 
 // records e = 0 .. count-1 at vals[e * stride] / idx[e * stride] (stride 1: separate arrays; 2: packed 16-byte
@@ -1297,16 +1331,38 @@ bool sweep_prune_ok(const Context* c, const gpx_kernel_params& p, int npad) {
   return npad >= (c->sweep_prune != 1 ? PRUNE_MIN_NPAD : PRUNE_DEFAULT_NPAD);  // (-2: forced, exact head means)
 }
 
+static int sweep_cu_count(Context* c) {
+  if (c->cu_count <= 0) {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) == hipSuccess &&
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
+      c->cu_count = cus;
+  }
+  return c->cu_count > 0 ? c->cu_count : 0;  // (unknown: the wide shape throughout)
+}
+
+// The grid of a tail launch whose work only the device knows (the gather, the compaction): `units` workgroups would
+// cover the round's capacity, but a round is mostly far below it and often empty, and an empty launch costs its grid
+// (DESIGN §5).  So at most per_cu workgroups per CU are launched, a small multiple of what the device holds at once,
+// and divide the live work among themselves.  Unknown residency or CU count: `units`.
+static unsigned tail_grid(Context* c, int per_cu, int64_t units) {
+  const int64_t bound = (int64_t)per_cu * sweep_cu_count(c);
+  return (unsigned)(bound > 0 && bound < units ? bound : units);
+}
+
 // K* and the partial means of one chunk (launch 1 of the file comment)
 static void launch_kstar(const SweepModel& M, const SweepCands& q, const SweepBuffers& b, int mode = KSTAR_FULL,
-                         const KstarAux& aux = KstarAux{}, int rows = 0) {
+                         const KstarAux& aux_in = KstarAux{}, int rows = 0) {
   if (rows == 0) rows = M.npad;  // (KSTAR_FULL over the leading `rows` rows only: the head phase)
   LaunchTimer tm(M.c, GPX_TIMER_KSTAR);
   const gpx_kernel_params& p = M.p;
   const int64_t C = b.chunk;
   hipStream_t stream = M.c->stream;
-  // (KSTAR_GATHER: q.m is the most columns the round can have; the kernel reads the count itself)
+  // (KSTAR_GATHER: q.m is the most columns the round can have; the kernel reads the count itself and its workgroups
+  // stride over the live (column block, row block) units)
   const dim3 g((unsigned)((q.m + WG - 1) / WG), (mode == KSTAR_MU ? M.npad - PRUNE_HEAD_ROWS : rows) / NB);
+  KstarAux aux = aux_in;
+  aux.nrb = (int)g.y;
   with_dmax(p.d, [&](auto D) {
     constexpr int DM = decltype(D)::value;
     auto diff = [&](auto F32) {  // the difference form
@@ -1325,8 +1381,19 @@ static void launch_kstar(const SweepModel& M, const SweepCands& q, const SweepBu
     } else {
       with_kind(p.kind, [&](auto K) {
         auto mfma = [&](auto ONE, auto MODE) {
-          kstar_mfma_kernel<DM, decltype(K)::value, decltype(ONE)::value, decltype(MODE)::value>
-              <<<g, WG, 0, stream>>>(p, M.n, M.X, M.ldx, M.alpha, M.nrhs, q.Xs, q.ldxs, q.m, C, b.kstar, b.mu_part, aux);
+          auto kernel = kstar_mfma_kernel<DM, decltype(K)::value, decltype(ONE)::value, decltype(MODE)::value>;
+          dim3 grid = g;
+          if constexpr (decltype(MODE)::value == KSTAR_GATHER) {
+            static const int resident = [&] {  // workgroups of this instance a CU holds (registers, LDS); 0: unknown
+              int r = 0;
+              return hipOccupancyMaxActiveBlocksPerMultiprocessor(&r, kernel, WG, 0) == hipSuccess ? r : 0;
+            }();
+            // twice the resident workgroups: with exactly one wave of them every workgroup of a full round runs its
+            // trips in step with the others, and the unprunable case measured 0.4 % slower than with this
+            grid = dim3(tail_grid(M.c, 2 * resident, (int64_t)g.x * g.y));
+          }
+          kernel<<<grid, WG, 0, stream>>>(p, M.n, M.X, M.ldx, M.alpha, M.nrhs, q.Xs, q.ldxs, q.m, C, b.kstar, b.mu_part,
+                                          aux);
         };
         M.nrhs != 1          ? mfma(std::false_type{}, Const<KSTAR_FULL>{})
         : mode == KSTAR_FULL ? mfma(std::true_type{}, Const<KSTAR_FULL>{})
@@ -1436,16 +1503,6 @@ static int prune_stage_bounds(int nI, int* R) {
   return S;
 }
 
-static int sweep_cu_count(Context* c) {
-  if (c->cu_count <= 0) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
-      c->cu_count = cus;
-  }
-  return c->cu_count > 0 ? c->cu_count : 0;  // (unknown: the wide shape throughout)
-}
-
 // A stage after the first of a chunk, super-chunk or round: `tiles` wide tiles at most, how many are active only the
 // device knows.  One launch of the dual kernel; its workgroups take the narrow shape when the stage's wide tiles would
 // not give every CU one (trmm_sumsq_body).  The grid is the larger of the two shapes' needs: the narrow shape runs
@@ -1544,8 +1601,11 @@ static void launch_stages(const SweepModel& M, const SweepCands& q, const PruneS
   sel.tau = ps.tau;
   {
     LaunchTimer tm(c, GPX_TIMER_TRMM);
-    constexpr int ROWS = 32;  // K* rows a compaction workgroup copies
-    const dim3 gc((sg.cap / 2 + TT + WG - 1) / WG, M.npad / ROWS);
+    // compaction: a workgroup per 256 slots x 32 rows of the set's capacity at most and per 256 slots at least (no
+    // more than the 8 per CU the device holds otherwise); a workgroup copies ROWS rows at least
+    const unsigned nsb = (unsigned)((sg.cap / 2 + TT + WG - 1) / WG);
+    const unsigned gc = std::max(tail_grid(c, 8, (int64_t)nsb * (M.npad / 32)), nsb);
+    constexpr int ROWS = 8;
     for (int s = 0; s < sg.ns; ++s) {
       const PruneStage st{sg.pb, desc + s, sg.R[s], sg.R[s + 1] - sg.R[s], 0};
       if (s == 0 && sg.wide_first)
@@ -1558,7 +1618,7 @@ static void launch_stages(const SweepModel& M, const SweepCands& q, const PruneS
       finalize_kernel<<<blocks, WG, 0, c->stream>>>(fa, 4, q.Xs, q.ldxs, q.m, sg.pitch, 1, nJB, sg.R[s + 1], sg.mu_part,
                                                     sg.ss_part, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
                                                     q.index_offset, sel);
-      prune_compact_kernel<<<gc, WG, 0, c->stream>>>(sg.pb, desc + s, desc + s + 1, count + s, ROWS,
+      prune_compact_kernel<<<gc, WG, 0, c->stream>>>(sg.pb, desc + s, desc + s + 1, count + s, M.npad, ROWS,
                                                      sg.R[s + 2] - sg.R[s + 1], s + 2 == sg.ns, ps.stats);
     }
   }

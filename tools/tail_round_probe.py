@@ -1,0 +1,51 @@
+"""The columns the live tail rounds of the lazy pruned sweep handle, read from the stage descriptors and
+survivor counts a call leaves in its workspace (gpx_sweep_layout.h: SR_DESC, SR_COUNT behind the main part).
+
+A call's first span is one chunk long and has one tail round, so a call over the first chunk's candidates alone leaves
+that round's descriptors (slot 1: the gather's set, then one per compaction: buf, col0, ncols, ntiles, list) and the
+survivors after every stage (count[0]: the head's).  After the whole call the later rounds have overwritten them, but
+count[0] is still the last span's head survivors, and sweep_stats[1] - 1024 - the first round's last set is what the
+last span computed to the end.  One JSON line per case.  The library is the tree's, or GPX_LIB's.
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+from bayesianoptimizer_amd import GPEngine, KernelParams, botorch_default_lengthscale, synthetic
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--seeds", default="0,1000")
+a = ap.parse_args()
+D, M, N = 8, 1 << 20, 4096
+dev = torch.device("cuda", 0)
+eng = GPEngine(0)
+kp = KernelParams("rbf", botorch_default_lengthscale(D), noise=1e-4)
+
+
+def workspace_state(npad, m):
+    ws = eng._ws["sweep"]
+    cap = ((1 << 30) // 8 // npad) // 256 * 256
+    C = min((m + 255) // 256 * 256, cap)
+    nrec = (m + 255) // 256 + 1
+    main = npad * C * 8 + (npad // 64) * C * 8 + (npad // 128) * C * 8 + 2 * nrec * 8
+    at = (-ws.data_ptr()) % 256 + (main + 255) // 256 * 256
+    torch.cuda.synchronize()
+    return (ws[at:at + 256].view(torch.int32).reshape(8, 8)[:, :5].tolist(),
+            ws[at + 256:at + 288].view(torch.int32).tolist())
+
+
+for seed in (int(s) for s in a.seeds.split(",")):
+    X, y = synthetic.problem(N, D, seed)
+    st = eng.fit(torch.tensor(X, device=dev), torch.tensor(y, device=dev), kp)
+    Xs = torch.tensor(synthetic.sobol(M, D, seed + 1), device=dev)
+    npad = st.npad
+    C = ((1 << 30) // 8 // npad) // 256 * 256
+    for name, m in (("first_chunk", C), ("whole_call", M)):
+        bv, bi = eng.acquire(st, Xs[:m], "logei", best_f=float(y.max()))
+        stats = eng.sweep_stats()
+        desc, count = workspace_state(npad, m)
+        print(json.dumps({"case": f"seed{seed}_{name}", "m": m, "sweep_stats": list(stats), "best": int(bi.item()),
+                          "descriptors": desc[:7], "counts": count[:7]}), flush=True)
