@@ -46,6 +46,11 @@ TIMERS = {"gram": 0, "potrf": 1, "trtri": 2, "alpha": 3, "kstar": 4, "trmm": 5, 
 MLL_NLL, MLL_QUAD, MLL_LOGDET, MLL_D_NOISE, MLL_D_OUTPUTSCALE, MLL_D_MEAN = 0, 1, 2, 3, 4, 5
 MLL_D_LENGTHSCALE, MLL_D_LINVAR, MLL_NOUT = 8, 40, 72
 
+# gpx_svgp_fit_collapsed_f64 bound layout (include/gpx.h GPX_SVGP_BOUND_*): F, then its five terms
+SVGP_BOUND_F, SVGP_BOUND_CONST, SVGP_BOUND_LOGDET, SVGP_BOUND_QUAD, SVGP_BOUND_FIT, SVGP_BOUND_TRACE = 0, 1, 2, 3, 4, 5
+SVGP_BOUND_NOUT = 6
+SVGP_FIT_CHUNK = 4096  # GPX_SVGP_FIT_CHUNK: the default chunk width
+
 
 class GPXLibraryError(RuntimeError):
     """libgpx.so is missing or failed to load (the HIP path is required; there is no fallback)."""
@@ -243,6 +248,10 @@ _PROTOS = {
     "gpx_svgp_predict_f64": (c_int32, [_h, POINTER(KernelParamsC), c_int64, c_int64, _p, c_int64, c_int64, _p, _p,
                                        _p, _p, c_int64, c_int64, c_double, _p, c_int64, _p, c_int64, _p, _p,
                                        c_size_t]),
+    "gpx_svgp_fit_collapsed_workspace_size": (c_int32, [c_int64, c_int64, c_int64, c_int64, POINTER(c_size_t)]),
+    "gpx_svgp_fit_collapsed_f64": (c_int32, [_h, POINTER(KernelParamsC), c_int64, c_int64, c_double, _p, c_int64,
+                                             c_int64, _p, c_int64, c_int64, _p, c_int64, _p, c_int64, _p, c_int64,
+                                             c_int64, _p, _p, _p, c_size_t]),
     "gpx_topk_workspace_size": (c_int32, [c_int64, POINTER(c_size_t)]),
     "gpx_topk_f64": (c_int32, [_h, _p, c_int64, c_int64, _p, _p, _p, c_size_t]),
     "gpx_fps_f64": (c_int32, [_h, _p, c_int64, c_int64, c_int64, c_int64, c_int64, _p]),

@@ -1619,6 +1619,176 @@ gpx_status gpx_svgp_predict_f64(gpx_handle h, const gpx_kernel_params* p, int64_
   return GPX_OK;
 }
 
+// ---- SVGP variational posterior in closed form (gpx_svgpfit.hip) --------------------------------------
+namespace {
+// Per task: A (K_ZZ, then its factor, then B_acc / B' / L'), Wb (W = L_ZZ^{-T}, then W' = L'^{-T}), the diagonal-block
+// inverses, the triangular inverse's scratch, and the vectors b', u, m' with the three scalar sums.  By chunk width: the
+// covariance chunk (Mpad x ldk, shared), one projected chunk per task (the tasks' rank updates share a launch), the K*
+// build's mean partials (unused) and the chunk's residual.  Besides: a zero vector standing in for that build's alpha
+// and the second factorisation's info words.
+struct SvgpFitLayout {
+  size_t A, Wb, dinv, slice, bvec, u, mrev, scal, task;      // per task: byte offsets, and the task pitch
+  size_t kc, phi, phi_task, mu, zero, r, info2, total;       // shared: byte offsets from the base (phi_task: its pitch)
+  int64_t ldk;
+};
+int64_t up128(int64_t v) { return (v + 127) / 128 * 128; }
+size_t svgp_fit_fixed_bytes(int64_t Mpad, int64_t ntask, SvgpFitLayout* l) {
+  const size_t mat = al256((size_t)Mpad * Mpad * 8), vec = al256((size_t)Mpad * 8);
+  l->A = 0;
+  l->Wb = mat;
+  l->dinv = 2 * mat;
+  l->slice = l->dinv + al256((size_t)2 * (Mpad / gpx::NB) * gpx::NB * gpx::NB * 8);
+  l->bvec = l->slice + al256(trtri_ws(Mpad));
+  l->u = l->bvec + vec;
+  l->mrev = l->u + vec;
+  l->scal = l->mrev + vec;
+  l->task = l->scal + 256;
+  return l->task * (size_t)ntask + vec /* zero */ + al256((size_t)ntask * 4) /* info2 */;
+}
+// bytes of the parts that scale with the chunk width C (a multiple of 128)
+size_t svgp_fit_chunk_bytes(int64_t Mpad, int64_t ntask, int64_t C) {
+  const size_t ldk = (size_t)((C + 255) / 256 * 256);
+  return (size_t)(1 + ntask) * al256((size_t)Mpad * ldk * 8) + al256((size_t)(Mpad / gpx::NB) * ldk * 8) +
+         al256(ldk * 8);
+}
+SvgpFitLayout svgp_fit_layout(int64_t Mpad, int64_t ntask, int64_t C) {
+  SvgpFitLayout l;
+  const size_t fixed = svgp_fit_fixed_bytes(Mpad, ntask, &l);
+  l.ldk = (C + 255) / 256 * 256;
+  l.zero = l.task * (size_t)ntask;
+  l.info2 = l.zero + al256((size_t)Mpad * 8);
+  l.kc = fixed;
+  l.phi_task = al256((size_t)Mpad * l.ldk * 8);
+  l.phi = l.kc + l.phi_task;
+  l.mu = l.phi + l.phi_task * (size_t)ntask;
+  l.r = l.mu + al256((size_t)(Mpad / gpx::NB) * l.ldk * 8);
+  l.total = fixed + svgp_fit_chunk_bytes(Mpad, ntask, C);
+  return l;
+}
+}  // namespace
+
+gpx_status gpx_svgp_fit_collapsed_workspace_size(int64_t M, int64_t n, int64_t ntask, int64_t chunk, size_t* bytes) {
+  if (!bytes || M < 1 || M > 65536 || n < 1 || ntask < 1 || ntask > 64 || chunk < 0 || chunk > ((int64_t)1 << 20))
+    return GPX_INVALID_ARG;
+  int64_t C = chunk == 0 ? GPX_SVGP_FIT_CHUNK : up128(chunk);
+  if (C > up128(n)) C = up128(n);
+  *bytes = svgp_fit_layout(padded(M), ntask, C).total + 256;
+  return GPX_OK;
+}
+
+gpx_status gpx_svgp_fit_collapsed_f64(gpx_handle h, const gpx_kernel_params* p, int64_t ntask, int64_t M, double jitter,
+                                      const double* Z, int64_t ldz, int64_t stride_z, const double* X, int64_t n,
+                                      int64_t ldx, const double* Y, int64_t ldy, double* vmean, int64_t stride_m,
+                                      double* vchol, int64_t ldc, int64_t stride_c, double* bound, int32_t* info,
+                                      void* ws, size_t ws_bytes) {
+  Context* c = reinterpret_cast<Context*>(h);
+  if (!c) return GPX_INVALID_ARG;
+  GPX_TRY(check_svgp(c, p, ntask, M));
+  GPX_NONNULL(c, Z);
+  GPX_NONNULL(c, X);
+  GPX_NONNULL(c, Y);
+  GPX_NONNULL(c, vmean);
+  GPX_NONNULL(c, vchol);
+  GPX_NONNULL(c, bound);
+  GPX_NONNULL(c, info);
+  GPX_NONNULL(c, ws);
+  if (!(jitter >= 0.0)) return fail(c, GPX_INVALID_ARG, "jitter must be non-negative");
+  if (n < 1 || n > ((int64_t)1 << 40)) return fail(c, GPX_INVALID_ARG, "n must be in [1, 2^40]");
+  GPX_TRY(check_ld(c, ldz, p[0].d, "Z", false));
+  GPX_TRY(check_ld(c, ldx, p[0].d, "X", false));
+  GPX_TRY(check_ld(c, ldy, ntask, "Y", false));
+  GPX_TRY(check_ld(c, ldc, M, "chol_variational_covar", false));
+  if (ntask > 1 && (stride_z < M * ldz || stride_m < M || stride_c < M * ldc))
+    return fail(c, GPX_INVALID_ARG, "task strides smaller than one task");
+  for (int64_t t = 0; t < ntask; ++t)
+    if (!(p[t].noise > 0.0)) return fail(c, GPX_INVALID_ARG, "the likelihood noise must be positive");
+  const int64_t Mpad = padded(M);
+  // the chunk width this workspace allows: the largest multiple of 128, at most the default (and the padded n)
+  SvgpFitLayout lay;
+  const size_t fixed = svgp_fit_fixed_bytes(Mpad, ntask, &lay) + 256;
+  int64_t C = GPX_SVGP_FIT_CHUNK < up128(n) ? GPX_SVGP_FIT_CHUNK : up128(n);
+  while (C >= 128 && fixed + svgp_fit_chunk_bytes(Mpad, ntask, C) > ws_bytes) C -= 128;
+  if (C < 128) return fail(c, GPX_INVALID_ARG, "svgp fit workspace too small");
+  lay = svgp_fit_layout(Mpad, ntask, C);
+  GPX_USE_DEVICE(c);
+  char* base = reinterpret_cast<char*>(align256(ws));
+  auto at = [&](int64_t t, size_t off) { return reinterpret_cast<double*>(base + lay.task * t + off); };
+  auto shared = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
+  int32_t* info2 = reinterpret_cast<int32_t*>(base + lay.info2);
+  const int64_t tstride = (int64_t)(lay.task / sizeof(double));
+  GPX_TRY(hip_check(c, hipMemsetAsync(info, 0, sizeof(int32_t) * ntask, c->stream), "memset info"));
+  GPX_TRY(hip_check(c, hipMemsetAsync(info2, 0, sizeof(int32_t) * ntask, c->stream), "memset info"));
+  GPX_TRY(hip_check(c, hipMemsetAsync(shared(lay.zero), 0, (size_t)Mpad * 8, c->stream), "memset"));
+  // W = (chol(K_ZZ + jitter I))^{-T} per task, as gpx_svgp_prepare_f64 builds it
+  for (int64_t t = 0; t < ntask; ++t) {
+    gpx_kernel_params q = p[t];
+    q.noise = 0.0;
+    q.jitter = jitter;
+    GPX_TRY(hip_check(c, gpx::launch_gram(c, q, (int)M, (int)Mpad, Z + t * stride_z, ldz, at(t, lay.A), Mpad), "gram"));
+  }
+  gpx::Batch bt;
+  bt.count = (int)ntask;
+  bt.k = bt.dinv = bt.ws = bt.w = tstride;
+  GPX_TRY(hip_check(c, gpx::launch_potrf(c, (int)Mpad, at(0, lay.A), Mpad, at(0, lay.dinv), info, bt), "potrf"));
+  GPX_TRY(hip_check(c, gpx::launch_trtri(c, (int)Mpad, at(0, lay.A), Mpad, at(0, lay.dinv), at(0, lay.Wb), Mpad,
+                                         at(0, lay.slice), bt),
+                    "trtri"));
+  // the accumulators: B_acc over the factor (no longer needed), b_acc and the scalar sums
+  for (int64_t t = 0; t < ntask; ++t) {
+    GPX_TRY(hip_check(c, hipMemsetAsync(at(t, lay.A), 0, (size_t)Mpad * Mpad * 8, c->stream), "memset"));
+    GPX_TRY(hip_check(c, hipMemsetAsync(at(t, lay.bvec), 0, lay.task - lay.bvec, c->stream), "memset"));
+  }
+  // chunks outside, tasks inside: one fixed order of accumulation per task
+  const int64_t pstride = (int64_t)(lay.phi_task / sizeof(double));
+  for (int64_t s = 0; s < n; s += C) {
+    const int64_t mc = (n - s) < C ? (n - s) : C;
+    for (int64_t t = 0; t < ntask; ++t) {
+      GPX_TRY(hip_check(c,
+                        gpx::launch_svgp_kchunk(c, p[t], (int)M, (int)Mpad, Z + t * stride_z, ldz, shared(lay.zero),
+                                                X + s * ldx, ldx, mc, lay.ldk, shared(lay.kc), shared(lay.mu)),
+                        "svgp fit covariance"));
+      GPX_TRY(hip_check(c,
+                        gpx::launch_svgp_fit_project(c, p[t], (int)Mpad, at(t, lay.Wb), shared(lay.kc),
+                                                     shared(lay.phi) + t * pstride, lay.ldk, X + s * ldx, ldx,
+                                                     Y + s * ldy + t, ldy, (int)mc, shared(lay.r), at(t, lay.bvec),
+                                                     at(t, lay.scal)),
+                        "svgp fit projection"));
+    }
+    GPX_TRY(hip_check(c,
+                      gpx::launch_svgp_fit_syrk(c, (int)ntask, (int)Mpad, shared(lay.phi), pstride, lay.ldk, (int)mc,
+                                                at(0, lay.A), tstride),
+                      "svgp fit rank update"));
+  }
+  // B' = I + B_acc / s2 = L' L'^T and W' = L'^{-T} (in reversed index order), batched over the tasks
+  for (int64_t t = 0; t < ntask; ++t)
+    GPX_TRY(hip_check(c,
+                      gpx::launch_svgp_fit_system(c, (int)Mpad, p[t].noise, info + t, at(t, lay.A), at(t, lay.bvec),
+                                                  at(t, lay.scal)),
+                      "svgp fit system"));
+  GPX_TRY(hip_check(c, gpx::launch_potrf(c, (int)Mpad, at(0, lay.A), Mpad, at(0, lay.dinv), info2, bt), "potrf B"));
+  GPX_TRY(hip_check(c, gpx::launch_trtri(c, (int)Mpad, at(0, lay.A), Mpad, at(0, lay.dinv), at(0, lay.Wb), Mpad,
+                                         at(0, lay.slice), bt),
+                    "trtri B"));
+  // u = W'^T b', m' = W' u
+  GPX_TRY(hip_check(c,
+                    gpx::launch_svgp_fit_utvec(c, (int)ntask, (int)Mpad, at(0, lay.Wb), tstride, at(0, lay.bvec),
+                                               at(0, lay.u), tstride),
+                    "svgp fit u"));
+  gpx::Batch tv;
+  tv.count = (int)ntask;
+  tv.w = tv.y = tv.alpha = tstride;
+  GPX_TRY(hip_check(c, gpx::launch_trmv_upper(c, (int)Mpad, at(0, lay.Wb), Mpad, at(0, lay.u), at(0, lay.mrev), tv),
+                    "svgp fit mean"));
+  for (int64_t t = 0; t < ntask; ++t)
+    GPX_TRY(hip_check(c,
+                      gpx::launch_svgp_fit_finish(c, (int)M, (int)Mpad, n, p[t].noise, at(t, lay.A), at(t, lay.Wb),
+                                                  at(t, lay.u), at(t, lay.mrev), at(t, lay.scal),
+                                                  vmean + t * stride_m, vchol + t * stride_c, ldc,
+                                                  bound + t * GPX_SVGP_BOUND_NOUT),
+                      "svgp fit finish"));
+  return GPX_OK;
+}
+
 gpx_status gpx_topk_workspace_size(int64_t m, size_t* bytes) {
   if (!bytes || m < 1 || m > ((int64_t)1 << 30)) return GPX_INVALID_ARG;
   *bytes = gpx::topk_workspace_bytes(m);

@@ -355,6 +355,27 @@ hipError_t launch_svgp_chunk(Context* c, const gpx_kernel_params& p, double min_
                              const double* alpha, const double* Xs, int64_t ldxs, int64_t m_chunk,
                              const SweepBuffers& b, double* ss2, double* mean_out, int64_t ldmean, double* var_out,
                              int64_t ldvar, double* score);
+// The collapsed SVGP fit (gpx_svgpfit.hip; launch_svgp_kchunk: its covariance chunk through the sweep's K* build).
+hipError_t launch_svgp_kchunk(Context* c, const gpx_kernel_params& p, int M, int Mpad, const double* Z, int64_t ldz,
+                              const double* zero_alpha, const double* Xs, int64_t ldxs, int64_t m_chunk, int64_t ldk,
+                              double* kstar, double* mu_scratch);
+// one chunk of one task: projection (rows reversed), residual and b_acc update; scal: {sum k(x,x), r^T r, tr}
+hipError_t launch_svgp_fit_project(Context* c, const gpx_kernel_params& p, int Mpad, const double* W, const double* kc,
+                                   double* phi, int64_t ldk, const double* X, int64_t ldx, const double* Y, int64_t ldy,
+                                   int mc, double* r, double* bacc, double* scal);
+// the chunk's B_acc update of all tasks in one launch (task strides sp of phi, sb of B_acc)
+hipError_t launch_svgp_fit_syrk(Context* c, int ntask, int Mpad, const double* phi, int64_t sp, int64_t ldk, int mc,
+                                double* Bacc, int64_t sb);
+// B' = I + B_acc / s2 and b' = b_acc / s2 in place (identity / 0 for a task whose *info != 0), scal[2] = tr B_acc
+hipError_t launch_svgp_fit_system(Context* c, int Mpad, double s2, const int32_t* info, double* B, double* bvec,
+                                  double* scal);
+// u = W'^T b' per task (task strides sw / sv)
+hipError_t launch_svgp_fit_utvec(Context* c, int ntask, int Mpad, const double* Wp, int64_t sw, const double* bvec,
+                                 double* u, int64_t sv);
+// vmean / vchol (back in the caller's index order) and the bound's GPX_SVGP_BOUND_NOUT values of one task
+hipError_t launch_svgp_fit_finish(Context* c, int M, int Mpad, int64_t n, double s2, const double* Lp, const double* Wp,
+                                  const double* u, const double* mrev, const double* scal, double* vmean, double* vchol,
+                                  int64_t ldc, double* bound);
 // SVGP preparation helpers (gpx_svgp.hip)
 hipError_t launch_svgp_pad(Context* c, int ntask, int M, int Mpad, const double* vmean, int64_t stride_m,
                            const double* vchol, int64_t ldc, int64_t stride_c, double* mpad, double* spad,

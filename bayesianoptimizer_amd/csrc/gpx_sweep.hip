@@ -2002,6 +2002,22 @@ hipError_t launch_svgp_chunk(Context* c, const gpx_kernel_params& p, double min_
   return hipGetLastError();
 }
 
+// K(Z, X_chunk) alone through the same build (the collapsed SVGP fit, gpx_svgpfit.hip): kstar is Mpad x ldk (ldk a
+// multiple of 256, the build's column granule), rows >= M zero; zero_alpha: Mpad zeros, mu_scratch: (Mpad / 64) x ldk.
+hipError_t launch_svgp_kchunk(Context* c, const gpx_kernel_params& p, int M, int Mpad, const double* Z, int64_t ldz,
+                              const double* zero_alpha, const double* Xs, int64_t ldxs, int64_t m_chunk, int64_t ldk,
+                              double* kstar, double* mu_scratch) {
+  LaunchTimer tm(c, GPX_TIMER_KSTAR);
+  dim3 g((int)((m_chunk + WG - 1) / WG), Mpad / NB);
+  with_dmax(p.d, [&](auto D) {
+    with_kind(p.kind, [&](auto K) {
+      kstar_kernel<decltype(D)::value, false, decltype(K)::value, true><<<g, WG, 0, c->stream>>>(
+          p, M, Z, ldz, zero_alpha, 1, Xs, ldxs, m_chunk, ldk, kstar, mu_scratch);
+    });
+  });
+  return hipGetLastError();
+}
+
 hipError_t launch_argmax_final(Context* c, const double* vals, const int64_t* idx, int64_t count, double* best_val,
                                int64_t* best_idx) {
   LaunchTimer tm(c, GPX_TIMER_ACQ);

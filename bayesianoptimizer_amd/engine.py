@@ -1044,6 +1044,55 @@ class GPEngine:
             _ptr(ws), ws.numel()))
         return mean, var, score
 
+    def _rows_f64(self, t, name: str) -> torch.Tensor:
+        """A 2-D fp64 device tensor with unit column stride; a row stride larger than the row length is kept."""
+        t = torch.as_tensor(t).to(device=self.device, dtype=torch.float64)
+        if t.dim() != 2:
+            raise ValueError(f"{name} must be a matrix")
+        if t.shape[1] > 1 and t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+            t = t.contiguous()
+        return t
+
+    def svgp_fit_collapsed(self, params: Sequence[KernelParams], Z, X, Y, jitter: float = 1e-4,
+                           chunk: Optional[int] = None):
+        """The closed-form optimum of the whitened SVGP variational distribution for given hyperparameters and
+        inducing points (gpx_svgp_fit_collapsed_f64): per task t, q(u) = N(m, S) with S = (I + Phi Phi^T / noise)^-1,
+        m = S Phi (y_t - const_mean) / noise, Phi = L_ZZ^-1 K(Z, X).  Z: T x M x d, X: n x d (input-transformed), Y:
+        n x T.  ``chunk``: columns of X per pass (a multiple of 128 is used; None: the library's default).  Returns
+        (vmean T x M, vchol T x M x M lower triangular, bound T x SVGP_BOUND_NOUT: the collapsed bound and its five
+        terms) on the device; raises NotPositiveDefiniteError naming the task whose K_ZZ failed."""
+        Z = torch.as_tensor(Z).to(device=self.device, dtype=torch.float64).contiguous()
+        X = self._rows_f64(X, "X")
+        Y = torch.as_tensor(Y)
+        Y = self._rows_f64(Y.unsqueeze(-1) if Y.dim() == 1 else Y, "Y")
+        if Z.dim() != 3:
+            raise ValueError("Z must be T x M x d")
+        T, M, d = Z.shape
+        n = X.shape[0]
+        if X.shape[1] != d or Y.shape != (n, T):
+            raise ValueError(f"X must be n x {d} and Y n x {T}")
+        if len(params) != T:
+            raise ValueError(f"expected {T} kernel parameter sets, got {len(params)}")
+        pcs = (KernelParamsC * T)(*[pp.to_c(d) for pp in params])
+        vmean = torch.empty((T, M), dtype=torch.float64, device=self.device)
+        vchol = torch.empty((T, M, M), dtype=torch.float64, device=self.device)
+        bound = torch.empty((T, _capi.SVGP_BOUND_NOUT), dtype=torch.float64, device=self.device)
+        info = torch.zeros((T,), dtype=torch.int32, device=self.device)
+        nbytes = ctypes.c_size_t()
+        self._check(self.lib.gpx_svgp_fit_collapsed_workspace_size(M, n, T, int(chunk or 0), ctypes.byref(nbytes)))
+        ws = self.workspace("svgp_fit", nbytes.value)
+        self._bind_stream()
+        # (the library derives the chunk width from the size it is told, not from the cached buffer's)
+        self._check(self.lib.gpx_svgp_fit_collapsed_f64(
+            self.handle, pcs, T, M, float(jitter), _ptr(Z), Z.stride(1), Z.stride(0), _ptr(X), n, X.stride(0), _ptr(Y),
+            Y.stride(0), _ptr(vmean), M, _ptr(vchol), M, M * M, _ptr(bound), _ptr(info), _ptr(ws), nbytes.value))
+        bad = info.cpu().numpy()
+        for t in range(T):
+            err = info_error(int(bad[t]), f"task {t}: K_ZZ")
+            if err is not None:
+                raise err
+        return vmean, vchol, bound
+
     def topk(self, scores: torch.Tensor, k: int):
         """(values, indices) of the k largest scores, descending, ties -> lower index first (gpx_topk_f64)."""
         scores = scores.to(device=self.device, dtype=torch.float64).contiguous().reshape(-1)

@@ -330,6 +330,32 @@ class ExactGP:
         return val, (idx + int(index_offset) if index_offset else idx)
 
 
+class SparseGP:
+    """The large-n sparse surrogate of the drop-in (GPConfig.large_n_model = "sparse"): a batched SVGP whose
+    variational distribution is the closed-form optimum for the given hyperparameters and inducing points
+    (SVGPModel.fit_collapsed), served by an SVGPPredictor.  ``posterior`` is the likelihood-wrapped predictive, as
+    the reference reads it (optimization/Bayesian7.py:558,668).  Memory is O(T M^2), independent of n."""
+
+    independent = True
+
+    def __init__(self, train_X, train_Y, params, Z, jitter: float, engine=None, input_transform=None):
+        from .svgp import SVGPModel, SVGPPredictor
+
+        self.engine = engine if engine is not None else GPEngine()
+        self.train_X, self.train_Y = train_X, train_Y
+        self.svgp = SVGPModel.fit_collapsed(train_X, train_Y, params, Z, jitter=jitter, engine=self.engine)
+        self.params = self.svgp.params
+        self.predictor = SVGPPredictor(self.svgp, engine=self.engine, input_transform=input_transform)
+
+    @property
+    def num_outputs(self) -> int:
+        return self.train_Y.shape[1]
+
+    def posterior(self, X) -> Posterior:
+        mean, var = self.predictor.predict(X, transformed=True)
+        return Posterior(mean=mean, variance=var)
+
+
 class _Analytic:
     kind = "logei"
 

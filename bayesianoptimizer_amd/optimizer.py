@@ -14,7 +14,10 @@ fitted by exact marginal likelihood on the GPU each round (mll.py) — one set P
 SingleTaskGP (optimization/Bayesian1.py:108-116; ``GPConfig.independent_outputs``), the 8 outputs fitted in one batched
 call — or held fixed and shared by the outputs (one factorisation with 8 right-hand sides, exact when the
 hyperparameters are tied), in which case new observations are folded in by the bordered Cholesky
-(``ExactGP.append_observations``) instead of a refit.  Acquisition modes (``acquisition=``):
+(``ExactGP.append_observations``) instead of a refit.  Opt-in above ``svgp_threshold`` points
+(``GPConfig.large_n_policy`` with ``large_n_model="sparse"``): Bayesian7's batched SVGP itself, its variational
+distribution in closed form for the fitted hyperparameters (``SVGPModel.fit_collapsed``, ``models.SparseGP``), serving
+``predict``, ``evaluate_model`` and the pool scan.  Acquisition modes (``acquisition=``):
 
 * ``"variance"`` (default, Bayesian7's pool scan ``:646-688``): Latin-hypercube pool -> summed posterior variance on
   the device -> top-K on the device (``gpx_topk_f64``, deterministic ties) -> farthest-point sampling on the device
@@ -47,7 +50,7 @@ import torch
 
 from . import _capi
 from .engine import GPEngine, KernelParams
-from .models import ExactGP, reference_jitter_schedule
+from .models import ExactGP, SparseGP, reference_jitter_schedule
 from .transforms import LogInputStandardizer, LogOutputStandardizer
 
 INPUT_COLUMNS = ("n", "eta", "sigma_y", "width", "height")  # simulator parameters, config/config.py order
@@ -94,6 +97,15 @@ class GPConfig:
     # device memory the exact factor may take (L and W = L^{-T}: 2 n^2 doubles at capacity), as a fraction of the free
     # device memory at the rebuild; beyond it the run stops with a clear error instead of an allocator failure
     large_n_memory_fraction: float = 0.85
+    # what the large-n policy builds above svgp_threshold: "exact" (above), or "sparse": a batched SVGP on
+    # max_inducing_points inducing points (farthest-point sampled from a random inducing_subset_size-row subsample of
+    # the training inputs, Bayesian7.py:45,48,109-123) whose variational distribution is the closed-form optimum for
+    # the hyperparameters (SVGPModel.fit_collapsed), refitted every round in O(n M^2) time and O(T M^2) memory.  The
+    # hyperparameters come as in the exact mode (subsample marginal likelihood, or the fixed values).  Only
+    # acquisition="variance" (the reference's pool scan) runs on the sparse surrogate.
+    large_n_model: str = "exact"
+    max_inducing_points: int = 2048
+    inducing_subset_size: int = 10000
     # acquisition="qlogei": optimize_acqf settings of optimization/Bayesian.py:100-112
     mc_samples: int = 512
     num_restarts: int = 10
@@ -212,6 +224,11 @@ class BayesianOptimizer:
         self.acquisition = str(kwargs.get("acquisition", "variance")).lower()
         if self.acquisition not in ("variance", "logei", "ei", "ucb", "qlogei", "qpsd", "qnei", "qlognei"):
             raise ValueError(f"unknown acquisition '{self.acquisition}'")
+        if self.config.large_n_model not in ("exact", "sparse"):
+            raise ValueError(f"unknown GPConfig.large_n_model '{self.config.large_n_model}'")
+        if self._sparse_policy() and self.acquisition != "variance":
+            raise ValueError(f"acquisition '{self.acquisition}' is not available with GPConfig.large_n_model='sparse': "
+                             "the sparse surrogate serves acquisition='variance' (the pool scan) only")
         self.seed = kwargs.get("seed", None)
         self._rng = np.random.default_rng(self.seed)
         # the large-n policy's hyperparameter subsamples draw from their own stream (never shift the candidate draws)
@@ -282,6 +299,9 @@ class BayesianOptimizer:
         return KernelParams(c.kernel, c.lengthscale, outputscale=c.outputscale, noise=c.noise,
                             linear_variance=c.linear_variance)
 
+    def _sparse_policy(self) -> bool:
+        return bool(self.config.large_n_policy) and self.config.large_n_model == "sparse"
+
     def fit_gp_model(self):
         """Log-standardise (Bayesian7.py:363-385) and build the exact posterior for all outputs on the engine.
 
@@ -296,7 +316,7 @@ class BayesianOptimizer:
         self.y_tf = LogOutputStandardizer().fit(self.train_Y_raw)
         Ys = self.y_tf(self.train_Y_raw)
         if cfg.large_n_policy and n > self.svgp_threshold:
-            return self._fit_large_n(n, Ys)
+            return self._fit_sparse(n, Ys) if self._sparse_policy() else self._fit_large_n(n, Ys)
         self._large_n_base = None
         grow = (not cfg.fit_hyperparameters and cfg.incremental_updates and self.gp_model is not None
                 and self.x_tf is not None and self.gp_model.train_X.shape[0] < n)
@@ -372,17 +392,42 @@ class BayesianOptimizer:
         Xs = self.x_tf(self.train_X)
         jit = reference_jitter_schedule(cfg.jitter_val)
         if cfg.fit_hyperparameters:
-            m = int(self.svgp_threshold)
-            sub = np.sort(self._subsample_rng.choice(n, size=m, replace=False))
-            sub_t = torch.as_tensor(sub, device=Xs.device)
-            sub_gp = ExactGP(Xs[sub_t], Ys[sub_t], params, engine=self.engine, jitter_schedule=jit,
-                             independent_outputs=cfg.independent_outputs or not isinstance(params, KernelParams))
-            sub_gp.fit_hyperparameters(cfg.prior_set, options=cfg.mll_options)
-            params = sub_gp.params
-            del sub_gp
-            print(f"[gpx] n={n} > svgp_threshold={self.svgp_threshold}: hyperparameters from a {m}-point subsample")
+            params = self._subsample_hyperparameters(n, Xs, Ys, params, jit)
         self.gp_model = ExactGP(Xs, Ys, params, engine=self.engine, jitter_schedule=jit, capacity=cap).fit()
         self._large_n_base = n
+        return self.gp_model
+
+    def _subsample_hyperparameters(self, n: int, Xs: torch.Tensor, Ys: torch.Tensor, params, jit):
+        """Marginal-likelihood fit on a random subsample of svgp_threshold points, starting from ``params``."""
+        cfg = self.config
+        m = int(self.svgp_threshold)
+        sub = np.sort(self._subsample_rng.choice(n, size=m, replace=False))
+        sub_t = torch.as_tensor(sub, device=Xs.device)
+        sub_gp = ExactGP(Xs[sub_t], Ys[sub_t], params, engine=self.engine, jitter_schedule=jit,
+                         independent_outputs=cfg.independent_outputs or not isinstance(params, KernelParams))
+        sub_gp.fit_hyperparameters(cfg.prior_set, options=cfg.mll_options)
+        print(f"[gpx] n={n} > svgp_threshold={self.svgp_threshold}: hyperparameters from a {m}-point subsample")
+        return sub_gp.params
+
+    def _fit_sparse(self, n: int, Ys: torch.Tensor):
+        """n > svgp_threshold with GPConfig.large_n_model = "sparse": hyperparameters as in _fit_large_n, inducing points
+        by select_inducing_points on the transformed inputs, the variational distribution in closed form; a fresh fit
+        every round (no n x n factor is ever held)."""
+        from .svgp import select_inducing_points
+
+        cfg = self.config
+        prev = self.gp_model
+        params = prev.params if prev is not None else self._kernel_params()
+        self.gp_model = prev = None
+        self._large_n_base = None
+        self.x_tf = LogInputStandardizer(self._bounds_t()).fit(self.train_X)
+        Xs = self.x_tf(self.train_X)
+        if cfg.fit_hyperparameters:
+            params = self._subsample_hyperparameters(n, Xs, Ys, params, reference_jitter_schedule(cfg.jitter_val))
+        gen = torch.Generator().manual_seed(int(self._subsample_rng.integers(0, 2 ** 31 - 1)))
+        Z = select_inducing_points(Xs, cfg.max_inducing_points, cfg.inducing_subset_size, generator=gen,
+                                   engine=self.engine)
+        self.gp_model = SparseGP(Xs, Ys, params, Z, jitter=cfg.jitter_val, engine=self.engine, input_transform=self.x_tf)
         return self.gp_model
 
     def predict(self, x_orig_numpy: np.ndarray, return_var: bool = False):
@@ -461,6 +506,9 @@ class BayesianOptimizer:
             return torch.empty((0, self.dim), dtype=self.dtype, device=self.gp_device)
         if self.acquisition == "variance":
             return self._pool_scan(k)
+        if isinstance(self.gp_model, SparseGP):
+            raise ValueError(f"acquisition '{self.acquisition}' is not available on the sparse surrogate "
+                             "(GPConfig.large_n_model='sparse' serves acquisition='variance' only)")
         if self.acquisition == "qlogei":
             return self._acquire_qlogei(k)
         if self.acquisition == "qpsd":
@@ -474,6 +522,10 @@ class BayesianOptimizer:
         cfg = self.config
         gp = self.gp_model
         pool = self._tensor(self._latin_hypercube(cfg.candidates_pool_size))
+        if isinstance(gp, SparseGP):  # the same scan on the sparse predictive (SVGPPredictor.pool_scan)
+            k_big = min(max(5000, 20 * k), cfg.K_BIG_CAP, pool.shape[0])
+            start = int(self._rng.integers(0, k_big)) if k < k_big else None
+            return gp.predictor.pool_scan(pool, k, k_big_cap=cfg.K_BIG_CAP, start=start)[0]
         if gp.independent:  # sum over the outputs of their own posterior variances, in one device sweep
             _, _, score = gp.engine.acquire_multi(gp.states, self.x_tf(pool), "variance", return_scores=True)
         else:

@@ -3,17 +3,19 @@
 SURVEY §8a row a9 and §8f row 2.  ``scripts/run_optimization.py:4`` drives ``Bayesian7.BayesianOptimizer``, whose
 acquisition (``optimization/Bayesian7.py:646-688``) is: LHS candidate pool -> per 2048-candidate chunk
 ``likelihood(model(x_std)).variance.sum(0)`` -> ``torch.topk(K_big)`` -> ``farthest_point_sampling(batch_k)``.  Here the
-predictive, the top-k and the FPS all run in libgpx (``gpx_svgp_*``, ``gpx_topk_f64``, ``gpx_fps_f64``); the SVGP's
-variational TRAINING (Adam on the ELBO, ``:451-538``) is not part of the hot path and stays out of scope
-(DESIGN.md §7): a model trained by the reference is loaded from its checkpoint state dict (``batch_svgp.pt``,
-``:702-707``) with ``SVGPModel.from_state_dict``.
+predictive, the top-k and the FPS all run in libgpx (``gpx_svgp_*``, ``gpx_topk_f64``, ``gpx_fps_f64``).  A model
+comes from one of two places: a checkpoint the reference trained (``batch_svgp.pt``, ``:702-707``) through
+``SVGPModel.from_state_dict``, or ``SVGPModel.fit_collapsed``: for given hyperparameters and inducing points the
+variational distribution the reference's Adam loop on the ELBO (``:451-538``) descends towards is known in closed form
+(Gaussian likelihood: Titsias' collapsed posterior), and ``gpx_svgp_fit_collapsed_f64`` computes it.
+Gradients of the bound, learning Z and minibatch training stay out of scope.
 
 All arithmetic is fp64 (the reference model is float32; its variational jitter, 1e-4, is kept as the default).
 """
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import List, Optional
+from typing import List, Optional, Sequence, Union
 
 import torch
 
@@ -41,10 +43,31 @@ class SVGPModel:
     vchol: torch.Tensor
     params: List[KernelParams]
     jitter: float = VARIATIONAL_JITTER_F32
+    bound: Optional[torch.Tensor] = None  # fit_collapsed: T x 6 on the host, the collapsed bound F and its five terms
 
     @property
     def num_tasks(self) -> int:
         return self.Z.shape[0]
+
+    @classmethod
+    def fit_collapsed(cls, X, Y, params: Union[KernelParams, Sequence[KernelParams]], Z,
+                      jitter: float = VARIATIONAL_JITTER_F32, engine: Optional[GPEngine] = None) -> "SVGPModel":
+        """The model whose variational distribution is the optimum of the full-batch ELBO for the given
+        hyperparameters (one KernelParams for all tasks, or one per task) and inducing points Z (M x d shared by the
+        tasks, or T x M x d): ``GPEngine.svgp_fit_collapsed``.  X: n x d input-transformed, Y: n x T.  The bound's value
+        and terms are kept as ``model.bound`` (T x 6, host)."""
+        eng = engine or GPEngine()
+        Y = torch.as_tensor(Y)
+        if Y.dim() == 1:
+            Y = Y.unsqueeze(-1)
+        T = Y.shape[1]
+        plist = [params] * T if isinstance(params, KernelParams) else list(params)
+        Z = torch.as_tensor(Z).to(device=eng.device, dtype=torch.float64)
+        if Z.dim() == 2:
+            Z = Z.unsqueeze(0).expand(T, -1, -1)
+        Z = Z.contiguous()
+        vmean, vchol, bound = eng.svgp_fit_collapsed(plist, Z, X, Y, jitter=jitter)
+        return cls(Z=Z, vmean=vmean, vchol=vchol, params=plist, jitter=jitter, bound=bound.cpu())
 
     @classmethod
     def from_state_dict(cls, model_sd: dict, likelihood_sd: Optional[dict] = None,
@@ -122,3 +145,21 @@ class SVGPPredictor:
             start = int(torch.randint(0, k_big, (1,), generator=generator).item())
         sel = self.engine.fps(cand_big, batch_k, start)
         return cand_big.index_select(0, sel), idx_big.index_select(0, sel)
+
+
+def select_inducing_points(X: torch.Tensor, m: int, subset_size: int = 10000,
+                           generator: Optional[torch.Generator] = None,
+                           engine: Optional[GPEngine] = None) -> torch.Tensor:
+    """Inducing points as ``optimization/Bayesian7.py:109-123`` picks them: a random subsample of ``subset_size`` rows
+    of X when it has more, then farthest-point sampling (``GPEngine.fps``, random start) of min(m, rows) of them.
+    ``generator``: a CPU torch.Generator for the two draws."""
+    n = X.shape[0]
+    if n > subset_size:
+        X = X[torch.randperm(n, generator=generator)[:subset_size].to(X.device)]
+        n = X.shape[0]
+    m = min(int(m), n)
+    if m >= n:  # farthest_point_sampling returns its input unchanged (:89-90)
+        return X
+    eng = engine or GPEngine()
+    start = int(torch.randint(0, n, (1,), generator=generator).item())
+    return X[eng.fps(X, m, start).to(X.device)]

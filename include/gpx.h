@@ -591,6 +591,38 @@ gpx_status gpx_svgp_predict_f64(gpx_handle h, const gpx_kernel_params* p, int64_
                                 int64_t ldmean, double* var_out, int64_t ldvar, double* score_out, void* ws,
                                 size_t ws_bytes);
 
+/* ---- SVGP variational posterior in closed form (the collapsed bound of Titsias 2009) ------------------------------ */
+/* For given hyperparameters p[t] and inducing points Z, the optimum of the whitened variational distribution
+ * q(u) = N(m, S) of Bayesian7.py's model (Gaussian likelihood) under the full-batch ELBO, per task t, all fp64:
+ *   K_ZZ + jitter I = L L^T, W = L^{-T};  Phi = W^T K(Z, X) (M x n);  r = y_t - const_mean;  s2 = noise
+ *   B = I + Phi Phi^T / s2,  b = Phi r / s2;  S = B^{-1},  m = S b
+ * vmean = m (ntask x M), vchol = the lower-triangular C with positive diagonal and C C^T = S (ntask x M x M, strict
+ * upper triangle written as 0): the layout gpx_svgp_prepare_f64 reads.  X (n x d, already input-transformed) is streamed
+ * in chunks of columns: Phi's chunk is formed first (projected), then Phi Phi^T and Phi r are accumulated from it, chunk
+ * after chunk in a fixed order, so equal inputs and an equal chunk width give equal bits.
+ * bound (ntask x GPX_SVGP_BOUND_NOUT): the collapsed bound F and its five terms (indices below).
+ * info: int32[ntask], K_ZZ's failing pivot + 1 (as gpx_svgp_prepare_f64); a failed task's outputs are unspecified, the
+ * other tasks are computed.
+ * Workspace: gpx_svgp_fit_collapsed_workspace_size(M, n, ntask, chunk) for a chunk width `chunk` (rounded up to a
+ * multiple of 128; 0 = the default, GPX_SVGP_FIT_CHUNK); it does not grow with n.  The call derives its chunk width from
+ * ws_bytes: the largest multiple of 128, at most the default, that fits; below the chunk = 128 size: GPX_INVALID_ARG. */
+enum {
+  GPX_SVGP_BOUND_F = 0,       /* the sum of the five terms */
+  GPX_SVGP_BOUND_CONST = 1,   /* -(n/2) log(2 pi s2) */
+  GPX_SVGP_BOUND_LOGDET = 2,  /* -(1/2) log |B| */
+  GPX_SVGP_BOUND_QUAD = 3,    /* -(1/2) r^T r / s2 */
+  GPX_SVGP_BOUND_FIT = 4,     /* +(1/2) b^T B^{-1} b */
+  GPX_SVGP_BOUND_TRACE = 5,   /* -(1/2) (sum_i k(x_i, x_i) - tr Phi Phi^T) / s2 */
+  GPX_SVGP_BOUND_NOUT = 6
+};
+#define GPX_SVGP_FIT_CHUNK 4096
+gpx_status gpx_svgp_fit_collapsed_workspace_size(int64_t M, int64_t n, int64_t ntask, int64_t chunk, size_t* bytes);
+gpx_status gpx_svgp_fit_collapsed_f64(gpx_handle h, const gpx_kernel_params* p, int64_t ntask, int64_t M, double jitter,
+                                      const double* Z, int64_t ldz, int64_t stride_z, const double* X, int64_t n,
+                                      int64_t ldx, const double* Y, int64_t ldy, double* vmean, int64_t stride_m,
+                                      double* vchol, int64_t ldc, int64_t stride_c, double* bound, int32_t* info,
+                                      void* ws, size_t ws_bytes);
+
 /* The k largest scores in descending order (replaces torch.topk, Bayesian7.py:681): stable, so equal scores keep
  * the lower index first; NaN ranks last.  idx_out: int64[k], val_out: double[k] (NULL = skip). */
 gpx_status gpx_topk_workspace_size(int64_t m, size_t* bytes);
