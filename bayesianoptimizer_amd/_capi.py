@@ -50,6 +50,9 @@ MLL_D_LENGTHSCALE, MLL_D_LINVAR, MLL_NOUT = 8, 40, 72
 SVGP_BOUND_F, SVGP_BOUND_CONST, SVGP_BOUND_LOGDET, SVGP_BOUND_QUAD, SVGP_BOUND_FIT, SVGP_BOUND_TRACE = 0, 1, 2, 3, 4, 5
 SVGP_BOUND_NOUT = 6
 SVGP_FIT_CHUNK = 4096  # GPX_SVGP_FIT_CHUNK: the default chunk width
+# gpx_svgp_bound_grad_f64 output layout (include/gpx.h GPX_SVGP_GRAD_*): the bound's six values, then a block in the MLL_*
+# layout holding -F and its gradient
+SVGP_GRAD_BOUND, SVGP_GRAD_MLL, SVGP_GRAD_NOUT = 0, 8, 80
 
 
 class GPXLibraryError(RuntimeError):
@@ -252,6 +255,9 @@ _PROTOS = {
     "gpx_svgp_fit_collapsed_f64": (c_int32, [_h, POINTER(KernelParamsC), c_int64, c_int64, c_double, _p, c_int64,
                                              c_int64, _p, c_int64, c_int64, _p, c_int64, _p, c_int64, _p, c_int64,
                                              c_int64, _p, _p, _p, c_size_t]),
+    "gpx_svgp_bound_grad_workspace_size": (c_int32, [c_int64, c_int64, c_int64, c_int64, POINTER(c_size_t)]),
+    "gpx_svgp_bound_grad_f64": (c_int32, [_h, POINTER(KernelParamsC), c_int64, c_int64, c_double, _p, c_int64,
+                                          c_int64, _p, c_int64, c_int64, _p, c_int64, _p, _p, _p, c_size_t]),
     "gpx_topk_workspace_size": (c_int32, [c_int64, POINTER(c_size_t)]),
     "gpx_topk_f64": (c_int32, [_h, _p, c_int64, c_int64, _p, _p, _p, c_size_t]),
     "gpx_fps_f64": (c_int32, [_h, _p, c_int64, c_int64, c_int64, c_int64, c_int64, _p]),

@@ -1632,7 +1632,8 @@ struct SvgpFitLayout {
   int64_t ldk;
 };
 int64_t up128(int64_t v) { return (v + 127) / 128 * 128; }
-size_t svgp_fit_fixed_bytes(int64_t Mpad, int64_t ntask, SvgpFitLayout* l) {
+// (extra: bytes appended to every task's block, for gpx_svgp_bound_grad_f64's SvgpGradLayout; 0 in the fit)
+size_t svgp_fit_fixed_bytes(int64_t Mpad, int64_t ntask, SvgpFitLayout* l, size_t extra = 0) {
   const size_t mat = al256((size_t)Mpad * Mpad * 8), vec = al256((size_t)Mpad * 8);
   l->A = 0;
   l->Wb = mat;
@@ -1642,7 +1643,7 @@ size_t svgp_fit_fixed_bytes(int64_t Mpad, int64_t ntask, SvgpFitLayout* l) {
   l->u = l->bvec + vec;
   l->mrev = l->u + vec;
   l->scal = l->mrev + vec;
-  l->task = l->scal + 256;
+  l->task = l->scal + 256 + extra;
   return l->task * (size_t)ntask + vec /* zero */ + al256((size_t)ntask * 4) /* info2 */;
 }
 // bytes of the parts that scale with the chunk width C (a multiple of 128)
@@ -1651,9 +1652,9 @@ size_t svgp_fit_chunk_bytes(int64_t Mpad, int64_t ntask, int64_t C) {
   return (size_t)(1 + ntask) * al256((size_t)Mpad * ldk * 8) + al256((size_t)(Mpad / gpx::NB) * ldk * 8) +
          al256(ldk * 8);
 }
-SvgpFitLayout svgp_fit_layout(int64_t Mpad, int64_t ntask, int64_t C) {
+SvgpFitLayout svgp_fit_layout(int64_t Mpad, int64_t ntask, int64_t C, size_t extra = 0) {
   SvgpFitLayout l;
-  const size_t fixed = svgp_fit_fixed_bytes(Mpad, ntask, &l);
+  const size_t fixed = svgp_fit_fixed_bytes(Mpad, ntask, &l, extra);
   l.ldk = (C + 255) / 256 * 256;
   l.zero = l.task * (size_t)ntask;
   l.info2 = l.zero + al256((size_t)Mpad * 8);
@@ -1675,6 +1676,93 @@ gpx_status gpx_svgp_fit_collapsed_workspace_size(int64_t M, int64_t n, int64_t n
   *bytes = svgp_fit_layout(padded(M), ntask, C).total + 256;
   return GPX_OK;
 }
+
+namespace {
+// The fit's launches up to m' (arguments checked by the entry points; the device is current): on return, per task, A
+// holds L' (B' = L' L'^T), Wb holds W' = L'^{-T}, and bvec / u / mrev / scal are final.  keepW / keepB (byte offsets in
+// the task's block, 0 = none): copies of W = L_ZZ^{-T} and of B' before they are overwritten.
+gpx_status svgp_fit_core(Context* c, const gpx_kernel_params* p, int64_t ntask, int64_t M, int64_t Mpad, double jitter,
+                         const double* Z, int64_t ldz, int64_t stride_z, const double* X, int64_t n, int64_t ldx,
+                         const double* Y, int64_t ldy, int32_t* info, const SvgpFitLayout& lay, char* base, int64_t C,
+                         size_t keepW, size_t keepB) {
+  auto at = [&](int64_t t, size_t off) { return reinterpret_cast<double*>(base + lay.task * t + off); };
+  auto shared = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
+  int32_t* info2 = reinterpret_cast<int32_t*>(base + lay.info2);
+  const int64_t tstride = (int64_t)(lay.task / sizeof(double));
+  GPX_TRY(hip_check(c, hipMemsetAsync(info, 0, sizeof(int32_t) * ntask, c->stream), "memset info"));
+  GPX_TRY(hip_check(c, hipMemsetAsync(info2, 0, sizeof(int32_t) * ntask, c->stream), "memset info"));
+  GPX_TRY(hip_check(c, hipMemsetAsync(shared(lay.zero), 0, (size_t)Mpad * 8, c->stream), "memset"));
+  // W = (chol(K_ZZ + jitter I))^{-T} per task, as gpx_svgp_prepare_f64 builds it
+  for (int64_t t = 0; t < ntask; ++t) {
+    gpx_kernel_params q = p[t];
+    q.noise = 0.0;
+    q.jitter = jitter;
+    GPX_TRY(hip_check(c, gpx::launch_gram(c, q, (int)M, (int)Mpad, Z + t * stride_z, ldz, at(t, lay.A), Mpad), "gram"));
+  }
+  gpx::Batch bt;
+  bt.count = (int)ntask;
+  bt.k = bt.dinv = bt.ws = bt.w = tstride;
+  GPX_TRY(hip_check(c, gpx::launch_potrf(c, (int)Mpad, at(0, lay.A), Mpad, at(0, lay.dinv), info, bt), "potrf"));
+  GPX_TRY(hip_check(c, gpx::launch_trtri(c, (int)Mpad, at(0, lay.A), Mpad, at(0, lay.dinv), at(0, lay.Wb), Mpad,
+                                         at(0, lay.slice), bt),
+                    "trtri"));
+  if (keepW)  // (gpx_svgp_bound_grad_f64: W' will overwrite W below)
+    for (int64_t t = 0; t < ntask; ++t)
+      GPX_TRY(hip_check(c, hipMemcpyAsync(at(t, keepW), at(t, lay.Wb), (size_t)Mpad * Mpad * 8,
+                                          hipMemcpyDeviceToDevice, c->stream), "keep W"));
+  // the accumulators: B_acc over the factor (no longer needed), b_acc and the scalar sums
+  for (int64_t t = 0; t < ntask; ++t) {
+    GPX_TRY(hip_check(c, hipMemsetAsync(at(t, lay.A), 0, (size_t)Mpad * Mpad * 8, c->stream), "memset"));
+    GPX_TRY(hip_check(c, hipMemsetAsync(at(t, lay.bvec), 0, lay.scal + 256 - lay.bvec, c->stream), "memset"));
+  }
+  // chunks outside, tasks inside: one fixed order of accumulation per task
+  const int64_t pstride = (int64_t)(lay.phi_task / sizeof(double));
+  for (int64_t s = 0; s < n; s += C) {
+    const int64_t mc = (n - s) < C ? (n - s) : C;
+    for (int64_t t = 0; t < ntask; ++t) {
+      GPX_TRY(hip_check(c,
+                        gpx::launch_svgp_kchunk(c, p[t], (int)M, (int)Mpad, Z + t * stride_z, ldz, shared(lay.zero),
+                                                X + s * ldx, ldx, mc, lay.ldk, shared(lay.kc), shared(lay.mu)),
+                        "svgp fit covariance"));
+      GPX_TRY(hip_check(c,
+                        gpx::launch_svgp_fit_project(c, p[t], (int)Mpad, at(t, lay.Wb), shared(lay.kc),
+                                                     shared(lay.phi) + t * pstride, lay.ldk, X + s * ldx, ldx,
+                                                     Y + s * ldy + t, ldy, (int)mc, shared(lay.r), at(t, lay.bvec),
+                                                     at(t, lay.scal)),
+                        "svgp fit projection"));
+    }
+    GPX_TRY(hip_check(c,
+                      gpx::launch_svgp_fit_syrk(c, (int)ntask, (int)Mpad, shared(lay.phi), pstride, lay.ldk, (int)mc,
+                                                at(0, lay.A), tstride),
+                      "svgp fit rank update"));
+  }
+  // B' = I + B_acc / s2 = L' L'^T and W' = L'^{-T} (in reversed index order), batched over the tasks
+  for (int64_t t = 0; t < ntask; ++t)
+    GPX_TRY(hip_check(c,
+                      gpx::launch_svgp_fit_system(c, (int)Mpad, p[t].noise, info + t, at(t, lay.A), at(t, lay.bvec),
+                                                  at(t, lay.scal)),
+                      "svgp fit system"));
+  if (keepB)  // (B' on its lower 128-tiles, the others 0, before its factor overwrites it)
+    for (int64_t t = 0; t < ntask; ++t)
+      GPX_TRY(hip_check(c, hipMemcpyAsync(at(t, keepB), at(t, lay.A), (size_t)Mpad * Mpad * 8,
+                                          hipMemcpyDeviceToDevice, c->stream), "keep B"));
+  GPX_TRY(hip_check(c, gpx::launch_potrf(c, (int)Mpad, at(0, lay.A), Mpad, at(0, lay.dinv), info2, bt), "potrf B"));
+  GPX_TRY(hip_check(c, gpx::launch_trtri(c, (int)Mpad, at(0, lay.A), Mpad, at(0, lay.dinv), at(0, lay.Wb), Mpad,
+                                         at(0, lay.slice), bt),
+                    "trtri B"));
+  // u = W'^T b', m' = W' u
+  GPX_TRY(hip_check(c,
+                    gpx::launch_svgp_fit_utvec(c, (int)ntask, (int)Mpad, at(0, lay.Wb), tstride, at(0, lay.bvec),
+                                               at(0, lay.u), tstride),
+                    "svgp fit u"));
+  gpx::Batch tv;
+  tv.count = (int)ntask;
+  tv.w = tv.y = tv.alpha = tstride;
+  GPX_TRY(hip_check(c, gpx::launch_trmv_upper(c, (int)Mpad, at(0, lay.Wb), Mpad, at(0, lay.u), at(0, lay.mrev), tv),
+                    "svgp fit mean"));
+  return GPX_OK;
+}
+}  // namespace
 
 gpx_status gpx_svgp_fit_collapsed_f64(gpx_handle h, const gpx_kernel_params* p, int64_t ntask, int64_t M, double jitter,
                                       const double* Z, int64_t ldz, int64_t stride_z, const double* X, int64_t n,
@@ -1713,72 +1801,7 @@ gpx_status gpx_svgp_fit_collapsed_f64(gpx_handle h, const gpx_kernel_params* p, 
   GPX_USE_DEVICE(c);
   char* base = reinterpret_cast<char*>(align256(ws));
   auto at = [&](int64_t t, size_t off) { return reinterpret_cast<double*>(base + lay.task * t + off); };
-  auto shared = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
-  int32_t* info2 = reinterpret_cast<int32_t*>(base + lay.info2);
-  const int64_t tstride = (int64_t)(lay.task / sizeof(double));
-  GPX_TRY(hip_check(c, hipMemsetAsync(info, 0, sizeof(int32_t) * ntask, c->stream), "memset info"));
-  GPX_TRY(hip_check(c, hipMemsetAsync(info2, 0, sizeof(int32_t) * ntask, c->stream), "memset info"));
-  GPX_TRY(hip_check(c, hipMemsetAsync(shared(lay.zero), 0, (size_t)Mpad * 8, c->stream), "memset"));
-  // W = (chol(K_ZZ + jitter I))^{-T} per task, as gpx_svgp_prepare_f64 builds it
-  for (int64_t t = 0; t < ntask; ++t) {
-    gpx_kernel_params q = p[t];
-    q.noise = 0.0;
-    q.jitter = jitter;
-    GPX_TRY(hip_check(c, gpx::launch_gram(c, q, (int)M, (int)Mpad, Z + t * stride_z, ldz, at(t, lay.A), Mpad), "gram"));
-  }
-  gpx::Batch bt;
-  bt.count = (int)ntask;
-  bt.k = bt.dinv = bt.ws = bt.w = tstride;
-  GPX_TRY(hip_check(c, gpx::launch_potrf(c, (int)Mpad, at(0, lay.A), Mpad, at(0, lay.dinv), info, bt), "potrf"));
-  GPX_TRY(hip_check(c, gpx::launch_trtri(c, (int)Mpad, at(0, lay.A), Mpad, at(0, lay.dinv), at(0, lay.Wb), Mpad,
-                                         at(0, lay.slice), bt),
-                    "trtri"));
-  // the accumulators: B_acc over the factor (no longer needed), b_acc and the scalar sums
-  for (int64_t t = 0; t < ntask; ++t) {
-    GPX_TRY(hip_check(c, hipMemsetAsync(at(t, lay.A), 0, (size_t)Mpad * Mpad * 8, c->stream), "memset"));
-    GPX_TRY(hip_check(c, hipMemsetAsync(at(t, lay.bvec), 0, lay.task - lay.bvec, c->stream), "memset"));
-  }
-  // chunks outside, tasks inside: one fixed order of accumulation per task
-  const int64_t pstride = (int64_t)(lay.phi_task / sizeof(double));
-  for (int64_t s = 0; s < n; s += C) {
-    const int64_t mc = (n - s) < C ? (n - s) : C;
-    for (int64_t t = 0; t < ntask; ++t) {
-      GPX_TRY(hip_check(c,
-                        gpx::launch_svgp_kchunk(c, p[t], (int)M, (int)Mpad, Z + t * stride_z, ldz, shared(lay.zero),
-                                                X + s * ldx, ldx, mc, lay.ldk, shared(lay.kc), shared(lay.mu)),
-                        "svgp fit covariance"));
-      GPX_TRY(hip_check(c,
-                        gpx::launch_svgp_fit_project(c, p[t], (int)Mpad, at(t, lay.Wb), shared(lay.kc),
-                                                     shared(lay.phi) + t * pstride, lay.ldk, X + s * ldx, ldx,
-                                                     Y + s * ldy + t, ldy, (int)mc, shared(lay.r), at(t, lay.bvec),
-                                                     at(t, lay.scal)),
-                        "svgp fit projection"));
-    }
-    GPX_TRY(hip_check(c,
-                      gpx::launch_svgp_fit_syrk(c, (int)ntask, (int)Mpad, shared(lay.phi), pstride, lay.ldk, (int)mc,
-                                                at(0, lay.A), tstride),
-                      "svgp fit rank update"));
-  }
-  // B' = I + B_acc / s2 = L' L'^T and W' = L'^{-T} (in reversed index order), batched over the tasks
-  for (int64_t t = 0; t < ntask; ++t)
-    GPX_TRY(hip_check(c,
-                      gpx::launch_svgp_fit_system(c, (int)Mpad, p[t].noise, info + t, at(t, lay.A), at(t, lay.bvec),
-                                                  at(t, lay.scal)),
-                      "svgp fit system"));
-  GPX_TRY(hip_check(c, gpx::launch_potrf(c, (int)Mpad, at(0, lay.A), Mpad, at(0, lay.dinv), info2, bt), "potrf B"));
-  GPX_TRY(hip_check(c, gpx::launch_trtri(c, (int)Mpad, at(0, lay.A), Mpad, at(0, lay.dinv), at(0, lay.Wb), Mpad,
-                                         at(0, lay.slice), bt),
-                    "trtri B"));
-  // u = W'^T b', m' = W' u
-  GPX_TRY(hip_check(c,
-                    gpx::launch_svgp_fit_utvec(c, (int)ntask, (int)Mpad, at(0, lay.Wb), tstride, at(0, lay.bvec),
-                                               at(0, lay.u), tstride),
-                    "svgp fit u"));
-  gpx::Batch tv;
-  tv.count = (int)ntask;
-  tv.w = tv.y = tv.alpha = tstride;
-  GPX_TRY(hip_check(c, gpx::launch_trmv_upper(c, (int)Mpad, at(0, lay.Wb), Mpad, at(0, lay.u), at(0, lay.mrev), tv),
-                    "svgp fit mean"));
+  GPX_TRY(svgp_fit_core(c, p, ntask, M, Mpad, jitter, Z, ldz, stride_z, X, n, ldx, Y, ldy, info, lay, base, C, 0, 0));
   for (int64_t t = 0; t < ntask; ++t)
     GPX_TRY(hip_check(c,
                       gpx::launch_svgp_fit_finish(c, (int)M, (int)Mpad, n, p[t].noise, at(t, lay.A), at(t, lay.Wb),
@@ -1786,6 +1809,147 @@ gpx_status gpx_svgp_fit_collapsed_f64(gpx_handle h, const gpx_kernel_params* p, 
                                                   vmean + t * stride_m, vchol + t * stride_c, ldc,
                                                   bound + t * GPX_SVGP_BOUND_NOUT),
                       "svgp fit finish"));
+  return GPX_OK;
+}
+
+// ---- Hyperparameter gradient of the collapsed bound (gpx_svgpgrad.hip) ----------------------------------
+namespace {
+// The fit's layout with a tail on every task's block: Wk (W = L_ZZ^{-T}, kept), Bc (B', then H), X1 (Q), the vectors
+// c_v and m (natural order), the second pass's scalar sums {sum e, e^T e, M - tr S, -, .., sum_i x_ik^2 at 8 + k}, the
+// gradient accumulator row and the bound's six values.  The fit's own matrices are reused between the passes: A holds
+// L', then T1 = I - S, then G_A; Wb holds W', then the products' intermediate U.  Shared, behind the fit's chunk part:
+// the chunk's residual e and the partial rows of one launch.  Bytes: (5 Mpad^2 + ..) 8 per task + (1 + T) Mpad ldk 8.
+struct SvgpGradLayout {
+  SvgpFitLayout fit;
+  size_t Wk, Bc, X1, cv, mnat, sc2, gacc, bnd;  // per task: byte offsets in the task's block
+  size_t ev, part, total;                       // shared: byte offsets from the base
+};
+size_t svgp_grad_extra(int64_t Mpad) {
+  return 3 * al256((size_t)Mpad * Mpad * 8) + 2 * al256((size_t)Mpad * 8) + 512 + al256(GPX_MLL_NOUT * 8) + 256;
+}
+size_t svgp_grad_shared_bytes(int64_t Mpad, int64_t C) {
+  const size_t nI = (size_t)(Mpad / 128), ncb = (size_t)(C / 128);
+  return al256((size_t)((C + 255) / 256 * 256) * 8) + al256(nI * (ncb > nI ? ncb : nI) * GPX_MLL_NOUT * 8);
+}
+SvgpGradLayout svgp_grad_layout(int64_t Mpad, int64_t ntask, int64_t C) {
+  SvgpGradLayout g;
+  g.fit = svgp_fit_layout(Mpad, ntask, C, svgp_grad_extra(Mpad));
+  const size_t mat = al256((size_t)Mpad * Mpad * 8), vec = al256((size_t)Mpad * 8);
+  g.Wk = g.fit.scal + 256;
+  g.Bc = g.Wk + mat;
+  g.X1 = g.Bc + mat;
+  g.cv = g.X1 + mat;
+  g.mnat = g.cv + vec;
+  g.sc2 = g.mnat + vec;
+  g.gacc = g.sc2 + 512;
+  g.bnd = g.gacc + al256(GPX_MLL_NOUT * 8);
+  g.ev = g.fit.total;
+  g.part = g.ev + al256((size_t)g.fit.ldk * 8);
+  g.total = g.fit.total + svgp_grad_shared_bytes(Mpad, C);
+  return g;
+}
+}  // namespace
+
+gpx_status gpx_svgp_bound_grad_workspace_size(int64_t M, int64_t n, int64_t ntask, int64_t chunk, size_t* bytes) {
+  if (!bytes || M < 1 || M > 65536 || n < 1 || ntask < 1 || ntask > 64 || chunk < 0 || chunk > ((int64_t)1 << 20))
+    return GPX_INVALID_ARG;
+  // (the size does not depend on n: a chunk wider than n only leaves columns unused)
+  const int64_t C = chunk == 0 ? GPX_SVGP_FIT_CHUNK : up128(chunk);
+  *bytes = svgp_grad_layout(padded(M), ntask, C).total + 256;
+  return GPX_OK;
+}
+
+gpx_status gpx_svgp_bound_grad_f64(gpx_handle h, const gpx_kernel_params* p, int64_t ntask, int64_t M, double jitter,
+                                   const double* Z, int64_t ldz, int64_t stride_z, const double* X, int64_t n,
+                                   int64_t ldx, const double* Y, int64_t ldy, double* out, int32_t* info, void* ws,
+                                   size_t ws_bytes) {
+  Context* c = reinterpret_cast<Context*>(h);
+  if (!c) return GPX_INVALID_ARG;
+  GPX_TRY(check_svgp(c, p, ntask, M));
+  GPX_NONNULL(c, Z);
+  GPX_NONNULL(c, X);
+  GPX_NONNULL(c, Y);
+  GPX_NONNULL(c, out);
+  GPX_NONNULL(c, info);
+  GPX_NONNULL(c, ws);
+  if (!(jitter >= 0.0)) return fail(c, GPX_INVALID_ARG, "jitter must be non-negative");
+  if (n < 1 || n > ((int64_t)1 << 40)) return fail(c, GPX_INVALID_ARG, "n must be in [1, 2^40]");
+  GPX_TRY(check_ld(c, ldz, p[0].d, "Z", false));
+  GPX_TRY(check_ld(c, ldx, p[0].d, "X", false));
+  GPX_TRY(check_ld(c, ldy, ntask, "Y", false));
+  if (ntask > 1 && stride_z < M * ldz) return fail(c, GPX_INVALID_ARG, "task stride of Z smaller than one task");
+  for (int64_t t = 0; t < ntask; ++t)
+    if (!(p[t].noise > 0.0)) return fail(c, GPX_INVALID_ARG, "the likelihood noise must be positive");
+  const int64_t Mpad = padded(M);
+  // the chunk width this workspace allows: the largest multiple of 128, at most the default (and the padded n)
+  int64_t C = GPX_SVGP_FIT_CHUNK < up128(n) ? GPX_SVGP_FIT_CHUNK : up128(n);
+  while (C >= 128 && svgp_grad_layout(Mpad, ntask, C).total + 256 > ws_bytes) C -= 128;
+  if (C < 128) return fail(c, GPX_INVALID_ARG, "svgp bound gradient workspace too small");
+  const SvgpGradLayout g = svgp_grad_layout(Mpad, ntask, C);
+  const SvgpFitLayout& lay = g.fit;
+  GPX_USE_DEVICE(c);
+  char* base = reinterpret_cast<char*>(align256(ws));
+  auto at = [&](int64_t t, size_t off) { return reinterpret_cast<double*>(base + lay.task * t + off); };
+  auto shared = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
+  const int64_t ts = (int64_t)(lay.task / sizeof(double));
+  // pass 1: the fit, keeping W and B'; then the bound while L' and u are in place
+  GPX_TRY(svgp_fit_core(c, p, ntask, M, Mpad, jitter, Z, ldz, stride_z, X, n, ldx, Y, ldy, info, lay, base, C, g.Wk,
+                        g.Bc));
+  for (int64_t t = 0; t < ntask; ++t) {
+    GPX_TRY(hip_check(c,
+                      gpx::launch_svgp_fit_bound(c, (int)Mpad, n, p[t].noise, at(t, lay.A), at(t, lay.u),
+                                                 at(t, lay.scal), at(t, g.bnd)),
+                      "svgp bound"));
+    GPX_TRY(hip_check(c, hipMemsetAsync(at(t, g.sc2), 0, g.bnd - g.sc2, c->stream), "memset"));
+  }
+  // between the passes: T1 = I - S -> A, Q -> X1; H = W T1 W^T -> Bc; G_A = W Q W^T / 2 -> A; c_v = W m
+  GPX_TRY(hip_check(c,
+                    gpx::launch_svgp_grad_sq(c, (int)ntask, (int)Mpad, ts, at(0, lay.Wb), at(0, g.Bc), at(0, lay.mrev),
+                                             at(0, lay.A), at(0, g.X1)),
+                    "svgp grad S"));
+  GPX_TRY(hip_check(c,
+                    gpx::launch_svgp_grad_unreverse(c, (int)ntask, (int)Mpad, ts, at(0, lay.mrev), at(0, lay.A),
+                                                    at(0, g.mnat), at(0, g.sc2)),
+                    "svgp grad m"));
+  gpx::Batch tv;
+  tv.count = (int)ntask;
+  tv.w = tv.y = tv.alpha = ts;
+  GPX_TRY(hip_check(c, gpx::launch_trmv_upper(c, (int)Mpad, at(0, g.Wk), Mpad, at(0, g.mnat), at(0, g.cv), tv),
+                    "svgp grad c_v"));
+  GPX_TRY(hip_check(c,
+                    gpx::launch_svgp_grad_conj(c, (int)ntask, (int)Mpad, ts, at(0, g.Wk), at(0, lay.A), 1.0,
+                                               at(0, lay.Wb), at(0, g.Bc)),
+                    "svgp grad H"));
+  GPX_TRY(hip_check(c,
+                    gpx::launch_svgp_grad_conj(c, (int)ntask, (int)Mpad, ts, at(0, g.Wk), at(0, g.X1), 0.5,
+                                               at(0, lay.Wb), at(0, lay.A)),
+                    "svgp grad G_A"));
+  for (int64_t t = 0; t < ntask; ++t)
+    GPX_TRY(hip_check(c,
+                      gpx::launch_svgp_grad_kzz(c, p[t], (int)M, (int)Mpad, Z + t * stride_z, ldz, at(t, lay.A),
+                                                shared(g.part), at(t, g.gacc)),
+                      "svgp grad K_ZZ"));
+  // pass 2: chunks outside, tasks inside, as in pass 1
+  for (int64_t s = 0; s < n; s += C) {
+    const int64_t mc = (n - s) < C ? (n - s) : C;
+    for (int64_t t = 0; t < ntask; ++t) {
+      GPX_TRY(hip_check(c,
+                        gpx::launch_svgp_kchunk(c, p[t], (int)M, (int)Mpad, Z + t * stride_z, ldz, at(t, g.cv),
+                                                X + s * ldx, ldx, mc, lay.ldk, shared(lay.kc), shared(lay.mu)),
+                        "svgp grad covariance"));
+      GPX_TRY(hip_check(c,
+                        gpx::launch_svgp_grad_chunk(c, p[t], (int)M, (int)Mpad, Z + t * stride_z, ldz, at(t, g.Bc),
+                                                    shared(lay.kc), shared(lay.mu), lay.ldk, X + s * ldx, ldx,
+                                                    Y + s * ldy + t, ldy, (int)mc, at(t, g.cv), shared(g.ev),
+                                                    at(t, g.sc2), shared(g.part), at(t, g.gacc)),
+                        "svgp grad chunk"));
+    }
+  }
+  for (int64_t t = 0; t < ntask; ++t)
+    GPX_TRY(hip_check(c,
+                      gpx::launch_svgp_grad_finish(c, p[t], (int)M, n, at(t, g.bnd), at(t, lay.scal), at(t, g.sc2),
+                                                   at(t, g.gacc), out + t * GPX_SVGP_GRAD_NOUT),
+                      "svgp grad finish"));
   return GPX_OK;
 }
 

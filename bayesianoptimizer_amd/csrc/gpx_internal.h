@@ -376,6 +376,28 @@ hipError_t launch_svgp_fit_utvec(Context* c, int ntask, int Mpad, const double* 
 hipError_t launch_svgp_fit_finish(Context* c, int M, int Mpad, int64_t n, double s2, const double* Lp, const double* Wp,
                                   const double* u, const double* mrev, const double* scal, double* vmean, double* vchol,
                                   int64_t ldc, double* bound);
+hipError_t launch_svgp_fit_bound(Context* c, int Mpad, int64_t n, double s2, const double* Lp, const double* u,
+                                 const double* scal, double* bound);
+// The bound's hyperparameter gradient (gpx_svgpgrad.hip).  Between the passes, all tasks per launch (task stride ts
+// doubles for every array): T1 = I - S and Q = 2I - S - B - m m^T in natural order from W', B', m' (reversed order);
+// out = scale W T W^T for a symmetric T (tmp: the intermediate W T); m in natural order and sc2[2] = tr T1.
+hipError_t launch_svgp_grad_sq(Context* c, int ntask, int Mpad, int64_t ts, const double* Wp, const double* Bp,
+                               const double* mrev, double* T1, double* Q);
+hipError_t launch_svgp_grad_conj(Context* c, int ntask, int Mpad, int64_t ts, const double* W, const double* T,
+                                 double scale, double* tmp, double* out);
+hipError_t launch_svgp_grad_unreverse(Context* c, int ntask, int Mpad, int64_t ts, const double* mrev, const double* T1,
+                                      double* mnat, double* sc2);
+// gacc (GPX_MLL_NOUT doubles, GPX_MLL_D_* slots) += sum G_A dK_ZZ/dtheta; part: (Mpad / 128)^2 rows of scratch
+hipError_t launch_svgp_grad_kzz(Context* c, const gpx_kernel_params& p, int M, int Mpad, const double* Z, int64_t ldz,
+                                const double* GA, double* part, double* gacc);
+// one chunk of one task behind launch_svgp_kchunk(alpha = c_v): e, sc2 += {sum e, e^T e, .., sum x_k^2 at 8 + k},
+// gacc += sum G_u dK_u/dtheta; part: (Mpad / 128) ceil(mc / 128) rows of scratch
+hipError_t launch_svgp_grad_chunk(Context* c, const gpx_kernel_params& p, int M, int Mpad, const double* Z, int64_t ldz,
+                                  const double* H, const double* kc, const double* mu, int64_t ldk, const double* X,
+                                  int64_t ldx, const double* Y, int64_t ldy, int mc, const double* cv, double* ev,
+                                  double* sc2, double* part, double* gacc);
+hipError_t launch_svgp_grad_finish(Context* c, const gpx_kernel_params& p, int M, int64_t n, const double* bound,
+                                   const double* scal, const double* sc2, const double* gacc, double* out);
 // SVGP preparation helpers (gpx_svgp.hip)
 hipError_t launch_svgp_pad(Context* c, int ntask, int M, int Mpad, const double* vmean, int64_t stride_m,
                            const double* vchol, int64_t ldc, int64_t stride_c, double* mpad, double* spad,

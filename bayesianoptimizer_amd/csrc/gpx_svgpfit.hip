@@ -249,4 +249,12 @@ hipError_t launch_svgp_fit_finish(Context* c, int M, int Mpad, int64_t n, double
   return hipGetLastError();
 }
 
+// The bound alone (gpx_svgp_bound_grad_f64): svgp_finish_kernel's workgroup 0 with no rows of vmean / vchol to write,
+// so the same arithmetic and the same bits as the fit's.
+hipError_t launch_svgp_fit_bound(Context* c, int Mpad, int64_t n, double s2, const double* Lp, const double* u,
+                                 const double* scal, double* bound) {
+  svgp_finish_kernel<<<1, WG, 0, c->stream>>>(0, Mpad, n, s2, Lp, nullptr, u, nullptr, scal, nullptr, nullptr, 0, bound);
+  return hipGetLastError();
+}
+
 }  // namespace gpx

@@ -1093,6 +1093,65 @@ class GPEngine:
                 raise err
         return vmean, vchol, bound
 
+    def svgp_bound_value_grad(self, params: Sequence[KernelParams], Z, X, Y, jitter: float = 1e-4,
+                              chunk: Optional[int] = None):
+        """The collapsed bound F of ``svgp_fit_collapsed`` and the gradient of -F with respect to the natural
+        hyperparameters of every task (gpx_svgp_bound_grad_f64: the fit's pass over X and a second one).  Arguments as
+        ``svgp_fit_collapsed``.  Returns a list of T host dicts with the keys ``mll._loss_grad`` reads: ``nll`` = -F,
+        ``noise``, ``outputscale``, ``const_mean``, ``lengthscale``, ``linear_variance`` (gradients of -F), and
+        ``bound`` (F and its five terms).  Raises NotPositiveDefiniteError naming the task whose K_ZZ failed.
+        Synchronises; the workspace is the engine's, reused across evaluations."""
+        out, info = self.svgp_bound_grad(params, Z, X, Y, jitter=jitter, chunk=chunk)
+        v = out.cpu().numpy()
+        bad = info.cpu().numpy()
+        for t in range(len(bad)):
+            err = info_error(int(bad[t]), f"task {t}: K_ZZ")
+            if err is not None:
+                raise err
+        d = X.shape[1]
+        res = []
+        for r in v:
+            g = r[_capi.SVGP_GRAD_MLL:]
+            res.append({
+                "nll": float(g[_capi.MLL_NLL]), "noise": float(g[_capi.MLL_D_NOISE]),
+                "outputscale": float(g[_capi.MLL_D_OUTPUTSCALE]), "const_mean": float(g[_capi.MLL_D_MEAN]),
+                "lengthscale": g[_capi.MLL_D_LENGTHSCALE:_capi.MLL_D_LENGTHSCALE + d].copy(),
+                "linear_variance": g[_capi.MLL_D_LINVAR:_capi.MLL_D_LINVAR + d].copy(),
+                "bound": r[_capi.SVGP_GRAD_BOUND:_capi.SVGP_GRAD_BOUND + _capi.SVGP_BOUND_NOUT].copy(),
+            })
+        return res
+
+    def svgp_bound_grad(self, params: Sequence[KernelParams], Z, X, Y, jitter: float = 1e-4,
+                        chunk: Optional[int] = None):
+        """The device side of ``svgp_bound_value_grad``: (out T x SVGP_GRAD_NOUT, info T) on the device, unchecked
+        (a task whose info is not 0 holds unspecified values) and without a synchronisation."""
+        Z = torch.as_tensor(Z).to(device=self.device, dtype=torch.float64)
+        if Z.dim() != 3:
+            raise ValueError("Z must be T x M x d")
+        if Z.stride(2) != 1 or Z.stride(1) < Z.shape[2] or (Z.shape[0] > 1 and Z.stride(0) < Z.shape[1] * Z.stride(1)):
+            Z = Z.contiguous()
+        X = self._rows_f64(X, "X")
+        Y = torch.as_tensor(Y)
+        Y = self._rows_f64(Y.unsqueeze(-1) if Y.dim() == 1 else Y, "Y")
+        T, M, d = Z.shape
+        n = X.shape[0]
+        if X.shape[1] != d or Y.shape != (n, T):
+            raise ValueError(f"X must be n x {d} and Y n x {T}")
+        if len(params) != T:
+            raise ValueError(f"expected {T} kernel parameter sets, got {len(params)}")
+        pcs = (KernelParamsC * T)(*[pp.to_c(d) for pp in params])
+        out = torch.empty((T, _capi.SVGP_GRAD_NOUT), dtype=torch.float64, device=self.device)
+        info = torch.zeros((T,), dtype=torch.int32, device=self.device)
+        nbytes = ctypes.c_size_t()
+        self._check(self.lib.gpx_svgp_bound_grad_workspace_size(M, n, T, int(chunk or 0), ctypes.byref(nbytes)))
+        ws = self.workspace("svgp_grad", nbytes.value)
+        self._bind_stream()
+        # (the library derives the chunk width from the size it is told, not from the cached buffer's)
+        self._check(self.lib.gpx_svgp_bound_grad_f64(
+            self.handle, pcs, T, M, float(jitter), _ptr(Z), Z.stride(1), Z.stride(0), _ptr(X), n, X.stride(0), _ptr(Y),
+            Y.stride(0), _ptr(out), _ptr(info), _ptr(ws), nbytes.value))
+        return out, info
+
     def topk(self, scores: torch.Tensor, k: int):
         """(values, indices) of the k largest scores, descending, ties -> lower index first (gpx_topk_f64)."""
         scores = scores.to(device=self.device, dtype=torch.float64).contiguous().reshape(-1)

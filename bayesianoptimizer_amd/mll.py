@@ -142,6 +142,13 @@ class HyperSpec:
     def bounds(self):
         return [h.raw_bounds() for h in self.hypers]
 
+    def raw_from_params(self, p: KernelParams) -> np.ndarray:
+        """The raw vector at which ``params_from_raw`` gives the fitted entries of ``p`` (a start from known values)."""
+        ls, lv = p.lengthscales(self.d), p.linear_variances(self.d)
+        nat = [ls[h.index] if h.name == "lengthscale" else lv[h.index] if h.name == "linear_variance"
+               else float(getattr(p, h.name)) for h in self.hypers]
+        return np.array([h.to_raw(v) for h, v in zip(self.hypers, nat)], dtype=np.float64)
+
 
 def default_spec(kind: str, d: int, prior_set: str = "dim_scaled", base: Optional[KernelParams] = None,
                  fit_mean: bool = True) -> HyperSpec:
@@ -354,3 +361,49 @@ def fit_hyperparameters_outputs(engine, X, Y, kind: str = "rbf", prior_set: str 
     return MLLFitOutputsResult(params=ps, loss=float(loss), nll=[float(g["nll"]) for g in final],
                                n_evals=int(res.nfev), success=bool(res.success), message=str(res.message),
                                raw=res.x.copy())
+
+
+def fit_hyperparameters_sparse(engine, X, Y, Z, kind: str = "scale_linear_matern52", prior_set: str = "none",
+                               bases: Optional[Sequence[KernelParams]] = None, fit_mean: bool = True,
+                               options: Optional[dict] = None, value_grad_all: Optional[Callable] = None,
+                               x0: Optional[Sequence[float]] = None, jitter: float = 1e-4) -> MLLFitOutputsResult:
+    """``fit_hyperparameters_outputs`` with the collapsed SVGP bound F in the place of the marginal likelihood: the
+    hyperparameters of T sparse models on inducing points Z (M x d shared, or T x M x d) that maximise F over all n
+    points.  F is the ELBO of optimization/Bayesian7.py:451-538 with q(u) already at its optimum, so its maximiser is
+    the fixed point of that joint training.  ONE L-BFGS-B over the concatenated raw vectors on the summed loss
+    (-F_t - log priors) / n; every evaluation is one batched GPU evaluation (GPEngine.svgp_bound_value_grad), a failed
+    K_ZZ scores +inf.  ``result.nll[t]`` = -F_t.  Tests inject a CPU reference through ``value_grad_all``."""
+    from scipy.optimize import minimize
+
+    Xn = np.asarray(X.cpu() if hasattr(X, "cpu") else X, dtype=np.float64)
+    Yn = np.asarray(Y.cpu() if hasattr(Y, "cpu") else Y, dtype=np.float64)
+    Yn = Yn.reshape(-1, 1) if Yn.ndim == 1 else Yn
+    n, d = Xn.shape
+    T = Yn.shape[1]
+    bases = list(bases) if bases is not None else [None] * T
+    if len(bases) != T:
+        raise ValueError(f"expected {T} base parameter sets, got {len(bases)}")
+    specs = [default_spec(kind, d, prior_set, bases[t], fit_mean) for t in range(T)]
+    if value_grad_all is None:
+        import torch
+
+        Zd = torch.as_tensor(Z).to(device=engine.device, dtype=torch.float64)
+        Zd = (Zd.unsqueeze(0).expand(T, -1, -1) if Zd.dim() == 2 else Zd).contiguous()
+        Xd = torch.as_tensor(X).to(device=engine.device, dtype=torch.float64)
+        Yd = torch.as_tensor(Yn).to(device=engine.device, dtype=torch.float64)
+
+        def value_grad_all(ps):
+            return engine.svgp_bound_value_grad(ps, Zd, Xd, Yd, jitter=jitter)
+
+    f = objective_outputs(specs, value_grad_all, n)
+    start = np.concatenate([sp.x0() for sp in specs]) if x0 is None else np.asarray(x0, dtype=np.float64)
+    bounds = [b for sp in specs for b in sp.bounds()]
+    res = minimize(f, start, jac=True, method="L-BFGS-B", bounds=bounds, options=options or {})
+    sizes = np.concatenate([[0], np.cumsum([len(sp.hypers) for sp in specs])])
+    ps = [sp.params_from_raw(res.x[sizes[t]:sizes[t + 1]]) for t, sp in enumerate(specs)]
+    loss, _ = f(res.x)
+    nll = [float("inf")] * T
+    if np.isfinite(loss):
+        nll = [float(g["nll"]) for g in value_grad_all(ps)]
+    return MLLFitOutputsResult(params=ps, loss=float(loss), nll=nll, n_evals=int(res.nfev), success=bool(res.success),
+                               message=str(res.message), raw=res.x.copy())

@@ -104,6 +104,12 @@ class GPConfig:
     # hyperparameters come as in the exact mode (subsample marginal likelihood, or the fixed values).  Only
     # acquisition="variance" (the reference's pool scan) runs on the sparse surrogate.
     large_n_model: str = "exact"
+    # where the sparse model's hyperparameters come from (with fit_hyperparameters): "subsample", the exact marginal
+    # likelihood on the svgp_threshold-point subsample (above), or "bound": the collapsed bound of the sparse model
+    # itself, maximised over all n points for the round's inducing points (SVGPModel.fit: what the reference's joint
+    # ELBO training converges to, Bayesian7.py:451-538), started from the previous round's values or, in the first
+    # sparse round, from the subsample fit
+    sparse_hyperparameters: str = "subsample"
     max_inducing_points: int = 2048
     inducing_subset_size: int = 10000
     # acquisition="qlogei": optimize_acqf settings of optimization/Bayesian.py:100-112
@@ -226,6 +232,8 @@ class BayesianOptimizer:
             raise ValueError(f"unknown acquisition '{self.acquisition}'")
         if self.config.large_n_model not in ("exact", "sparse"):
             raise ValueError(f"unknown GPConfig.large_n_model '{self.config.large_n_model}'")
+        if self.config.sparse_hyperparameters not in ("subsample", "bound"):
+            raise ValueError(f"unknown GPConfig.sparse_hyperparameters '{self.config.sparse_hyperparameters}'")
         if self._sparse_policy() and self.acquisition != "variance":
             raise ValueError(f"acquisition '{self.acquisition}' is not available with GPConfig.large_n_model='sparse': "
                              "the sparse surrogate serves acquisition='variance' (the pool scan) only")
@@ -250,6 +258,7 @@ class BayesianOptimizer:
                 self.test_X, self.test_Y_raw = self._tensor(self._to_unit(held_out[0])), self._tensor(held_out[1])
         self.gp_model: Optional[ExactGP] = None
         self._large_n_base: Optional[int] = None  # n at the last large-n rebuild
+        self.sparse_hyper_result = None  # sparse_hyperparameters="bound": the last round's MLLFitOutputsResult
         self.x_tf: Optional[LogInputStandardizer] = None
         self.y_tf: Optional[LogOutputStandardizer] = None
         self.iteration_counter = 0
@@ -409,24 +418,51 @@ class BayesianOptimizer:
         print(f"[gpx] n={n} > svgp_threshold={self.svgp_threshold}: hyperparameters from a {m}-point subsample")
         return sub_gp.params
 
+    def _bound_hyperparameters(self, n: int, Xs: torch.Tensor, Ys: torch.Tensor, params, Z):
+        """GPConfig.sparse_hyperparameters = "bound": the collapsed bound of the sparse model on Z, maximised over all n
+        points from ``params`` (one set per output)."""
+        from .mll import default_spec, fit_hyperparameters_sparse
+
+        cfg = self.config
+        T, d = Ys.shape[1], Xs.shape[1]
+        plist = [params] * T if isinstance(params, KernelParams) else list(params)
+        x0 = np.concatenate([default_spec(cfg.kernel, d, cfg.prior_set, p).raw_from_params(p) for p in plist])
+        res = fit_hyperparameters_sparse(self.engine, Xs, Ys, Z, cfg.kernel, cfg.prior_set, bases=plist,
+                                         options=cfg.mll_options, x0=x0, jitter=cfg.jitter_val)
+        print(f"[gpx] n={n}: sparse hyperparameters from the collapsed bound on all points ({res.n_evals} evaluations)")
+        self.sparse_hyper_result = res
+        return res.params if np.isfinite(res.loss) else plist
+
     def _fit_sparse(self, n: int, Ys: torch.Tensor):
         """n > svgp_threshold with GPConfig.large_n_model = "sparse": hyperparameters as in _fit_large_n, inducing points
         by select_inducing_points on the transformed inputs, the variational distribution in closed form; a fresh fit
-        every round (no n x n factor is ever held)."""
+        every round (no n x n factor is ever held).  GPConfig.sparse_hyperparameters = "bound": the inducing points
+        first, then the hyperparameters that maximise the sparse model's own bound over all n points."""
         from .svgp import select_inducing_points
 
         cfg = self.config
         prev = self.gp_model
         params = prev.params if prev is not None else self._kernel_params()
+        have_prev = prev is not None
         self.gp_model = prev = None
         self._large_n_base = None
         self.x_tf = LogInputStandardizer(self._bounds_t()).fit(self.train_X)
         Xs = self.x_tf(self.train_X)
-        if cfg.fit_hyperparameters:
-            params = self._subsample_hyperparameters(n, Xs, Ys, params, reference_jitter_schedule(cfg.jitter_val))
-        gen = torch.Generator().manual_seed(int(self._subsample_rng.integers(0, 2 ** 31 - 1)))
-        Z = select_inducing_points(Xs, cfg.max_inducing_points, cfg.inducing_subset_size, generator=gen,
-                                   engine=self.engine)
+
+        def inducing():
+            gen = torch.Generator().manual_seed(int(self._subsample_rng.integers(0, 2 ** 31 - 1)))
+            return select_inducing_points(Xs, cfg.max_inducing_points, cfg.inducing_subset_size, generator=gen,
+                                          engine=self.engine)
+
+        if cfg.fit_hyperparameters and cfg.sparse_hyperparameters == "bound":
+            Z = inducing()
+            if not have_prev:
+                params = self._subsample_hyperparameters(n, Xs, Ys, params, reference_jitter_schedule(cfg.jitter_val))
+            params = self._bound_hyperparameters(n, Xs, Ys, params, Z)
+        else:
+            if cfg.fit_hyperparameters:
+                params = self._subsample_hyperparameters(n, Xs, Ys, params, reference_jitter_schedule(cfg.jitter_val))
+            Z = inducing()
         self.gp_model = SparseGP(Xs, Ys, params, Z, jitter=cfg.jitter_val, engine=self.engine, input_transform=self.x_tf)
         return self.gp_model
 

@@ -8,7 +8,8 @@ comes from one of two places: a checkpoint the reference trained (``batch_svgp.p
 ``SVGPModel.from_state_dict``, or ``SVGPModel.fit_collapsed``: for given hyperparameters and inducing points the
 variational distribution the reference's Adam loop on the ELBO (``:451-538``) descends towards is known in closed form
 (Gaussian likelihood: Titsias' collapsed posterior), and ``gpx_svgp_fit_collapsed_f64`` computes it.
-Gradients of the bound, learning Z and minibatch training stay out of scope.
+``SVGPModel.fit`` also chooses the hyperparameters, by maximising that bound over all n points
+(``gpx_svgp_bound_grad_f64``).  Learning Z, minibatch training and non-Gaussian likelihoods stay out of scope.
 
 All arithmetic is fp64 (the reference model is float32; its variational jitter, 1e-4, is kept as the default).
 """
@@ -44,6 +45,7 @@ class SVGPModel:
     params: List[KernelParams]
     jitter: float = VARIATIONAL_JITTER_F32
     bound: Optional[torch.Tensor] = None  # fit_collapsed: T x 6 on the host, the collapsed bound F and its five terms
+    hyper_result: Optional[object] = None  # fit: the MLLFitOutputsResult of the hyperparameter search
 
     @property
     def num_tasks(self) -> int:
@@ -68,6 +70,33 @@ class SVGPModel:
         Z = Z.contiguous()
         vmean, vchol, bound = eng.svgp_fit_collapsed(plist, Z, X, Y, jitter=jitter)
         return cls(Z=Z, vmean=vmean, vchol=vchol, params=plist, jitter=jitter, bound=bound.cpu())
+
+    @classmethod
+    def fit(cls, X, Y, Z, params0: Union[KernelParams, Sequence[KernelParams]], prior_set: str = "none",
+            fit_mean: bool = True, options: Optional[dict] = None, jitter: float = VARIATIONAL_JITTER_F32,
+            engine: Optional[GPEngine] = None, value_grad_all=None) -> "SVGPModel":
+        """Hyperparameters and variational distribution together: the hyperparameters that maximise the collapsed
+        bound over all n points, starting from ``params0`` (``mll.fit_hyperparameters_sparse``: L-BFGS-B on
+        ``GPEngine.svgp_bound_value_grad``), then ``fit_collapsed`` at the result: the fixed point of the reference's
+        joint ELBO training (``optimization/Bayesian7.py:451-538``) for the given inducing points.  The optimiser's
+        result is kept as ``model.hyper_result``."""
+        from .mll import default_spec, fit_hyperparameters_sparse
+        import numpy as np
+
+        eng = engine or GPEngine()
+        Y = torch.as_tensor(Y)
+        if Y.dim() == 1:
+            Y = Y.unsqueeze(-1)
+        T, d = Y.shape[1], torch.as_tensor(X).shape[1]
+        plist = [params0] * T if isinstance(params0, KernelParams) else list(params0)
+        kind = plist[0].kind if isinstance(plist[0].kind, str) else \
+            {0: "rbf", 1: "matern52", 2: "scale_linear_matern52"}[int(plist[0].kind)]
+        x0 = np.concatenate([default_spec(kind, d, prior_set, p, fit_mean).raw_from_params(p) for p in plist])
+        res = fit_hyperparameters_sparse(eng, X, Y, Z, kind, prior_set, bases=plist, fit_mean=fit_mean, options=options,
+                                         value_grad_all=value_grad_all, x0=x0, jitter=jitter)
+        model = cls.fit_collapsed(X, Y, res.params, Z, jitter=jitter, engine=eng)
+        model.hyper_result = res
+        return model
 
     @classmethod
     def from_state_dict(cls, model_sd: dict, likelihood_sd: Optional[dict] = None,

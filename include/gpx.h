@@ -623,6 +623,34 @@ gpx_status gpx_svgp_fit_collapsed_f64(gpx_handle h, const gpx_kernel_params* p, 
                                       double* vchol, int64_t ldc, int64_t stride_c, double* bound, int32_t* info,
                                       void* ws, size_t ws_bytes);
 
+/* ---- Hyperparameter gradient of the collapsed bound ------------------------------------------------------------- */
+/* F(theta) of gpx_svgp_fit_collapsed_f64 (q(u) already at its optimum) and the gradient of -F with respect to the
+ * natural hyperparameters of every task: likelihood noise, outputscale, constant mean, lengthscales and linear variances
+ * (the jitter is a constant; Z is not differentiated).  One evaluation is the fit's pass over X and a second one: with
+ * c_v = W m, e = r - K(Z, X)^T c_v, H = W (I - S) W^T,
+ *   dF/dK(Z, X) = (H K(Z, X) + c_v e^T) / s2  is formed tile by tile and contracted with dK/dtheta on the spot,
+ *   dF/dK_ZZ    = W (2I - S - B - m m^T) W^T / 2,   dF/dk(x_i, x_i) = -1 / (2 s2).
+ * out (ntask x GPX_SVGP_GRAD_NOUT): F and its five terms in the GPX_SVGP_BOUND_* order (the bits
+ * gpx_svgp_fit_collapsed_f64 writes for equal inputs and an equal chunk width), then from GPX_SVGP_GRAD_MLL on a block
+ * in the layout of gpx_mll_grad_f64's output with -F in the place of -log p(y): out[GPX_SVGP_GRAD_MLL + GPX_MLL_NLL] =
+ * -F, [.. + GPX_MLL_D_NOISE], [.. + GPX_MLL_D_OUTPUTSCALE], [.. + GPX_MLL_D_MEAN], [.. + GPX_MLL_D_LENGTHSCALE + k],
+ * [.. + GPX_MLL_D_LINVAR + k] the derivatives of -F (QUAD, LOGDET and unused slots 0).
+ * Arguments, info and the chunk rule as gpx_svgp_fit_collapsed_f64: chunks and tasks run in stream order without
+ * floating-point atomics, so equal inputs and an equal chunk width give equal bits.
+ * Workspace: gpx_svgp_bound_grad_workspace_size(M, n, ntask, chunk); with Mpad = gpx_padded_n(M), C the chunk width and
+ * ldk = C rounded up to 256 it is about ntask 5 Mpad^2 8 + (1 + ntask) Mpad ldk 8 bytes (the fit's two matrices per
+ * task and three more: W kept, H, and dF/dK_ZZ's inner matrix), and does not depend on n. */
+enum {
+  GPX_SVGP_GRAD_BOUND = 0,  /* GPX_SVGP_BOUND_NOUT values: F and its five terms */
+  GPX_SVGP_GRAD_MLL = 8,    /* GPX_MLL_NOUT values in the GPX_MLL_* layout, of -F */
+  GPX_SVGP_GRAD_NOUT = 80
+};
+gpx_status gpx_svgp_bound_grad_workspace_size(int64_t M, int64_t n, int64_t ntask, int64_t chunk, size_t* bytes);
+gpx_status gpx_svgp_bound_grad_f64(gpx_handle h, const gpx_kernel_params* p, int64_t ntask, int64_t M, double jitter,
+                                   const double* Z, int64_t ldz, int64_t stride_z, const double* X, int64_t n,
+                                   int64_t ldx, const double* Y, int64_t ldy, double* out, int32_t* info, void* ws,
+                                   size_t ws_bytes);
+
 /* The k largest scores in descending order (replaces torch.topk, Bayesian7.py:681): stable, so equal scores keep
  * the lower index first; NaN ranks last.  idx_out: int64[k], val_out: double[k] (NULL = skip). */
 gpx_status gpx_topk_workspace_size(int64_t m, size_t* bytes);

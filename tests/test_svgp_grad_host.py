@@ -1,0 +1,188 @@
+"""Host checks of the collapsed bound's hyperparameter gradient (gpx_svgp_bound_grad_f64): the two CPU references of
+tests/sgpr_grad_ref.py against tests/sgpr_ref.py and against each other (which fixes the suite's tolerance tau), the
+L-BFGS-B driver mll.fit_hyperparameters_sparse with reference (a) injected, the C ABI's new symbols, and the drop-in's
+GPConfig.sparse_hyperparameters switch on the oracle engine."""
+import dataclasses
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+from bayesianoptimizer_amd import _capi
+from bayesianoptimizer_amd.mll import default_spec, fit_hyperparameters_sparse, objective_outputs
+from oracle import gp_oracle as O
+from tests import sgpr_grad_ref as G
+from tests import sgpr_ref as R
+from tests.oracle_engine import OracleEngine, to_oracle_params
+
+ORACLE_KIND = {"rbf": O.RBF, "matern52": O.MATERN52, "scale_linear_matern52": O.SCALE_LINEAR_MATERN52}
+
+
+@pytest.mark.parametrize("shape", [1, 2, 3, 4])
+@pytest.mark.parametrize("kind", G.KINDS)
+def test_autograd_bound_equals_the_fit_reference(shape, kind):
+    pb, kps, refs = G.reference(shape, kind)
+    for t, a in enumerate(refs):
+        op = dataclasses.replace(pb.ops[t], kind=ORACLE_KIND[kind])
+        F = R.fit_collapsed_task(pb.Z[t], pb.X, pb.Y[:, t], op)["F"]
+        assert abs(-a["nll"] - F) <= 1e-12 * abs(F), (shape, kind, t, -a["nll"], F)
+
+
+def test_formulas_equal_autograd_and_fix_the_tolerance():
+    """(b) against (a), entrywise against the sum of the absolute parts: tau0 is the largest ratio; the suite's tau =
+    32 tau0 (sgpr_grad_ref.TAU) must cover it with that margin and stay below 1e-6, or the H arrangement is the wrong
+    one to build."""
+    tau0, where = 0.0, None
+    for shape in (1, 2, 3, 4):
+        for kind in G.KINDS:
+            pb, kps, refs = G.reference(shape, kind)
+            for t, a in enumerate(refs):
+                b = G.formula_task(pb.Z[t], pb.X, pb.Y[:, t], kps[t])
+                ratio = G.entry_ratio(b, a)
+                assert abs(b["nll"] - a["nll"]) <= 1e-11 * np.abs(a["bound"][1:]).sum()
+                if ratio > tau0:
+                    tau0, where = ratio, (shape, kind, t)
+    print(f"tau0 = {tau0:.3e} at (shape, kind, task) = {where}; recorded TAU0 = {G.TAU0:.2e}, tau = {G.TAU:.2e}")
+    assert G.TAU <= 1e-6
+    assert tau0 <= 2.0 * G.TAU0, "the recorded tau0 no longer describes the references"
+
+
+# ---- the driver ---------------------------------------------------------------------------------------------------
+def small():
+    pb = G.make_problem(90, 14, 2, 2, 0.5, lambda t: 2e-2 * (t + 1), seed=5)
+    return pb, G.value_grad_all(pb.Z, pb.X, pb.Y)
+
+
+def test_fit_hyperparameters_sparse_descends_to_a_stationary_point():
+    pb, vg = small()
+    specs = [default_spec("rbf", 2, "none") for _ in range(2)]
+    f = objective_outputs(specs, vg, 90)
+    x0 = np.concatenate([sp.x0() for sp in specs])
+    v0, _ = f(x0)
+    res = fit_hyperparameters_sparse(None, pb.X, pb.Y, pb.Z, "rbf", "none", value_grad_all=vg)
+    assert np.isfinite(res.loss) and res.loss < v0 and len(res.params) == 2
+    assert np.isclose(res.loss, sum(res.nll) / 90, rtol=1e-12)  # no priors: the loss is the summed -F / n
+    tight = fit_hyperparameters_sparse(None, pb.X, pb.Y, pb.Z, "rbf", "none", value_grad_all=vg,
+                                       options={"ftol": 1e-15, "gtol": 1e-10, "maxiter": 2000})
+    v, g = f(tight.raw)
+    assert v <= res.loss + 1e-12
+    assert np.all(np.abs(g) < 1e-6), g  # every parameter of the "none" set is free (softplus / identity)
+    # a start from given parameters
+    x1 = np.concatenate([sp.raw_from_params(p) for sp, p in zip(specs, tight.params)])
+    np.testing.assert_allclose(x1, tight.raw, rtol=1e-9, atol=1e-9)
+
+
+def test_fit_hyperparameters_sparse_infeasible_start_is_inf():
+    pb, vg = small()
+    calls = []
+
+    def counted(ps):
+        calls.append(len(ps))
+        return vg(ps)
+
+    n_raw = 2 * len(default_spec("rbf", 2, "none").hypers)
+    res = fit_hyperparameters_sparse(None, pb.X, pb.Y, pb.Z, "rbf", "none", value_grad_all=counted,
+                                     x0=np.full(n_raw, -800.0))  # softplus underflows: lengthscale = 0
+    assert res.loss == np.inf and all(v == np.inf for v in res.nll) and not calls
+
+    def failing(ps):
+        raise np.linalg.LinAlgError("K_ZZ is not positive definite")
+
+    res = fit_hyperparameters_sparse(None, pb.X, pb.Y, pb.Z, "rbf", "none", value_grad_all=failing)
+    assert res.loss == np.inf
+
+
+# ---- the C ABI --------------------------------------------------------------------------------------------------
+NEW_SYMBOLS = ("gpx_svgp_bound_grad_workspace_size", "gpx_svgp_bound_grad_f64")
+
+
+def test_header_declares_and_library_exports_the_new_symbols():
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    header = open(os.path.join(root, "include", "gpx.h")).read()
+    for name in NEW_SYMBOLS:
+        assert re.search(r"gpx_status\s+" + name + r"\s*\(", header), name
+        assert name in _capi._PROTOS
+    for name, value in (("GPX_SVGP_GRAD_BOUND", _capi.SVGP_GRAD_BOUND), ("GPX_SVGP_GRAD_MLL", _capi.SVGP_GRAD_MLL),
+                        ("GPX_SVGP_GRAD_NOUT", _capi.SVGP_GRAD_NOUT)):
+        assert int(re.search(name + r"\s*=\s*(\d+)", header).group(1)) == value
+    assert _capi.SVGP_GRAD_NOUT == _capi.SVGP_GRAD_MLL + _capi.MLL_NOUT
+    if not os.path.exists(_capi.LIB_PATH):
+        pytest.skip("libgpx.so not built")
+    out = subprocess.run(["nm", "-D", "--defined-only", _capi.LIB_PATH], capture_output=True, text=True, check=True)
+    exported = {line.split()[-1] for line in out.stdout.splitlines() if line.strip()}
+    for name in NEW_SYMBOLS:
+        assert name in exported, name
+
+
+# ---- the drop-in's switch ---------------------------------------------------------------------------------------------
+class SparseOracleEngine(OracleEngine):
+    """The oracle engine with the sparse model's calls restated on the CPU: the closed-form fit (sgpr_ref), the
+    predictive (oracle) and the bound's value and gradient (reference (a))."""
+
+    device = torch.device("cpu")
+
+    def svgp_fit_collapsed(self, params, Z, X, Y, jitter=1e-4, chunk=None):
+        self.calls["svgp_fit"] = self.calls.get("svgp_fit", 0) + 1
+        Z, X, Y = (np.asarray(torch.as_tensor(v).cpu(), dtype=np.float64) for v in (Z, X, Y))
+        res = [R.fit_collapsed_task(Z[t], X, Y[:, t], to_oracle_params(p, X.shape[1]), jitter)
+               for t, p in enumerate(params)]
+        bound = np.stack([np.concatenate([[r["F"]], r["terms"]]) for r in res])
+        return (torch.tensor(np.stack([r["m"] for r in res])), torch.tensor(np.stack([r["C"] for r in res])),
+                torch.tensor(bound))
+
+    def svgp_bound_value_grad(self, params, Z, X, Y, jitter=1e-4, chunk=None):
+        self.calls.setdefault("bound_n", []).append(int(X.shape[0]))
+        Z, X, Y = (np.asarray(torch.as_tensor(v).cpu(), dtype=np.float64) for v in (Z, X, Y))
+        return [G.autograd_task(Z[t], X, Y[:, t], p, jitter) for t, p in enumerate(params)]
+
+    def svgp_prepare(self, params, Z, vmean, vchol, jitter=1e-4):
+        return {"Z": Z, "vmean": vmean, "vchol": vchol, "params": list(params), "jitter": jitter}
+
+    def svgp_predict(self, prep, Xs, min_var=1e-10, want=("mean", "var", "score")):
+        d = Xs.shape[1]
+        mu, var, score = O.svgp_predict(prep["Z"].numpy(), prep["vmean"].numpy(), prep["vchol"].numpy(),
+                                        [to_oracle_params(p, d) for p in prep["params"]], np.asarray(Xs),
+                                        jitter=prep["jitter"])
+        return torch.tensor(mu), torch.tensor(var), torch.tensor(score)
+
+
+def test_gpconfig_rejects_unknown_sparse_hyperparameters(tmp_path):
+    from bayesianoptimizer_amd.optimizer import BayesianOptimizer, GPConfig
+    from tests.stubs import BOUNDS, StubSimulator
+
+    assert GPConfig().sparse_hyperparameters == "subsample"
+    with pytest.raises(ValueError, match="sparse_hyperparameters"):
+        BayesianOptimizer(StubSimulator(), BOUNDS, str(tmp_path), n_initial_points=8, n_batches=1, batch_size=4,
+                          engine=OracleEngine(), gp_config=GPConfig(sparse_hyperparameters="nonsense"))
+
+
+def test_dropin_bound_mode_routes_through_the_sparse_driver(tmp_path):
+    """"bound": Z first, then the bound over ALL points (first sparse round: started from the subsample fit; later
+    rounds: from the previous round's parameters, no further subsample fit).  "subsample" never evaluates the bound."""
+    from bayesianoptimizer_amd.models import SparseGP
+    from bayesianoptimizer_amd.optimizer import BayesianOptimizer, GPConfig
+    from tests.stubs import BOUNDS, StubSimulator
+
+    runs = {}
+    for mode in ("bound", "subsample"):
+        cfg = GPConfig(candidates_pool_size=64, acq_batch_size=4, fit_hyperparameters=True, prior_set="none",
+                       mll_options={"maxiter": 3}, large_n_policy=True, large_n_model="sparse", max_inducing_points=8,
+                       sparse_hyperparameters=mode)
+        eng = SparseOracleEngine()
+        opt = BayesianOptimizer(StubSimulator(), BOUNDS, str(tmp_path / mode), n_initial_points=24, n_batches=1,
+                                batch_size=4, svgp_threshold=16, target_total=28, engine=eng, gp_config=cfg,
+                                acquisition="variance", seed=7)
+        opt.optimize()
+        opt.fit_gp_model()
+        assert isinstance(opt.gp_model, SparseGP) and opt.train_X.shape[0] == 28
+        runs[mode] = (eng, opt)
+    eng, opt = runs["bound"]
+    assert set(eng.calls["bound_n"]) == {24, 28}, eng.calls["bound_n"]  # all points, both rounds
+    assert eng.calls["mll_n"] == {16}, eng.calls["mll_n"]               # the subsample fit
+    assert opt.sparse_hyper_result is not None and np.isfinite(opt.sparse_hyper_result.loss)
+    assert [p.noise for p in opt.gp_model.params] == [p.noise for p in opt.sparse_hyper_result.params]
+    eng, opt = runs["subsample"]
+    assert "bound_n" not in eng.calls and opt.sparse_hyper_result is None
