@@ -85,8 +85,8 @@ gpx_status check_ld(Context* c, int64_t ld, int64_t minimum, const char* name, b
 #define GPX_NONNULL(c, ptr) \
   do { if (!(ptr)) return fail((c), GPX_INVALID_ARG, #ptr " is NULL"); } while (0)
 
-size_t trtri_ws(int64_t npad) { return (size_t)npad * npad / 4 * 8 + 256; }
-size_t alpha_ws(int64_t npad, int64_t nrhs) { return ((size_t)(npad / 128) + 1) * npad * nrhs * 8 + 512; }
+using gpx::alpha_ws;  // (gpx_svgp_layout.h)
+using gpx::trtri_ws;
 
 double* align256(void* p) {
   uintptr_t u = reinterpret_cast<uintptr_t>(p);
@@ -1470,24 +1470,10 @@ gpx_status gpx_argmax_combine_f64(gpx_handle h, const double* vals, const int64_
 }
 
 // ---- SVGP predictive + pool-scan selection --------------------------------------
+// The workspaces of the prepare, fit and gradient calls: gpx_svgp_layout.h.
 namespace {
-struct SvgpPrepLayout {
-  size_t L, dinv, slice, spad, mpad, total;  // byte offsets / sizes per task (256-aligned)
-};
-size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-SvgpPrepLayout svgp_prep_layout(int64_t Mpad) {
-  SvgpPrepLayout l;
-  const size_t L = al256((size_t)Mpad * Mpad * 8);
-  const size_t D = al256((size_t)2 * (Mpad / gpx::NB) * gpx::NB * gpx::NB * 8);
-  const size_t fs = al256(trtri_ws(Mpad) > alpha_ws(Mpad, 1) ? trtri_ws(Mpad) : alpha_ws(Mpad, 1));
-  l.L = 0;
-  l.dinv = L;
-  l.slice = L + D;
-  l.spad = L + D + fs;
-  l.mpad = l.spad + L;
-  l.total = l.mpad + al256((size_t)Mpad * 8);
-  return l;
-}
+using gpx::SvgpWorkspace;
+using gpx::up128;
 gpx_status check_svgp(Context* c, const gpx_kernel_params* p, int64_t ntask, int64_t M) {
   if (ntask < 1 || ntask > 64) return fail(c, GPX_INVALID_ARG, "ntask must be in [1, 64]");
   if (M < 1 || M > 65536) return fail(c, GPX_INVALID_ARG, "number of inducing points must be in [1, 65536]");
@@ -1498,11 +1484,33 @@ gpx_status check_svgp(Context* c, const gpx_kernel_params* p, int64_t ntask, int
   }
   return GPX_OK;
 }
+// W = (chol(K_ZZ + jitter I))^{-T} per task, batched over the tasks: K_ZZ into the tasks' A (the hyperparameters differ
+// per task; the likelihood noise is not part of K_ZZ), its factor in place, the inverse's transpose into W (wpitch
+// doubles between tasks).  *bt: the batch strides of the two launches.
+gpx_status svgp_inducing_factor(Context* c, const gpx_kernel_params* p, int64_t ntask, int64_t M, int64_t Mpad,
+                                double jitter, const double* Z, int64_t ldz, int64_t stride_z, const SvgpWorkspace& w,
+                                double* W, int64_t wpitch, int32_t* info, gpx::Batch* bt) {
+  for (int64_t t = 0; t < ntask; ++t) {
+    gpx_kernel_params q = p[t];
+    q.noise = 0.0;
+    q.jitter = jitter;
+    GPX_TRY(hip_check(c, gpx::launch_gram(c, q, (int)M, (int)Mpad, Z + t * stride_z, ldz, w.task(t, gpx::SV_A), Mpad),
+                      "gram"));
+  }
+  bt->count = (int)ntask;
+  bt->k = bt->dinv = bt->ws = w.pitch();
+  bt->w = wpitch;
+  GPX_TRY(hip_check(c, gpx::launch_potrf(c, (int)Mpad, w.task(0, gpx::SV_A), Mpad, w.task(0, gpx::SV_DINV), info, *bt),
+                    "potrf"));
+  return hip_check(c, gpx::launch_trtri(c, (int)Mpad, w.task(0, gpx::SV_A), Mpad, w.task(0, gpx::SV_DINV), W, Mpad,
+                                        w.task(0, gpx::SV_SLICE), *bt),
+                   "trtri");
+}
 }  // namespace
 
 gpx_status gpx_svgp_prepare_workspace_size(int64_t M, int64_t ntask, size_t* bytes) {
   if (!bytes || M < 1 || ntask < 1) return GPX_INVALID_ARG;
-  *bytes = svgp_prep_layout(padded(M)).total * (size_t)ntask + 256;
+  *bytes = gpx::svgp_layout(gpx::SVGP_PREPARE, padded(M), ntask).total + 256;
   return GPX_OK;
 }
 
@@ -1531,39 +1539,22 @@ gpx_status gpx_svgp_prepare_f64(gpx_handle h, const gpx_kernel_params* p, int64_
   GPX_TRY(gpx_svgp_prepare_workspace_size(M, ntask, &need));
   if (ws_bytes < need) return fail(c, GPX_INVALID_ARG, "svgp prepare workspace too small");
   GPX_USE_DEVICE(c);
-  const SvgpPrepLayout lay = svgp_prep_layout(Mpad);
-  char* base = reinterpret_cast<char*>(align256(ws));
-  auto at = [&](int64_t t, size_t off) { return reinterpret_cast<double*>(base + lay.total * t + off); };
-  const int64_t tstride = (int64_t)(lay.total / sizeof(double));  // elements between tasks in the workspace
+  const SvgpWorkspace w(ws, gpx::svgp_layout(gpx::SVGP_PREPARE, Mpad, ntask));
   GPX_TRY(hip_check(c, hipMemsetAsync(info, 0, sizeof(int32_t) * ntask, c->stream), "memset info"));
-  // K_ZZ + jitter I per task (the hyperparameters differ per task; the likelihood noise is not part of K_ZZ)
-  for (int64_t t = 0; t < ntask; ++t) {
-    gpx_kernel_params q = p[t];
-    q.noise = 0.0;
-    q.jitter = jitter;
-    GPX_TRY(hip_check(c, gpx::launch_gram(c, q, (int)M, (int)Mpad, Z + t * stride_z, ldz, at(t, lay.L), Mpad), "gram"));
-  }
   gpx::Batch bt;
-  bt.count = (int)ntask;
-  bt.k = tstride;
-  bt.dinv = tstride;
-  bt.ws = tstride;
-  bt.w = Mpad * Mpad;
-  GPX_TRY(hip_check(c, gpx::launch_potrf(c, (int)Mpad, at(0, lay.L), Mpad, at(0, lay.dinv), info, bt), "potrf"));
-  GPX_TRY(hip_check(c, gpx::launch_trtri(c, (int)Mpad, at(0, lay.L), Mpad, at(0, lay.dinv), W, Mpad, at(0, lay.slice),
-                                         bt),
-                    "trtri"));
+  GPX_TRY(svgp_inducing_factor(c, p, ntask, M, Mpad, jitter, Z, ldz, stride_z, w, W, Mpad * Mpad, info, &bt));
   // zero-padded m and S = tril(chol) in the workspace, then alpha' = W m and W2 = W S
   GPX_TRY(hip_check(c, gpx::launch_svgp_pad(c, (int)ntask, (int)M, (int)Mpad, vmean, stride_m, vchol, ldc, stride_c,
-                                            at(0, lay.mpad), at(0, lay.spad), tstride),
+                                            w.task(0, gpx::SV_MPAD), w.task(0, gpx::SV_SPAD), w.pitch()),
                     "svgp pad"));
   gpx::Batch tv;
   tv.count = (int)ntask;
   tv.w = Mpad * Mpad;
-  tv.y = tstride;
+  tv.y = w.pitch();
   tv.alpha = Mpad;
-  GPX_TRY(hip_check(c, gpx::launch_trmv_upper(c, (int)Mpad, W, Mpad, at(0, lay.mpad), alpha, tv), "alpha'"));
-  return hip_check(c, gpx::launch_svgp_w2(c, (int)ntask, (int)Mpad, W, at(0, lay.spad), tstride, W2), "svgp W2");
+  GPX_TRY(hip_check(c, gpx::launch_trmv_upper(c, (int)Mpad, W, Mpad, w.task(0, gpx::SV_MPAD), alpha, tv), "alpha'"));
+  return hip_check(c, gpx::launch_svgp_w2(c, (int)ntask, (int)Mpad, W, w.task(0, gpx::SV_SPAD), w.pitch(), W2),
+                   "svgp W2");
 }
 
 gpx_status gpx_svgp_predict_workspace_size(int64_t M, int64_t m, size_t* bytes) {
@@ -1619,336 +1610,233 @@ gpx_status gpx_svgp_predict_f64(gpx_handle h, const gpx_kernel_params* p, int64_
   return GPX_OK;
 }
 
-// ---- SVGP variational posterior in closed form (gpx_svgpfit.hip) --------------------------------------
+// ---- SVGP variational posterior in closed form (gpx_svgpfit.hip) and the hyperparameter gradient of its
+// ---- bound (gpx_svgpgrad.hip): the gradient call is the fit's launches up to m', then a second pass over X ----------
 namespace {
-// Per task: A (K_ZZ, then its factor, then B_acc / B' / L'), Wb (W = L_ZZ^{-T}, then W' = L'^{-T}), the diagonal-block
-// inverses, the triangular inverse's scratch, and the vectors b', u, m' with the three scalar sums.  By chunk width: the
-// covariance chunk (Mpad x ldk, shared), one projected chunk per task (the tasks' rank updates share a launch), the K*
-// build's mean partials (unused) and the chunk's residual.  Besides: a zero vector standing in for that build's alpha
-// and the second factorisation's info words.
-struct SvgpFitLayout {
-  size_t A, Wb, dinv, slice, bvec, u, mrev, scal, task;      // per task: byte offsets, and the task pitch
-  size_t kc, phi, phi_task, mu, zero, r, info2, total;       // shared: byte offsets from the base (phi_task: its pitch)
-  int64_t ldk;
-};
-int64_t up128(int64_t v) { return (v + 127) / 128 * 128; }
-// (extra: bytes appended to every task's block, for gpx_svgp_bound_grad_f64's SvgpGradLayout; 0 in the fit)
-size_t svgp_fit_fixed_bytes(int64_t Mpad, int64_t ntask, SvgpFitLayout* l, size_t extra = 0) {
-  const size_t mat = al256((size_t)Mpad * Mpad * 8), vec = al256((size_t)Mpad * 8);
-  l->A = 0;
-  l->Wb = mat;
-  l->dinv = 2 * mat;
-  l->slice = l->dinv + al256((size_t)2 * (Mpad / gpx::NB) * gpx::NB * gpx::NB * 8);
-  l->bvec = l->slice + al256(trtri_ws(Mpad));
-  l->u = l->bvec + vec;
-  l->mrev = l->u + vec;
-  l->scal = l->mrev + vec;
-  l->task = l->scal + 256 + extra;
-  return l->task * (size_t)ntask + vec /* zero */ + al256((size_t)ntask * 4) /* info2 */;
-}
-// bytes of the parts that scale with the chunk width C (a multiple of 128)
-size_t svgp_fit_chunk_bytes(int64_t Mpad, int64_t ntask, int64_t C) {
-  const size_t ldk = (size_t)((C + 255) / 256 * 256);
-  return (size_t)(1 + ntask) * al256((size_t)Mpad * ldk * 8) + al256((size_t)(Mpad / gpx::NB) * ldk * 8) +
-         al256(ldk * 8);
-}
-SvgpFitLayout svgp_fit_layout(int64_t Mpad, int64_t ntask, int64_t C, size_t extra = 0) {
-  SvgpFitLayout l;
-  const size_t fixed = svgp_fit_fixed_bytes(Mpad, ntask, &l, extra);
-  l.ldk = (C + 255) / 256 * 256;
-  l.zero = l.task * (size_t)ntask;
-  l.info2 = l.zero + al256((size_t)Mpad * 8);
-  l.kc = fixed;
-  l.phi_task = al256((size_t)Mpad * l.ldk * 8);
-  l.phi = l.kc + l.phi_task;
-  l.mu = l.phi + l.phi_task * (size_t)ntask;
-  l.r = l.mu + al256((size_t)(Mpad / gpx::NB) * l.ldk * 8);
-  l.total = fixed + svgp_fit_chunk_bytes(Mpad, ntask, C);
-  return l;
-}
-}  // namespace
-
-gpx_status gpx_svgp_fit_collapsed_workspace_size(int64_t M, int64_t n, int64_t ntask, int64_t chunk, size_t* bytes) {
+// The chunk width a size function reports for: the default, or `chunk` rounded up to 128.  0: invalid arguments.
+int64_t svgp_size_chunk(int64_t M, int64_t n, int64_t ntask, int64_t chunk, const size_t* bytes) {
   if (!bytes || M < 1 || M > 65536 || n < 1 || ntask < 1 || ntask > 64 || chunk < 0 || chunk > ((int64_t)1 << 20))
-    return GPX_INVALID_ARG;
-  int64_t C = chunk == 0 ? GPX_SVGP_FIT_CHUNK : up128(chunk);
-  if (C > up128(n)) C = up128(n);
-  *bytes = svgp_fit_layout(padded(M), ntask, C).total + 256;
+    return 0;
+  return chunk == 0 ? GPX_SVGP_FIT_CHUNK : up128(chunk);
+}
+// The argument checks of the fit and of the gradient.  outs: the call's own outputs, under the names the messages give
+// them.  q: the fit's {stride_m, ldc, stride_c} of the variational outputs; null in the gradient, which has none.
+gpx_status check_svgp_data(Context* c, const gpx_kernel_params* p, int64_t ntask, int64_t M, double jitter,
+                           const double* Z, int64_t ldz, int64_t stride_z, const double* X, int64_t n, int64_t ldx,
+                           const double* Y, int64_t ldy,
+                           std::initializer_list<std::pair<const void*, const char*>> outs, const int32_t* info,
+                           const void* ws, const int64_t* q) {
+  GPX_TRY(check_svgp(c, p, ntask, M));
+  GPX_NONNULL(c, Z);
+  GPX_NONNULL(c, X);
+  GPX_NONNULL(c, Y);
+  for (const auto& o : outs)
+    if (!o.first) return fail(c, GPX_INVALID_ARG, std::string(o.second) + " is NULL");
+  GPX_NONNULL(c, info);
+  GPX_NONNULL(c, ws);
+  if (!(jitter >= 0.0)) return fail(c, GPX_INVALID_ARG, "jitter must be non-negative");
+  if (n < 1 || n > ((int64_t)1 << 40)) return fail(c, GPX_INVALID_ARG, "n must be in [1, 2^40]");
+  GPX_TRY(check_ld(c, ldz, p[0].d, "Z", false));
+  GPX_TRY(check_ld(c, ldx, p[0].d, "X", false));
+  GPX_TRY(check_ld(c, ldy, ntask, "Y", false));
+  if (q) {
+    GPX_TRY(check_ld(c, q[1], M, "chol_variational_covar", false));
+    if (ntask > 1 && (stride_z < M * ldz || q[0] < M || q[2] < M * q[1]))
+      return fail(c, GPX_INVALID_ARG, "task strides smaller than one task");
+  } else if (ntask > 1 && stride_z < M * ldz) {
+    return fail(c, GPX_INVALID_ARG, "task stride of Z smaller than one task");
+  }
+  for (int64_t t = 0; t < ntask; ++t)
+    if (!(p[t].noise > 0.0)) return fail(c, GPX_INVALID_ARG, "the likelihood noise must be positive");
   return GPX_OK;
 }
-
-namespace {
 // The fit's launches up to m' (arguments checked by the entry points; the device is current): on return, per task, A
-// holds L' (B' = L' L'^T), Wb holds W' = L'^{-T}, and bvec / u / mrev / scal are final.  keepW / keepB (byte offsets in
-// the task's block, 0 = none): copies of W = L_ZZ^{-T} and of B' before they are overwritten.
+// holds L' (B' = L' L'^T), Wb holds W' = L'^{-T}, and bvec / u / mrev / scal are final.  Where the layout has Wk and Bc
+// (the gradient's), they get copies of W = L_ZZ^{-T} and of B' before those are overwritten.
 gpx_status svgp_fit_core(Context* c, const gpx_kernel_params* p, int64_t ntask, int64_t M, int64_t Mpad, double jitter,
                          const double* Z, int64_t ldz, int64_t stride_z, const double* X, int64_t n, int64_t ldx,
-                         const double* Y, int64_t ldy, int32_t* info, const SvgpFitLayout& lay, char* base, int64_t C,
-                         size_t keepW, size_t keepB) {
-  auto at = [&](int64_t t, size_t off) { return reinterpret_cast<double*>(base + lay.task * t + off); };
-  auto shared = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
-  int32_t* info2 = reinterpret_cast<int32_t*>(base + lay.info2);
-  const int64_t tstride = (int64_t)(lay.task / sizeof(double));
+                         const double* Y, int64_t ldy, int32_t* info, const SvgpWorkspace& w, int64_t C) {
+  using namespace gpx;  // (the region names)
+  const int64_t ldk = w.L.ldk, tstride = w.pitch(), pstride = w.phi_pitch();
+  int32_t* info2 = w.shared<int32_t>(SV_INFO2);
   GPX_TRY(hip_check(c, hipMemsetAsync(info, 0, sizeof(int32_t) * ntask, c->stream), "memset info"));
   GPX_TRY(hip_check(c, hipMemsetAsync(info2, 0, sizeof(int32_t) * ntask, c->stream), "memset info"));
-  GPX_TRY(hip_check(c, hipMemsetAsync(shared(lay.zero), 0, (size_t)Mpad * 8, c->stream), "memset"));
-  // W = (chol(K_ZZ + jitter I))^{-T} per task, as gpx_svgp_prepare_f64 builds it
-  for (int64_t t = 0; t < ntask; ++t) {
-    gpx_kernel_params q = p[t];
-    q.noise = 0.0;
-    q.jitter = jitter;
-    GPX_TRY(hip_check(c, gpx::launch_gram(c, q, (int)M, (int)Mpad, Z + t * stride_z, ldz, at(t, lay.A), Mpad), "gram"));
-  }
-  gpx::Batch bt;
-  bt.count = (int)ntask;
-  bt.k = bt.dinv = bt.ws = bt.w = tstride;
-  GPX_TRY(hip_check(c, gpx::launch_potrf(c, (int)Mpad, at(0, lay.A), Mpad, at(0, lay.dinv), info, bt), "potrf"));
-  GPX_TRY(hip_check(c, gpx::launch_trtri(c, (int)Mpad, at(0, lay.A), Mpad, at(0, lay.dinv), at(0, lay.Wb), Mpad,
-                                         at(0, lay.slice), bt),
-                    "trtri"));
-  if (keepW)  // (gpx_svgp_bound_grad_f64: W' will overwrite W below)
+  GPX_TRY(hip_check(c, hipMemsetAsync(w.shared(SV_ZERO), 0, (size_t)Mpad * 8, c->stream), "memset"));
+  Batch bt;
+  GPX_TRY(svgp_inducing_factor(c, p, ntask, M, Mpad, jitter, Z, ldz, stride_z, w, w.task(0, SV_WB), tstride, info,
+                               &bt));
+  if (w.task(0, SV_WK))  // (W' will overwrite W below)
     for (int64_t t = 0; t < ntask; ++t)
-      GPX_TRY(hip_check(c, hipMemcpyAsync(at(t, keepW), at(t, lay.Wb), (size_t)Mpad * Mpad * 8,
+      GPX_TRY(hip_check(c, hipMemcpyAsync(w.task(t, SV_WK), w.task(t, SV_WB), (size_t)Mpad * Mpad * 8,
                                           hipMemcpyDeviceToDevice, c->stream), "keep W"));
   // the accumulators: B_acc over the factor (no longer needed), b_acc and the scalar sums
   for (int64_t t = 0; t < ntask; ++t) {
-    GPX_TRY(hip_check(c, hipMemsetAsync(at(t, lay.A), 0, (size_t)Mpad * Mpad * 8, c->stream), "memset"));
-    GPX_TRY(hip_check(c, hipMemsetAsync(at(t, lay.bvec), 0, lay.scal + 256 - lay.bvec, c->stream), "memset"));
+    GPX_TRY(hip_check(c, hipMemsetAsync(w.task(t, SV_A), 0, (size_t)Mpad * Mpad * 8, c->stream), "memset"));
+    GPX_TRY(hip_check(c, hipMemsetAsync(w.task(t, w.L.acc), 0, w.L.acc.bytes, c->stream), "memset"));
   }
   // chunks outside, tasks inside: one fixed order of accumulation per task
-  const int64_t pstride = (int64_t)(lay.phi_task / sizeof(double));
   for (int64_t s = 0; s < n; s += C) {
     const int64_t mc = (n - s) < C ? (n - s) : C;
     for (int64_t t = 0; t < ntask; ++t) {
       GPX_TRY(hip_check(c,
-                        gpx::launch_svgp_kchunk(c, p[t], (int)M, (int)Mpad, Z + t * stride_z, ldz, shared(lay.zero),
-                                                X + s * ldx, ldx, mc, lay.ldk, shared(lay.kc), shared(lay.mu)),
+                        launch_svgp_kchunk(c, p[t], (int)M, (int)Mpad, Z + t * stride_z, ldz, w.shared(SV_ZERO),
+                                           X + s * ldx, ldx, mc, ldk, w.shared(SV_KC), w.shared(SV_MU)),
                         "svgp fit covariance"));
       GPX_TRY(hip_check(c,
-                        gpx::launch_svgp_fit_project(c, p[t], (int)Mpad, at(t, lay.Wb), shared(lay.kc),
-                                                     shared(lay.phi) + t * pstride, lay.ldk, X + s * ldx, ldx,
-                                                     Y + s * ldy + t, ldy, (int)mc, shared(lay.r), at(t, lay.bvec),
-                                                     at(t, lay.scal)),
+                        launch_svgp_fit_project(c, p[t], (int)Mpad, w.task(t, SV_WB), w.shared(SV_KC),
+                                                w.shared(SV_PHI) + t * pstride, ldk, X + s * ldx, ldx, Y + s * ldy + t,
+                                                ldy, (int)mc, w.shared(SV_R), w.task(t, SV_BVEC), w.task(t, SV_SCAL)),
                         "svgp fit projection"));
     }
     GPX_TRY(hip_check(c,
-                      gpx::launch_svgp_fit_syrk(c, (int)ntask, (int)Mpad, shared(lay.phi), pstride, lay.ldk, (int)mc,
-                                                at(0, lay.A), tstride),
+                      launch_svgp_fit_syrk(c, (int)ntask, (int)Mpad, w.shared(SV_PHI), pstride, ldk, (int)mc,
+                                           w.task(0, SV_A), tstride),
                       "svgp fit rank update"));
   }
   // B' = I + B_acc / s2 = L' L'^T and W' = L'^{-T} (in reversed index order), batched over the tasks
   for (int64_t t = 0; t < ntask; ++t)
     GPX_TRY(hip_check(c,
-                      gpx::launch_svgp_fit_system(c, (int)Mpad, p[t].noise, info + t, at(t, lay.A), at(t, lay.bvec),
-                                                  at(t, lay.scal)),
+                      launch_svgp_fit_system(c, (int)Mpad, p[t].noise, info + t, w.task(t, SV_A), w.task(t, SV_BVEC),
+                                             w.task(t, SV_SCAL)),
                       "svgp fit system"));
-  if (keepB)  // (B' on its lower 128-tiles, the others 0, before its factor overwrites it)
+  if (w.task(0, SV_BC))  // (B' on its lower 128-tiles, the others 0, before its factor overwrites it)
     for (int64_t t = 0; t < ntask; ++t)
-      GPX_TRY(hip_check(c, hipMemcpyAsync(at(t, keepB), at(t, lay.A), (size_t)Mpad * Mpad * 8,
+      GPX_TRY(hip_check(c, hipMemcpyAsync(w.task(t, SV_BC), w.task(t, SV_A), (size_t)Mpad * Mpad * 8,
                                           hipMemcpyDeviceToDevice, c->stream), "keep B"));
-  GPX_TRY(hip_check(c, gpx::launch_potrf(c, (int)Mpad, at(0, lay.A), Mpad, at(0, lay.dinv), info2, bt), "potrf B"));
-  GPX_TRY(hip_check(c, gpx::launch_trtri(c, (int)Mpad, at(0, lay.A), Mpad, at(0, lay.dinv), at(0, lay.Wb), Mpad,
-                                         at(0, lay.slice), bt),
+  GPX_TRY(hip_check(c, launch_potrf(c, (int)Mpad, w.task(0, SV_A), Mpad, w.task(0, SV_DINV), info2, bt), "potrf B"));
+  GPX_TRY(hip_check(c, launch_trtri(c, (int)Mpad, w.task(0, SV_A), Mpad, w.task(0, SV_DINV), w.task(0, SV_WB), Mpad,
+                                    w.task(0, SV_SLICE), bt),
                     "trtri B"));
   // u = W'^T b', m' = W' u
   GPX_TRY(hip_check(c,
-                    gpx::launch_svgp_fit_utvec(c, (int)ntask, (int)Mpad, at(0, lay.Wb), tstride, at(0, lay.bvec),
-                                               at(0, lay.u), tstride),
+                    launch_svgp_fit_utvec(c, (int)ntask, (int)Mpad, w.task(0, SV_WB), tstride, w.task(0, SV_BVEC),
+                                          w.task(0, SV_U), tstride),
                     "svgp fit u"));
-  gpx::Batch tv;
+  Batch tv;
   tv.count = (int)ntask;
   tv.w = tv.y = tv.alpha = tstride;
-  GPX_TRY(hip_check(c, gpx::launch_trmv_upper(c, (int)Mpad, at(0, lay.Wb), Mpad, at(0, lay.u), at(0, lay.mrev), tv),
-                    "svgp fit mean"));
-  return GPX_OK;
+  return hip_check(c, launch_trmv_upper(c, (int)Mpad, w.task(0, SV_WB), Mpad, w.task(0, SV_U), w.task(0, SV_MREV), tv),
+                   "svgp fit mean");
 }
 }  // namespace
+
+gpx_status gpx_svgp_fit_collapsed_workspace_size(int64_t M, int64_t n, int64_t ntask, int64_t chunk, size_t* bytes) {
+  int64_t C = svgp_size_chunk(M, n, ntask, chunk, bytes);
+  if (!C) return GPX_INVALID_ARG;
+  if (C > up128(n)) C = up128(n);
+  *bytes = gpx::svgp_layout(gpx::SVGP_FIT, padded(M), ntask, C).total + 256;
+  return GPX_OK;
+}
 
 gpx_status gpx_svgp_fit_collapsed_f64(gpx_handle h, const gpx_kernel_params* p, int64_t ntask, int64_t M, double jitter,
                                       const double* Z, int64_t ldz, int64_t stride_z, const double* X, int64_t n,
                                       int64_t ldx, const double* Y, int64_t ldy, double* vmean, int64_t stride_m,
                                       double* vchol, int64_t ldc, int64_t stride_c, double* bound, int32_t* info,
                                       void* ws, size_t ws_bytes) {
+  using namespace gpx;  // (the region names)
   Context* c = reinterpret_cast<Context*>(h);
   if (!c) return GPX_INVALID_ARG;
-  GPX_TRY(check_svgp(c, p, ntask, M));
-  GPX_NONNULL(c, Z);
-  GPX_NONNULL(c, X);
-  GPX_NONNULL(c, Y);
-  GPX_NONNULL(c, vmean);
-  GPX_NONNULL(c, vchol);
-  GPX_NONNULL(c, bound);
-  GPX_NONNULL(c, info);
-  GPX_NONNULL(c, ws);
-  if (!(jitter >= 0.0)) return fail(c, GPX_INVALID_ARG, "jitter must be non-negative");
-  if (n < 1 || n > ((int64_t)1 << 40)) return fail(c, GPX_INVALID_ARG, "n must be in [1, 2^40]");
-  GPX_TRY(check_ld(c, ldz, p[0].d, "Z", false));
-  GPX_TRY(check_ld(c, ldx, p[0].d, "X", false));
-  GPX_TRY(check_ld(c, ldy, ntask, "Y", false));
-  GPX_TRY(check_ld(c, ldc, M, "chol_variational_covar", false));
-  if (ntask > 1 && (stride_z < M * ldz || stride_m < M || stride_c < M * ldc))
-    return fail(c, GPX_INVALID_ARG, "task strides smaller than one task");
-  for (int64_t t = 0; t < ntask; ++t)
-    if (!(p[t].noise > 0.0)) return fail(c, GPX_INVALID_ARG, "the likelihood noise must be positive");
+  const int64_t q[3] = {stride_m, ldc, stride_c};
+  GPX_TRY(check_svgp_data(c, p, ntask, M, jitter, Z, ldz, stride_z, X, n, ldx, Y, ldy,
+                          {{vmean, "vmean"}, {vchol, "vchol"}, {bound, "bound"}}, info, ws, q));
   const int64_t Mpad = padded(M);
-  // the chunk width this workspace allows: the largest multiple of 128, at most the default (and the padded n)
-  SvgpFitLayout lay;
-  const size_t fixed = svgp_fit_fixed_bytes(Mpad, ntask, &lay) + 256;
-  int64_t C = GPX_SVGP_FIT_CHUNK < up128(n) ? GPX_SVGP_FIT_CHUNK : up128(n);
-  while (C >= 128 && fixed + svgp_fit_chunk_bytes(Mpad, ntask, C) > ws_bytes) C -= 128;
-  if (C < 128) return fail(c, GPX_INVALID_ARG, "svgp fit workspace too small");
-  lay = svgp_fit_layout(Mpad, ntask, C);
+  const int64_t C = svgp_chunk_width(SVGP_FIT, Mpad, ntask, n, GPX_SVGP_FIT_CHUNK, ws_bytes);
+  if (!C) return fail(c, GPX_INVALID_ARG, "svgp fit workspace too small");
+  const SvgpWorkspace w(ws, svgp_layout(SVGP_FIT, Mpad, ntask, C));
   GPX_USE_DEVICE(c);
-  char* base = reinterpret_cast<char*>(align256(ws));
-  auto at = [&](int64_t t, size_t off) { return reinterpret_cast<double*>(base + lay.task * t + off); };
-  GPX_TRY(svgp_fit_core(c, p, ntask, M, Mpad, jitter, Z, ldz, stride_z, X, n, ldx, Y, ldy, info, lay, base, C, 0, 0));
+  GPX_TRY(svgp_fit_core(c, p, ntask, M, Mpad, jitter, Z, ldz, stride_z, X, n, ldx, Y, ldy, info, w, C));
   for (int64_t t = 0; t < ntask; ++t)
     GPX_TRY(hip_check(c,
-                      gpx::launch_svgp_fit_finish(c, (int)M, (int)Mpad, n, p[t].noise, at(t, lay.A), at(t, lay.Wb),
-                                                  at(t, lay.u), at(t, lay.mrev), at(t, lay.scal),
-                                                  vmean + t * stride_m, vchol + t * stride_c, ldc,
-                                                  bound + t * GPX_SVGP_BOUND_NOUT),
+                      launch_svgp_fit_finish(c, (int)M, (int)Mpad, n, p[t].noise, w.task(t, SV_A), w.task(t, SV_WB),
+                                             w.task(t, SV_U), w.task(t, SV_MREV), w.task(t, SV_SCAL),
+                                             vmean + t * stride_m, vchol + t * stride_c, ldc,
+                                             bound + t * GPX_SVGP_BOUND_NOUT),
                       "svgp fit finish"));
   return GPX_OK;
 }
 
-// ---- Hyperparameter gradient of the collapsed bound (gpx_svgpgrad.hip) ----------------------------------
-namespace {
-// The fit's layout with a tail on every task's block: Wk (W = L_ZZ^{-T}, kept), Bc (B', then H), X1 (Q), the vectors
-// c_v and m (natural order), the second pass's scalar sums {sum e, e^T e, M - tr S, -, .., sum_i x_ik^2 at 8 + k}, the
-// gradient accumulator row and the bound's six values.  The fit's own matrices are reused between the passes: A holds
-// L', then T1 = I - S, then G_A; Wb holds W', then the products' intermediate U.  Shared, behind the fit's chunk part:
-// the chunk's residual e and the partial rows of one launch.  Bytes: (5 Mpad^2 + ..) 8 per task + (1 + T) Mpad ldk 8.
-struct SvgpGradLayout {
-  SvgpFitLayout fit;
-  size_t Wk, Bc, X1, cv, mnat, sc2, gacc, bnd;  // per task: byte offsets in the task's block
-  size_t ev, part, total;                       // shared: byte offsets from the base
-};
-size_t svgp_grad_extra(int64_t Mpad) {
-  return 3 * al256((size_t)Mpad * Mpad * 8) + 2 * al256((size_t)Mpad * 8) + 512 + al256(GPX_MLL_NOUT * 8) + 256;
-}
-size_t svgp_grad_shared_bytes(int64_t Mpad, int64_t C) {
-  const size_t nI = (size_t)(Mpad / 128), ncb = (size_t)(C / 128);
-  return al256((size_t)((C + 255) / 256 * 256) * 8) + al256(nI * (ncb > nI ? ncb : nI) * GPX_MLL_NOUT * 8);
-}
-SvgpGradLayout svgp_grad_layout(int64_t Mpad, int64_t ntask, int64_t C) {
-  SvgpGradLayout g;
-  g.fit = svgp_fit_layout(Mpad, ntask, C, svgp_grad_extra(Mpad));
-  const size_t mat = al256((size_t)Mpad * Mpad * 8), vec = al256((size_t)Mpad * 8);
-  g.Wk = g.fit.scal + 256;
-  g.Bc = g.Wk + mat;
-  g.X1 = g.Bc + mat;
-  g.cv = g.X1 + mat;
-  g.mnat = g.cv + vec;
-  g.sc2 = g.mnat + vec;
-  g.gacc = g.sc2 + 512;
-  g.bnd = g.gacc + al256(GPX_MLL_NOUT * 8);
-  g.ev = g.fit.total;
-  g.part = g.ev + al256((size_t)g.fit.ldk * 8);
-  g.total = g.fit.total + svgp_grad_shared_bytes(Mpad, C);
-  return g;
-}
-}  // namespace
-
 gpx_status gpx_svgp_bound_grad_workspace_size(int64_t M, int64_t n, int64_t ntask, int64_t chunk, size_t* bytes) {
-  if (!bytes || M < 1 || M > 65536 || n < 1 || ntask < 1 || ntask > 64 || chunk < 0 || chunk > ((int64_t)1 << 20))
-    return GPX_INVALID_ARG;
   // (the size does not depend on n: a chunk wider than n only leaves columns unused)
-  const int64_t C = chunk == 0 ? GPX_SVGP_FIT_CHUNK : up128(chunk);
-  *bytes = svgp_grad_layout(padded(M), ntask, C).total + 256;
+  const int64_t C = svgp_size_chunk(M, n, ntask, chunk, bytes);
+  if (!C) return GPX_INVALID_ARG;
+  *bytes = gpx::svgp_layout(gpx::SVGP_GRAD, padded(M), ntask, C, GPX_MLL_NOUT).total + 256;
   return GPX_OK;
 }
 
+// The fit's matrices are reused between the passes: A holds L', then T1 = I - S, then G_A; Wb holds W', then the
+// products' intermediate U.
 gpx_status gpx_svgp_bound_grad_f64(gpx_handle h, const gpx_kernel_params* p, int64_t ntask, int64_t M, double jitter,
                                    const double* Z, int64_t ldz, int64_t stride_z, const double* X, int64_t n,
                                    int64_t ldx, const double* Y, int64_t ldy, double* out, int32_t* info, void* ws,
                                    size_t ws_bytes) {
+  using namespace gpx;  // (the region names)
   Context* c = reinterpret_cast<Context*>(h);
   if (!c) return GPX_INVALID_ARG;
-  GPX_TRY(check_svgp(c, p, ntask, M));
-  GPX_NONNULL(c, Z);
-  GPX_NONNULL(c, X);
-  GPX_NONNULL(c, Y);
-  GPX_NONNULL(c, out);
-  GPX_NONNULL(c, info);
-  GPX_NONNULL(c, ws);
-  if (!(jitter >= 0.0)) return fail(c, GPX_INVALID_ARG, "jitter must be non-negative");
-  if (n < 1 || n > ((int64_t)1 << 40)) return fail(c, GPX_INVALID_ARG, "n must be in [1, 2^40]");
-  GPX_TRY(check_ld(c, ldz, p[0].d, "Z", false));
-  GPX_TRY(check_ld(c, ldx, p[0].d, "X", false));
-  GPX_TRY(check_ld(c, ldy, ntask, "Y", false));
-  if (ntask > 1 && stride_z < M * ldz) return fail(c, GPX_INVALID_ARG, "task stride of Z smaller than one task");
-  for (int64_t t = 0; t < ntask; ++t)
-    if (!(p[t].noise > 0.0)) return fail(c, GPX_INVALID_ARG, "the likelihood noise must be positive");
+  GPX_TRY(check_svgp_data(c, p, ntask, M, jitter, Z, ldz, stride_z, X, n, ldx, Y, ldy, {{out, "out"}}, info, ws,
+                          nullptr));
   const int64_t Mpad = padded(M);
-  // the chunk width this workspace allows: the largest multiple of 128, at most the default (and the padded n)
-  int64_t C = GPX_SVGP_FIT_CHUNK < up128(n) ? GPX_SVGP_FIT_CHUNK : up128(n);
-  while (C >= 128 && svgp_grad_layout(Mpad, ntask, C).total + 256 > ws_bytes) C -= 128;
-  if (C < 128) return fail(c, GPX_INVALID_ARG, "svgp bound gradient workspace too small");
-  const SvgpGradLayout g = svgp_grad_layout(Mpad, ntask, C);
-  const SvgpFitLayout& lay = g.fit;
+  const int64_t C = svgp_chunk_width(SVGP_GRAD, Mpad, ntask, n, GPX_SVGP_FIT_CHUNK, ws_bytes, GPX_MLL_NOUT);
+  if (!C) return fail(c, GPX_INVALID_ARG, "svgp bound gradient workspace too small");
+  const SvgpWorkspace w(ws, svgp_layout(SVGP_GRAD, Mpad, ntask, C, GPX_MLL_NOUT));
+  const int64_t ldk = w.L.ldk, ts = w.pitch();
   GPX_USE_DEVICE(c);
-  char* base = reinterpret_cast<char*>(align256(ws));
-  auto at = [&](int64_t t, size_t off) { return reinterpret_cast<double*>(base + lay.task * t + off); };
-  auto shared = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
-  const int64_t ts = (int64_t)(lay.task / sizeof(double));
   // pass 1: the fit, keeping W and B'; then the bound while L' and u are in place
-  GPX_TRY(svgp_fit_core(c, p, ntask, M, Mpad, jitter, Z, ldz, stride_z, X, n, ldx, Y, ldy, info, lay, base, C, g.Wk,
-                        g.Bc));
+  GPX_TRY(svgp_fit_core(c, p, ntask, M, Mpad, jitter, Z, ldz, stride_z, X, n, ldx, Y, ldy, info, w, C));
   for (int64_t t = 0; t < ntask; ++t) {
     GPX_TRY(hip_check(c,
-                      gpx::launch_svgp_fit_bound(c, (int)Mpad, n, p[t].noise, at(t, lay.A), at(t, lay.u),
-                                                 at(t, lay.scal), at(t, g.bnd)),
+                      launch_svgp_fit_bound(c, (int)Mpad, n, p[t].noise, w.task(t, SV_A), w.task(t, SV_U),
+                                            w.task(t, SV_SCAL), w.task(t, SV_BND)),
                       "svgp bound"));
-    GPX_TRY(hip_check(c, hipMemsetAsync(at(t, g.sc2), 0, g.bnd - g.sc2, c->stream), "memset"));
+    GPX_TRY(hip_check(c, hipMemsetAsync(w.task(t, w.L.acc2), 0, w.L.acc2.bytes, c->stream), "memset"));
   }
   // between the passes: T1 = I - S -> A, Q -> X1; H = W T1 W^T -> Bc; G_A = W Q W^T / 2 -> A; c_v = W m
   GPX_TRY(hip_check(c,
-                    gpx::launch_svgp_grad_sq(c, (int)ntask, (int)Mpad, ts, at(0, lay.Wb), at(0, g.Bc), at(0, lay.mrev),
-                                             at(0, lay.A), at(0, g.X1)),
+                    launch_svgp_grad_sq(c, (int)ntask, (int)Mpad, ts, w.task(0, SV_WB), w.task(0, SV_BC),
+                                        w.task(0, SV_MREV), w.task(0, SV_A), w.task(0, SV_X1)),
                     "svgp grad S"));
   GPX_TRY(hip_check(c,
-                    gpx::launch_svgp_grad_unreverse(c, (int)ntask, (int)Mpad, ts, at(0, lay.mrev), at(0, lay.A),
-                                                    at(0, g.mnat), at(0, g.sc2)),
+                    launch_svgp_grad_unreverse(c, (int)ntask, (int)Mpad, ts, w.task(0, SV_MREV), w.task(0, SV_A),
+                                               w.task(0, SV_MNAT), w.task(0, SV_SC2)),
                     "svgp grad m"));
-  gpx::Batch tv;
+  Batch tv;
   tv.count = (int)ntask;
   tv.w = tv.y = tv.alpha = ts;
-  GPX_TRY(hip_check(c, gpx::launch_trmv_upper(c, (int)Mpad, at(0, g.Wk), Mpad, at(0, g.mnat), at(0, g.cv), tv),
+  GPX_TRY(hip_check(c,
+                    launch_trmv_upper(c, (int)Mpad, w.task(0, SV_WK), Mpad, w.task(0, SV_MNAT), w.task(0, SV_CV), tv),
                     "svgp grad c_v"));
   GPX_TRY(hip_check(c,
-                    gpx::launch_svgp_grad_conj(c, (int)ntask, (int)Mpad, ts, at(0, g.Wk), at(0, lay.A), 1.0,
-                                               at(0, lay.Wb), at(0, g.Bc)),
+                    launch_svgp_grad_conj(c, (int)ntask, (int)Mpad, ts, w.task(0, SV_WK), w.task(0, SV_A), 1.0,
+                                          w.task(0, SV_WB), w.task(0, SV_BC)),
                     "svgp grad H"));
   GPX_TRY(hip_check(c,
-                    gpx::launch_svgp_grad_conj(c, (int)ntask, (int)Mpad, ts, at(0, g.Wk), at(0, g.X1), 0.5,
-                                               at(0, lay.Wb), at(0, lay.A)),
+                    launch_svgp_grad_conj(c, (int)ntask, (int)Mpad, ts, w.task(0, SV_WK), w.task(0, SV_X1), 0.5,
+                                          w.task(0, SV_WB), w.task(0, SV_A)),
                     "svgp grad G_A"));
   for (int64_t t = 0; t < ntask; ++t)
     GPX_TRY(hip_check(c,
-                      gpx::launch_svgp_grad_kzz(c, p[t], (int)M, (int)Mpad, Z + t * stride_z, ldz, at(t, lay.A),
-                                                shared(g.part), at(t, g.gacc)),
+                      launch_svgp_grad_kzz(c, p[t], (int)M, (int)Mpad, Z + t * stride_z, ldz, w.task(t, SV_A),
+                                           w.shared(SV_PART), w.task(t, SV_GACC)),
                       "svgp grad K_ZZ"));
   // pass 2: chunks outside, tasks inside, as in pass 1
   for (int64_t s = 0; s < n; s += C) {
     const int64_t mc = (n - s) < C ? (n - s) : C;
     for (int64_t t = 0; t < ntask; ++t) {
       GPX_TRY(hip_check(c,
-                        gpx::launch_svgp_kchunk(c, p[t], (int)M, (int)Mpad, Z + t * stride_z, ldz, at(t, g.cv),
-                                                X + s * ldx, ldx, mc, lay.ldk, shared(lay.kc), shared(lay.mu)),
+                        launch_svgp_kchunk(c, p[t], (int)M, (int)Mpad, Z + t * stride_z, ldz, w.task(t, SV_CV),
+                                           X + s * ldx, ldx, mc, ldk, w.shared(SV_KC), w.shared(SV_MU)),
                         "svgp grad covariance"));
       GPX_TRY(hip_check(c,
-                        gpx::launch_svgp_grad_chunk(c, p[t], (int)M, (int)Mpad, Z + t * stride_z, ldz, at(t, g.Bc),
-                                                    shared(lay.kc), shared(lay.mu), lay.ldk, X + s * ldx, ldx,
-                                                    Y + s * ldy + t, ldy, (int)mc, at(t, g.cv), shared(g.ev),
-                                                    at(t, g.sc2), shared(g.part), at(t, g.gacc)),
+                        launch_svgp_grad_chunk(c, p[t], (int)M, (int)Mpad, Z + t * stride_z, ldz, w.task(t, SV_BC),
+                                               w.shared(SV_KC), w.shared(SV_MU), ldk, X + s * ldx, ldx, Y + s * ldy + t,
+                                               ldy, (int)mc, w.task(t, SV_CV), w.shared(SV_EV), w.task(t, SV_SC2),
+                                               w.shared(SV_PART), w.task(t, SV_GACC)),
                         "svgp grad chunk"));
     }
   }
   for (int64_t t = 0; t < ntask; ++t)
     GPX_TRY(hip_check(c,
-                      gpx::launch_svgp_grad_finish(c, p[t], (int)M, n, at(t, g.bnd), at(t, lay.scal), at(t, g.sc2),
-                                                   at(t, g.gacc), out + t * GPX_SVGP_GRAD_NOUT),
+                      launch_svgp_grad_finish(c, p[t], (int)M, n, w.task(t, SV_BND), w.task(t, SV_SCAL),
+                                              w.task(t, SV_SC2), w.task(t, SV_GACC), out + t * GPX_SVGP_GRAD_NOUT),
                       "svgp grad finish"));
   return GPX_OK;
 }

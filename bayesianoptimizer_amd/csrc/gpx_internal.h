@@ -8,6 +8,7 @@
 #include <vector>
 #include "../../include/gpx.h"
 #include "gpx_sweep_layout.h"  // NB, TILE, TT, WG, the PRUNE_* sizes and the sweep's workspace layout
+#include "gpx_svgp_layout.h"   // the SVGP calls' workspace layout and its carve
 
 namespace gpx {
 
