@@ -45,7 +45,7 @@ TAU_MAX = 1e-2
 _LOG_SQRT_2PI = 0.5 * math.log(2.0 * math.pi)
 _LOG_SQRT_PI_DIV_2 = 0.5 * math.log(math.pi / 2.0)
 _INV_SQRT_2 = 1.0 / math.sqrt(2.0)
-_NEG_INV_SQRT_EPS = -1.0 / math.sqrt(np.finfo(np.float64).eps)
+_ASYMPTOTIC_BOUND = -1024.0  # log_ei_helper: erfcx form above, asymptotic series below
 GPYTORCH_MIN_VAR_F64 = 1e-10
 BOTORCH_MIN_VAR = 1e-12
 
@@ -162,15 +162,26 @@ def _log1mexp(x):
     return torch.where(x > -math.log(2.0), torch.log(-torch.expm1(xs)), torch.log1p(-torch.exp(torch.clamp(x, max=0.0))))
 
 
+def _ndtr(u):
+    """standard normal cdf with the branches of the GPU finalize kernel: through erfc away from zero, so the left tail
+    keeps its digits (0.5 (1 + erf) returns 0 from u = -8.3 down)"""
+    x = u * _INV_SQRT_2
+    half = 0.5 * torch.erfc(x.abs())
+    return torch.where(x.abs() < _INV_SQRT_2, 0.5 + 0.5 * torch.erf(x), torch.where(x > 0, 1.0 - half, half))
+
+
 def log_ei_helper(u):
-    """log(phi(u) + u Phi(u)) with the two-branch form of the GPU finalize kernel (gpx_sweep.hip)."""
+    """log(phi(u) + u Phi(u)) with the three-branch form of the GPU finalize kernel (gpx_sweep.hip): the log of the sum
+    down to -1, the erfcx form down to -1024, the asymptotic series below (oracle/gp_oracle.py: log_ei_helper)."""
     uu = torch.clamp(u, min=-1.0)
-    upper = torch.log(_phi(uu) + uu * torch.special.ndtr(uu))
+    upper = torch.log(_phi(uu) + uu * _ndtr(uu))
     u_lo = torch.clamp(u, max=-1.0)
-    u_eps = torch.clamp(u_lo, min=_NEG_INV_SQRT_EPS)
-    w = torch.log(torch.special.erfcx(-u_eps * _INV_SQRT_2) * u_eps.abs()) + _LOG_SQRT_PI_DIV_2
+    u_mid = torch.clamp(u_lo, min=_ASYMPTOTIC_BOUND)
+    w = torch.log(torch.special.erfcx(-u_mid * _INV_SQRT_2) * u_mid.abs()) + _LOG_SQRT_PI_DIV_2
     log_phi = -0.5 * u_lo * u_lo - _LOG_SQRT_2PI
-    lower = log_phi + torch.where(u_lo > _NEG_INV_SQRT_EPS, _log1mexp(w), -2.0 * torch.log(u_lo.abs()))
+    r = 1.0 / (u_lo * u_lo)
+    series = -2.0 * torch.log(u_lo.abs()) + torch.log1p(r * (15.0 * r - 3.0))
+    lower = log_phi + torch.where(u_lo > _ASYMPTOTIC_BOUND, _log1mexp(w), series)
     return torch.where(u > -1.0, upper, lower)
 
 
@@ -323,7 +334,7 @@ class AnalyticAcquisition:
             return mu + math.sqrt(self.beta) * sigma
         u = (mu - self.best_f) / sigma
         if self.kind == "ei":
-            return sigma * (_phi(u) + u * torch.special.ndtr(u))
+            return sigma * torch.clamp(_phi(u) + u * _ndtr(u), min=0.0)
         return log_ei_helper(u) + torch.log(sigma)
 
 

@@ -46,19 +46,29 @@ __device__ __forceinline__ double ei_helper_d(double u) { return phi_d(u) + u * 
 __device__ __forceinline__ double log1mexp_d(double x) {
   return (x > -0.69314718055994530941723212145818) ? log(-expm1(x)) : log1p(-exp(x));
 }
+// log(phi(u) + u Phi(u)): the log of the sum down to u = -1, the erfcx form down to -1024, the asymptotic series below.
+// The erfcx form takes log(1 - e^w) of w ~ -1/u^2, which it knows to ~1e-16 only: it loses u^2 eps of the sum, and at
+// BoTorch's hand-over -1/sqrt(eps) [upstream] the rounded w reaches 0 and beyond (log of zero or of a negative number).
+// The series u^-2 (1 - 3 u^-2 + 15 u^-4) loses 105 u^-6, below eps from 1024 on.
 __device__ __forceinline__ double log_ei_helper_d(double u) {
-  const double neg_inv_sqrt_eps = -67108864.0;  // -1/sqrt(2^-52)
+  const double asymptotic_bound = -1024.0;
   if (u > -1.0) return log(ei_helper_d(u));
-  const double u_eps = fmax(u, neg_inv_sqrt_eps);
-  const double w = log(erfcx(-u_eps * 0.70710678118654752440084436210485) * fabs(u_eps)) +
-                   0.22579135264472743236309761494744;  // log(sqrt(pi/2))
   const double log_phi = -0.5 * u * u - 0.91893853320467274178032973640562;  // log(sqrt(2 pi))
-  if (u > neg_inv_sqrt_eps) return log_phi + log1mexp_d(w);
-  return log_phi - 2.0 * log(fabs(u));
+  if (u > asymptotic_bound) {
+    const double w = log(erfcx(-u * 0.70710678118654752440084436210485) * fabs(u)) +
+                     0.22579135264472743236309761494744;  // log(sqrt(pi/2))
+    return log_phi + log1mexp_d(w);
+  }
+  const double r = 1.0 / (u * u);
+  return log_phi - 2.0 * log(fabs(u)) + log1p(r * (15.0 * r - 3.0));
 }
+// EI: phi(u) and Phi(u) are denormal below u ~ -37.5 and their difference may round below zero; EI is not negative.
 __device__ __forceinline__ double acq_score(int kind, double mu, double var, double best_f, double beta) {
   const double sigma = sqrt(var);
-  if (kind == GPX_ACQ_EI) return sigma * ei_helper_d((mu - best_f) / sigma);
+  if (kind == GPX_ACQ_EI) {
+    const double h = ei_helper_d((mu - best_f) / sigma);
+    return sigma * (h < 0.0 ? 0.0 : h);  // NaN stays NaN
+  }
   if (kind == GPX_ACQ_LOGEI) return log_ei_helper_d((mu - best_f) / sigma) + log(sigma);
   if (kind == GPX_ACQ_UCB) return mu + sqrt(beta) * sigma;
   return var;

@@ -64,7 +64,15 @@ enum {
 enum { GPX_KERNEL_RBF = 0, GPX_KERNEL_MATERN52 = 1, GPX_KERNEL_SCALE_LINEAR_MATERN52 = 2 };
 
 /* Acquisition scores (maximised). EI/LOGEI/UCB: BoTorch analytic forms [upstream] of the qLogEI call
- * (optimization/Bayesian.py:100-101); VARIANCE: the pool-scan score of optimization/Bayesian7.py:671. */
+ * (optimization/Bayesian.py:100-101); VARIANCE: the pool-scan score of optimization/Bayesian7.py:671.
+ * With sigma = sqrt(var), u = (mu - best_f) / sigma:
+ *   EI    = sigma (phi(u) + u Phi(u)), the plain sum as BoTorch's.  For u <= 0 its error is a few tens of eps of
+ *           sigma phi(u) (1 + |u|), the size of the two terms that cancel, not of the result (~ sigma phi(u) / u^2).
+ *           Below u ~ -37.5 Phi(u), then phi(u), are denormal: the result is then only bounded, 0 <= EI <= sigma phi(u)
+ *           (never negative), and it is 0 from u ~ -38.6 down.  Use LOGEI where improvements that small matter.
+ *   LOGEI = log EI in a stable form (the log of the sum down to u = -1, an erfcx form down to -1024, the asymptotic
+ *           series below): within a few tens of eps of 1 + |LOGEI| for every finite u; -inf where u^2 overflows
+ *           (|u| > 1.3e154). */
 enum { GPX_ACQ_EI = 0, GPX_ACQ_LOGEI = 1, GPX_ACQ_UCB = 2, GPX_ACQ_VARIANCE = 3 };
 
 /* Timers kept by gpx_timing_* (one per kernel family; gpx_timing_enable takes a bitmask of 1<<timer). */

@@ -404,7 +404,7 @@ def objective_posterior(states: Sequence[GPState], Xs: np.ndarray, weights, y_me
 _LOG_SQRT_2PI = 0.5 * math.log(2.0 * math.pi)
 _LOG_SQRT_PI_DIV_2 = 0.5 * math.log(math.pi / 2.0)
 _INV_SQRT_2 = 1.0 / math.sqrt(2.0)
-_NEG_INV_SQRT_EPS_F64 = -1.0 / math.sqrt(np.finfo(np.float64).eps)
+_ASYMPTOTIC_BOUND = -1024.0  # hand-over from the erfcx form to the asymptotic series of log_ei_helper
 
 
 def _phi(u):
@@ -427,14 +427,21 @@ def ei_helper(u):
 
 
 def log_ei_helper(u):
-    """log(phi(u) + u Phi(u)), stable for very negative u (two-branch form, bound = -1)."""
+    """log(phi(u) + u Phi(u)), stable for very negative u: log of the sum down to -1, the erfcx form down to
+    _ASYMPTOTIC_BOUND, the asymptotic series below.  The erfcx form takes log(1 - e^w) of w ~ -1/u^2, which it knows to
+    ~1e-16 only: it loses u^2 eps of the sum (all of it at BoTorch's hand-over -1/sqrt(eps) [upstream], where the
+    rounded w reaches 0 and beyond), the series u^-2 (1 - 3 u^-2 + 15 u^-4) loses 105 u^-6, which is below eps from
+    1024 on."""
     u = np.asarray(u, dtype=np.float64)
     upper = np.log(ei_helper(np.maximum(u, -1.0)))
     u_lo = np.minimum(u, -1.0)
-    u_eps = np.maximum(u_lo, _NEG_INV_SQRT_EPS_F64)
-    w = np.log(erfcx(-u_eps * _INV_SQRT_2) * np.abs(u_eps)) + _LOG_SQRT_PI_DIV_2
+    u_mid = np.maximum(u_lo, _ASYMPTOTIC_BOUND)
+    w = np.log(erfcx(-u_mid * _INV_SQRT_2) * np.abs(u_mid)) + _LOG_SQRT_PI_DIV_2
     log_phi = -0.5 * u * u - _LOG_SQRT_2PI
-    lower = log_phi + np.where(u > _NEG_INV_SQRT_EPS_F64, _log1mexp(w), -2.0 * np.log(np.abs(u_lo)))
+    with np.errstate(over="ignore"):
+        r = 1.0 / (u_lo * u_lo)
+    series = -2.0 * np.log(np.abs(u_lo)) + np.log1p(r * (15.0 * r - 3.0))
+    lower = log_phi + np.where(u > _ASYMPTOTIC_BOUND, _log1mexp(w), series)
     return np.where(u > -1.0, upper, lower)
 
 
@@ -445,7 +452,7 @@ def acquisition(mu, var, kind: int, best_f: float = 0.0, beta: float = 4.0):
     sigma = np.sqrt(var)
     if kind == ACQ_EI:
         u = (mu - best_f) / sigma
-        return sigma * ei_helper(u)
+        return sigma * np.maximum(ei_helper(u), 0.0)  # denormal phi, Phi (u < -37.5) may difference below zero
     if kind == ACQ_LOGEI:
         u = (mu - best_f) / sigma
         return log_ei_helper(u) + np.log(sigma)
