@@ -1763,21 +1763,41 @@ gpx_status gpx_svgp_bound_grad_workspace_size(int64_t M, int64_t n, int64_t ntas
   return GPX_OK;
 }
 
+gpx_status gpx_svgp_bound_grad_z_workspace_size(int64_t M, int64_t n, int64_t ntask, int64_t chunk, size_t* bytes) {
+  const int64_t C = svgp_size_chunk(M, n, ntask, chunk, bytes);
+  if (!C) return GPX_INVALID_ARG;
+  *bytes = gpx::svgp_layout(gpx::SVGP_GRAD_Z, padded(M), ntask, C, GPX_MLL_NOUT, GPX_MAX_DIM).total + 256;
+  return GPX_OK;
+}
+
+namespace {
+// The driver of both gradient calls.  zg: gpx_svgp_bound_grad_z_f64, whose layout has the two regions of dF/dZ; the
+// K_ZZ contraction and the chunks' tile contractions then also fill them (null pointers otherwise: not wanted).
 // The fit's matrices are reused between the passes: A holds L', then T1 = I - S, then G_A; Wb holds W', then the
 // products' intermediate U.
-gpx_status gpx_svgp_bound_grad_f64(gpx_handle h, const gpx_kernel_params* p, int64_t ntask, int64_t M, double jitter,
-                                   const double* Z, int64_t ldz, int64_t stride_z, const double* X, int64_t n,
-                                   int64_t ldx, const double* Y, int64_t ldy, double* out, int32_t* info, void* ws,
-                                   size_t ws_bytes) {
+gpx_status svgp_bound_grad_driver(gpx_handle h, const gpx_kernel_params* p, int64_t ntask, int64_t M, double jitter,
+                                  const double* Z, int64_t ldz, int64_t stride_z, const double* X, int64_t n,
+                                  int64_t ldx, const double* Y, int64_t ldy, double* out, bool zg, double* dZ,
+                                  int64_t lddz, int64_t stride_dz, int32_t* info, void* ws, size_t ws_bytes) {
   using namespace gpx;  // (the region names)
   Context* c = reinterpret_cast<Context*>(h);
   if (!c) return GPX_INVALID_ARG;
-  GPX_TRY(check_svgp_data(c, p, ntask, M, jitter, Z, ldz, stride_z, X, n, ldx, Y, ldy, {{out, "out"}}, info, ws,
-                          nullptr));
+  if (zg)
+    GPX_TRY(check_svgp_data(c, p, ntask, M, jitter, Z, ldz, stride_z, X, n, ldx, Y, ldy, {{out, "out"}, {dZ, "dZ"}},
+                            info, ws, nullptr));
+  else
+    GPX_TRY(check_svgp_data(c, p, ntask, M, jitter, Z, ldz, stride_z, X, n, ldx, Y, ldy, {{out, "out"}}, info, ws,
+                            nullptr));
+  if (zg) {
+    GPX_TRY(check_ld(c, lddz, p[0].d, "dZ", false));
+    if (ntask > 1 && stride_dz < M * lddz) return fail(c, GPX_INVALID_ARG, "task stride of dZ smaller than one task");
+  }
   const int64_t Mpad = padded(M);
-  const int64_t C = svgp_chunk_width(SVGP_GRAD, Mpad, ntask, n, GPX_SVGP_FIT_CHUNK, ws_bytes, GPX_MLL_NOUT);
+  const SvgpKind kind = zg ? SVGP_GRAD_Z : SVGP_GRAD;
+  const int64_t zdim = zg ? GPX_MAX_DIM : 0;
+  const int64_t C = svgp_chunk_width(kind, Mpad, ntask, n, GPX_SVGP_FIT_CHUNK, ws_bytes, GPX_MLL_NOUT, zdim);
   if (!C) return fail(c, GPX_INVALID_ARG, "svgp bound gradient workspace too small");
-  const SvgpWorkspace w(ws, svgp_layout(SVGP_GRAD, Mpad, ntask, C, GPX_MLL_NOUT));
+  const SvgpWorkspace w(ws, svgp_layout(kind, Mpad, ntask, C, GPX_MLL_NOUT, zdim));
   const int64_t ldk = w.L.ldk, ts = w.pitch();
   GPX_USE_DEVICE(c);
   // pass 1: the fit, keeping W and B'; then the bound while L' and u are in place
@@ -1815,7 +1835,7 @@ gpx_status gpx_svgp_bound_grad_f64(gpx_handle h, const gpx_kernel_params* p, int
   for (int64_t t = 0; t < ntask; ++t)
     GPX_TRY(hip_check(c,
                       launch_svgp_grad_kzz(c, p[t], (int)M, (int)Mpad, Z + t * stride_z, ldz, w.task(t, SV_A),
-                                           w.shared(SV_PART), w.task(t, SV_GACC)),
+                                           w.shared(SV_PART), w.task(t, SV_GACC), w.task(t, SV_ZACC)),
                       "svgp grad K_ZZ"));
   // pass 2: chunks outside, tasks inside, as in pass 1
   for (int64_t s = 0; s < n; s += C) {
@@ -1829,16 +1849,35 @@ gpx_status gpx_svgp_bound_grad_f64(gpx_handle h, const gpx_kernel_params* p, int
                         launch_svgp_grad_chunk(c, p[t], (int)M, (int)Mpad, Z + t * stride_z, ldz, w.task(t, SV_BC),
                                                w.shared(SV_KC), w.shared(SV_MU), ldk, X + s * ldx, ldx, Y + s * ldy + t,
                                                ldy, (int)mc, w.task(t, SV_CV), w.shared(SV_EV), w.task(t, SV_SC2),
-                                               w.shared(SV_PART), w.task(t, SV_GACC)),
+                                               w.shared(SV_PART), w.task(t, SV_GACC), w.shared(SV_ZPART),
+                                               w.task(t, SV_ZACC)),
                         "svgp grad chunk"));
     }
   }
   for (int64_t t = 0; t < ntask; ++t)
     GPX_TRY(hip_check(c,
                       launch_svgp_grad_finish(c, p[t], (int)M, n, w.task(t, SV_BND), w.task(t, SV_SCAL),
-                                              w.task(t, SV_SC2), w.task(t, SV_GACC), out + t * GPX_SVGP_GRAD_NOUT),
+                                              w.task(t, SV_SC2), w.task(t, SV_GACC), out + t * GPX_SVGP_GRAD_NOUT,
+                                              w.task(t, SV_ZACC), zg ? dZ + t * stride_dz : nullptr, lddz),
                       "svgp grad finish"));
   return GPX_OK;
+}
+}  // namespace
+
+gpx_status gpx_svgp_bound_grad_f64(gpx_handle h, const gpx_kernel_params* p, int64_t ntask, int64_t M, double jitter,
+                                   const double* Z, int64_t ldz, int64_t stride_z, const double* X, int64_t n,
+                                   int64_t ldx, const double* Y, int64_t ldy, double* out, int32_t* info, void* ws,
+                                   size_t ws_bytes) {
+  return svgp_bound_grad_driver(h, p, ntask, M, jitter, Z, ldz, stride_z, X, n, ldx, Y, ldy, out, false, nullptr, 0, 0,
+                                info, ws, ws_bytes);
+}
+
+gpx_status gpx_svgp_bound_grad_z_f64(gpx_handle h, const gpx_kernel_params* p, int64_t ntask, int64_t M, double jitter,
+                                     const double* Z, int64_t ldz, int64_t stride_z, const double* X, int64_t n,
+                                     int64_t ldx, const double* Y, int64_t ldy, double* out, double* dZ, int64_t lddz,
+                                     int64_t stride_dz, int32_t* info, void* ws, size_t ws_bytes) {
+  return svgp_bound_grad_driver(h, p, ntask, M, jitter, Z, ldz, stride_z, X, n, ldx, Y, ldy, out, true, dZ, lddz,
+                                stride_dz, info, ws, ws_bytes);
 }
 
 gpx_status gpx_topk_workspace_size(int64_t m, size_t* bytes) {

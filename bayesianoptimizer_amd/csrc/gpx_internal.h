@@ -388,17 +388,21 @@ hipError_t launch_svgp_grad_conj(Context* c, int ntask, int Mpad, int64_t ts, co
                                  double scale, double* tmp, double* out);
 hipError_t launch_svgp_grad_unreverse(Context* c, int ntask, int Mpad, int64_t ts, const double* mrev, const double* T1,
                                       double* mnat, double* sc2);
-// gacc (GPX_MLL_NOUT doubles, GPX_MLL_D_* slots) += sum G_A dK_ZZ/dtheta; part: (Mpad / 128)^2 rows of scratch
+// gacc (GPX_MLL_NOUT doubles, GPX_MLL_D_* slots) += sum G_A dK_ZZ/dtheta; part: (Mpad / 128)^2 rows of scratch.
+// zacc (the inducing-location gradient's accumulator, Mpad rows of dmax(d) doubles; null: not wanted) = its K_ZZ part
 hipError_t launch_svgp_grad_kzz(Context* c, const gpx_kernel_params& p, int M, int Mpad, const double* Z, int64_t ldz,
-                                const double* GA, double* part, double* gacc);
+                                const double* GA, double* part, double* gacc, double* zacc);
 // one chunk of one task behind launch_svgp_kchunk(alpha = c_v): e, sc2 += {sum e, e^T e, .., sum x_k^2 at 8 + k},
-// gacc += sum G_u dK_u/dtheta; part: (Mpad / 128) ceil(mc / 128) rows of scratch
+// gacc += sum G_u dK_u/dtheta; part: (Mpad / 128) ceil(mc / 128) rows of scratch.  With zacc: zacc += the chunk's part of
+// dF/dZ through K_u, the tiles' row partials passing through zpart ((Mpad / 128) ceil(mc / 128) blocks of 128 x dmax(d))
 hipError_t launch_svgp_grad_chunk(Context* c, const gpx_kernel_params& p, int M, int Mpad, const double* Z, int64_t ldz,
                                   const double* H, const double* kc, const double* mu, int64_t ldk, const double* X,
                                   int64_t ldx, const double* Y, int64_t ldy, int mc, const double* cv, double* ev,
-                                  double* sc2, double* part, double* gacc);
+                                  double* sc2, double* part, double* gacc, double* zpart, double* zacc);
+// (with zacc: dZ[a][k] = -zacc[a][k] for a < M, k < d, rows lddz apart)
 hipError_t launch_svgp_grad_finish(Context* c, const gpx_kernel_params& p, int M, int64_t n, const double* bound,
-                                   const double* scal, const double* sc2, const double* gacc, double* out);
+                                   const double* scal, const double* sc2, const double* gacc, double* out,
+                                   const double* zacc, double* dZ, int64_t lddz);
 // SVGP preparation helpers (gpx_svgp.hip)
 hipError_t launch_svgp_pad(Context* c, int ntask, int M, int Mpad, const double* vmean, int64_t stride_m,
                            const double* vchol, int64_t ldc, int64_t stride_c, double* mpad, double* spad,

@@ -1,7 +1,8 @@
-// The one description of the SVGP calls' workspaces: gpx_svgp_prepare_f64, gpx_svgp_fit_collapsed_f64 and
-// gpx_svgp_bound_grad_f64.  svgp_layout walks every region once with a bump cursor; the reported sizes, the chunk width
+// The one description of the SVGP calls' workspaces: gpx_svgp_prepare_f64, gpx_svgp_fit_collapsed_f64,
+// gpx_svgp_bound_grad_f64 and gpx_svgp_bound_grad_z_f64.  svgp_layout walks every region once with a bump cursor; the reported sizes, the chunk width
 // a given workspace allows (svgp_chunk_width) and the pointers the launches get (SvgpWorkspace) all come from it.  The
-// fit is the gradient's layout without the gradient's regions.  No HIP in here: tests/host/svgp_layout_check.cpp
+// fit is the gradient's layout without the gradient's regions, and the inducing-location gradient's is the gradient's
+// plus two regions.  No HIP in here: tests/host/svgp_layout_check.cpp
 // compiles this file alone with the host compiler and checks it against a second statement of the layout.
 #pragma once
 #include <cstddef>
@@ -41,6 +42,7 @@ enum SvgpRegion {
   SV_SC2,    // 512 bytes: the second pass's sums {sum e, e^T e, M - tr S, -, .., sum_i x_ik^2 at 8 + k}
   SV_GACC,   // the gradient accumulator row (nout doubles)
   SV_BND,    // 256 bytes: the bound's six values
+  SV_ZACC,   // inducing-location gradient: the accumulator of dF/dZ, Mpad rows of zdim doubles
   // shared
   SV_ZERO,   // fit: Mpad zeros, standing in for the K* build's alpha
   SV_INFO2,  // ntask int32: the second factorisation's info words
@@ -50,10 +52,14 @@ enum SvgpRegion {
   SV_R,      // the chunk's residual, ldk
   SV_EV,     // gradient: the chunk's residual e, ldk
   SV_PART,   // the partial rows of one launch: (Mpad/128) max(Mpad/128, C/128) rows of nout doubles
+  SV_ZPART,  // inducing-location gradient: one launch's row partials, (Mpad/128) (C/128) blocks of 128 x zdim doubles;
+             // sized like SV_PART, for (Mpad/128) max(Mpad/128, C/128) blocks: two chunk widths whose gradient layouts
+             // have one size then have one size here too, so a workspace sized for `chunk` by either gradient call's
+             // size function gives both calls the same chunk width (and with it the same bits of `out`)
   SV_REGIONS,
   SV_SHARED = SV_ZERO  // the first shared region
 };
-enum SvgpKind { SVGP_PREPARE, SVGP_FIT, SVGP_GRAD };
+enum SvgpKind { SVGP_PREPARE, SVGP_FIT, SVGP_GRAD, SVGP_GRAD_Z };
 
 struct SvgpLayout {
   struct Region { size_t at = 0, bytes = 0; };  // bytes = 0: not in this call's workspace
@@ -68,10 +74,11 @@ struct SvgpLayout {
 };
 
 // Mpad: padded M; C: chunk width, a multiple of 128 (not used by prepare); nout: doubles of a gradient row
-// (GPX_MLL_NOUT; the gradient only).
-inline SvgpLayout svgp_layout(SvgpKind kind, int64_t Mpad, int64_t ntask, int64_t C = 0, int64_t nout = 0) {
+// (GPX_MLL_NOUT; the gradients only); zdim: doubles of a row of dF/dZ (GPX_MAX_DIM; SVGP_GRAD_Z only).
+inline SvgpLayout svgp_layout(SvgpKind kind, int64_t Mpad, int64_t ntask, int64_t C = 0, int64_t nout = 0,
+                              int64_t zdim = 0) {
   SvgpLayout L;
-  const bool prep = kind == SVGP_PREPARE, fit = !prep, grad = kind == SVGP_GRAD;
+  const bool prep = kind == SVGP_PREPARE, fit = !prep, gz = kind == SVGP_GRAD_Z, grad = kind == SVGP_GRAD || gz;
   const size_t mat = up256((size_t)Mpad * Mpad * 8), vec = up256((size_t)Mpad * 8);
   size_t at = 0;
   auto take = [&](SvgpRegion id, bool have, size_t bytes) {
@@ -100,6 +107,7 @@ inline SvgpLayout svgp_layout(SvgpKind kind, int64_t Mpad, int64_t ntask, int64_
   take(SV_SC2, grad, 512);
   take(SV_GACC, grad, up256((size_t)nout * 8));
   take(SV_BND, grad, 256);
+  take(SV_ZACC, gz, up256((size_t)Mpad * zdim * 8));
   L.acc = span(SV_BVEC, SV_SCAL);
   L.acc2 = span(SV_SC2, SV_GACC);
   L.task = at;
@@ -115,6 +123,7 @@ inline SvgpLayout svgp_layout(SvgpKind kind, int64_t Mpad, int64_t ntask, int64_
   take(SV_R, fit, up256((size_t)L.ldk * 8));
   take(SV_EV, grad, up256((size_t)L.ldk * 8));
   take(SV_PART, grad, up256(nI * (ncb > nI ? ncb : nI) * nout * 8));
+  take(SV_ZPART, gz, up256(nI * (ncb > nI ? ncb : nI) * 128 * (size_t)zdim * 8));
   L.total = at;
   return L;
 }
@@ -122,9 +131,9 @@ inline SvgpLayout svgp_layout(SvgpKind kind, int64_t Mpad, int64_t ntask, int64_
 // The chunk width a workspace of ws_bytes allows the fit or the gradient: the largest multiple of 128, at most cap
 // (GPX_SVGP_FIT_CHUNK) and the padded n, whose layout's reported size fits; 0 if none does.
 inline int64_t svgp_chunk_width(SvgpKind kind, int64_t Mpad, int64_t ntask, int64_t n, int64_t cap, size_t ws_bytes,
-                                int64_t nout = 0) {
+                                int64_t nout = 0, int64_t zdim = 0) {
   int64_t C = cap < up128(n) ? cap : up128(n);
-  while (C >= 128 && svgp_layout(kind, Mpad, ntask, C, nout).total + 256 > ws_bytes) C -= 128;
+  while (C >= 128 && svgp_layout(kind, Mpad, ntask, C, nout, zdim).total + 256 > ws_bytes) C -= 128;
   return C >= 128 ? C : 0;
 }
 

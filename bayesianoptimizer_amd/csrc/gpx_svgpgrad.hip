@@ -71,10 +71,11 @@ struct DkSums {
 
 // sums += G dk(x1, x2)/dtheta for one pair of points (rows of DMAX doubles, zero beyond d): mll_grad_kernel's element.
 // KIND >= 0 is compile-time; KIND < 0 reads the kind at run time (the Scale(Linear + Matern) instantiation).
+// Returns G kfac, the factor of -(x1_k - x2_k) / l_k^2 in G d1 k(x1, x2)_k (the inducing-location gradient's element).
 template <int DMAX, int KIND>
-__device__ __forceinline__ void dk_add(const gpx_kernel_params& p, int kind, const double (&il)[DMAX], double G,
-                                       const double* __restrict__ x1, const double* __restrict__ x2,
-                                       DkSums<DMAX>& a) {
+__device__ __forceinline__ double dk_add(const gpx_kernel_params& p, int kind, const double (&il)[DMAX], double G,
+                                         const double* __restrict__ x1, const double* __restrict__ x2,
+                                         DkSums<DMAX>& a) {
   const int d = p.d;
   const bool lin = kind == GPX_KERNEL_SCALE_LINEAR_MATERN52;
   double q[DMAX];
@@ -114,6 +115,40 @@ __device__ __forceinline__ void dk_add(const gpx_kernel_params& p, int kind, con
   const double gk = G * kfac;
 #pragma unroll
   for (int k = 0; k < DMAX; ++k) a.gl[k] += gk * q[k];
+  return gk;
+}
+
+// The inducing-location gradient (gpx_svgp_bound_grad_z_f64).  With G = dF/dk(z_a, x) for one pair of points,
+//   G d1 k(z_a, x)_k = -il_k^2 [ (G kfac) (z_ak - x_k) + G cz_k x_k ],   cz_k = -outputscale v_k l_k^2 (linear kind; else 0)
+// so a row's running sum gz[k] takes two FMAs per pair and dimension (one without the linear part) and is multiplied by
+// -il_k^2 once, when the row leaves the workgroup.
+template <int DMAX>
+__device__ __forceinline__ void dz_consts(const gpx_kernel_params& p, bool lin, double (&cz)[DMAX]) {
+#pragma unroll
+  for (int k = 0; k < DMAX; ++k)
+    cz[k] = (lin && k < p.d) ? -(p.outputscale * p.linear_variance[k]) * (p.lengthscale[k] * p.lengthscale[k]) : 0.0;
+}
+
+// The two column halves of a row (threads row and 128 + row) joined in a fixed order through LDS (buf: 128 x (DMAX + 1)
+// doubles, free to overwrite), scaled, into dst[row][DMAX] (k >= d: 0).  Every thread of the workgroup calls it.
+template <int DMAX>
+__device__ __forceinline__ void dz_store(const gpx_kernel_params& p, const double (&gz)[DMAX], double scale,
+                                         double* buf, double* __restrict__ dst) {
+  constexpr int XP = DMAX + 1;
+  const int row = threadIdx.x & (MT - 1), hh = threadIdx.x >> 7;
+  if (hh == 1) {
+#pragma unroll
+    for (int k = 0; k < DMAX; ++k) buf[row * XP + k] = gz[k];
+  }
+  __syncthreads();
+  if (hh == 0) {
+#pragma unroll
+    for (int k = 0; k < DMAX; ++k) {
+      const double il = (k < p.d) ? 1.0 / p.lengthscale[k] : 0.0;
+      dst[row * DMAX + k] = -scale * (il * il) * (gz[k] + buf[row * XP + k]);
+    }
+  }
+  __syncthreads();
 }
 
 // the workgroup's sums, in a fixed order, into one partial row (red: 4 x NROW doubles of LDS, free to overwrite)
@@ -243,6 +278,69 @@ __global__ void __launch_bounds__(WG) svgp_kzz_kernel(gpx_kernel_params p, int M
   dk_store<DMAX>(p, kind, il, a, smem, part + (int64_t)blockIdx.x * NROW);
 }
 
+// The K_ZZ part of the inducing-location gradient: zacc[a][k] = 2 sum_{b < M} G_A[a][b] d1 k(z_a, z_b)_k for the rows of
+// tile I = blockIdx.x, the column tiles J in ascending order.  Thread (row, half) owns row a = 128 I + row and the
+// columns 64 half .. 64 half + 63 of every tile; G_A is read through its transpose (it is symmetric), which the lanes'
+// consecutive rows read coalesced.  b = a needs no special case: the stationary part is 0 there and the linear part's
+// 2 G_A[a][a] outputscale v_k z_ak is the whole derivative of k(z_a, z_a).
+template <int DMAX>
+__global__ void __launch_bounds__(WG) svgp_kzz_z_kernel(gpx_kernel_params p, int M, int P, const double* __restrict__ Z,
+                                                        int64_t ldz, const double* __restrict__ GA,
+                                                        double* __restrict__ zacc) {
+  constexpr int XP = DMAX + 1;
+  __shared__ double zj[MT * XP];
+  const int nI = P / MT, i0 = (int)blockIdx.x * MT;
+  const int d = p.d, kind = p.kind;
+  const bool lin = kind == GPX_KERNEL_SCALE_LINEAR_MATERN52;
+  const int row = threadIdx.x & (MT - 1), hh = threadIdx.x >> 7;
+  const bool rowin = i0 + row < M;
+  double il[DMAX], cz[DMAX], zr[DMAX], gz[DMAX];
+  dz_consts<DMAX>(p, lin, cz);
+#pragma unroll
+  for (int k = 0; k < DMAX; ++k) {
+    il[k] = (k < d) ? 1.0 / p.lengthscale[k] : 0.0;
+    zr[k] = (k < d && rowin) ? Z[(int64_t)(i0 + row) * ldz + k] : 0.0;
+    gz[k] = 0.0;
+  }
+#pragma unroll 1
+  for (int J = 0; J < nI; ++J) {
+    const int j0 = J * MT;
+    __syncthreads();
+    for (int e = threadIdx.x; e < MT * DMAX; e += WG) {
+      const int r = e / DMAX, k = e % DMAX;
+      zj[r * XP + k] = (k < d && j0 + r < M) ? Z[(int64_t)(j0 + r) * ldz + k] : 0.0;
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int c = hh * (MT / 2); c < (hh + 1) * (MT / 2); ++c) {
+      if (!rowin || j0 + c >= M) continue;
+      const double G = GA[(int64_t)(j0 + c) * P + i0 + row];
+      const double* zb = zj + c * XP;
+      double r2 = 0.0;
+#pragma unroll
+      for (int k = 0; k < DMAX; ++k) {
+        const double df = (zr[k] - zb[k]) * il[k];
+        r2 += df * df;
+      }
+      double kfac;
+      if (kind == GPX_KERNEL_RBF) {
+        kfac = p.outputscale * exp(-0.5 * r2);
+      } else {
+        const double rr = sqrt(r2);
+        kfac = p.outputscale * (5.0 / 3.0) * (1.0 + SQRT5 * rr) * exp(-SQRT5 * rr);
+      }
+      const double gk = G * kfac;
+#pragma unroll
+      for (int k = 0; k < DMAX; ++k) {
+        gz[k] += gk * (zr[k] - zb[k]);
+        if (lin) gz[k] += (G * cz[k]) * zb[k];
+      }
+    }
+  }
+  __syncthreads();
+  dz_store<DMAX>(p, gz, 2.0, zj, zacc + (int64_t)i0 * DMAX);
+}
+
 // e[c] = y_c - const_mean - sum_jb mu[jb][c] (the covariance build's partials of K_chunk^T c_v) for the chunk's mc
 // points, 0 up to the next multiple of 128: one column per thread.  Workgroup b leaves its sums in epart[b][ESUM]:
 // {sum e, e^T e, sum_c x_ck^2 at 2 + k (linear kind)}; svgp_esum_kernel adds them in workgroup order into sc2.
@@ -289,22 +387,34 @@ __global__ void __launch_bounds__(WG) svgp_esum_kernel(const double* __restrict_
 
 // Tile (I, cb) of H K_chunk (H symmetric, Mpad x Mpad; kc: Mpad x ldk, k over all of Mpad) and its contraction:
 // part[blockIdx.x] = sum_{a in tile, a < M} sum_{i in tile, i < mc} (acc + c_v[a] e[i]) / s2 * dk(z_a, x_i)/dtheta.
-template <int DMAX, int KIND>
+//
+// ZG (gpx_svgp_bound_grad_z_f64): the same tile is also contracted against d1 k(z_a, x_i), into zpart[blockIdx.x], the
+// workgroup's 128 x DMAX row partial of dF/dZ.  The hyperparameter contraction keeps its thread mapping and order (its
+// sums are the other instantiation's bit for bit); each thread leaves G kfac in the slab element it has just read (and G
+// beside it for the linear kind), and a second loop over the slab, thread (row, half) = (tid % 128, tid / 128) owning
+// one row and 8 of the slab's 16 columns, sums them into DMAX registers: no second exponential, one row per thread, and
+// conflict-free LDS reads (KVP and XP are odd).  The slab's sums are added to the row's running sums in LDS (za), half
+// 0 before half 1, so they are not live across the hyperparameter loop (with them the d > 16 linear kind would spill).
+template <int DMAX, int KIND, bool ZG = false>
 __global__ void __launch_bounds__(WG) svgp_grad_kernel(gpx_kernel_params p, int M, int Mpad,
                                                        const double* __restrict__ Z, int64_t ldz,
                                                        const double* __restrict__ H, const double* __restrict__ kc,
                                                        int64_t ldk, int ncb, const double* __restrict__ X, int64_t ldx,
                                                        int mc, const double* __restrict__ cv,
-                                                       const double* __restrict__ ev, double* __restrict__ part) {
-  // Epilogue LDS: the tile's rows of Z and of X_chunk, c_v and e, and one 128 x SW slab of the product
+                                                       const double* __restrict__ ev, double* __restrict__ part,
+                                                       double* __restrict__ zpart) {
+  // Epilogue LDS: the tile's rows of Z and of X_chunk, c_v and e, and one 128 x SW slab of the product (ZG, linear kind:
+  // a second slab for G)
   constexpr int SW = 16, KVP = SW + 1, XP = DMAX + 1;
-  constexpr int EPI = 2 * MT * XP + 2 * MT + MT * KVP;
+  constexpr bool ZLIN = ZG && KIND < 0;
+  constexpr bool CZS = ZLIN && DMAX > 16;  // the linear part's constants in LDS instead of registers
+  constexpr int EPI = 2 * MT * XP + 2 * MT + MT * KVP + (ZLIN ? MT * KVP : 0) + (ZG ? MT * XP : 0) + (CZS ? DMAX : 0);
   constexpr int SMEM = EPI > GTile::LDS_DOUBLES ? EPI : GTile::LDS_DOUBLES;  // 73.7 KB for d <= 16
   __shared__ __attribute__((aligned(16))) double smem[SMEM];
   const int I = (int)blockIdx.x / ncb, cb = (int)blockIdx.x % ncb;
   const int a0 = I * MT, c0 = cb * MT;
   // A(m, k) = H[k][a0 + m] (H = H^T), B(k, c) = K[k][c0 + c]: both k-major, the projection's operand form
-  trmm_asm::TileT<true, true, false, 16 * DMAX + KIND + 2> t;
+  trmm_asm::TileT<true, true, false, 16 * DMAX + KIND + 2 + (ZG ? 1024 : 0)> t;
   t.zero();
   t.run(H + a0, Mpad, kc + c0, ldk, Mpad / 16, smem);
 
@@ -331,6 +441,21 @@ __global__ void __launch_bounds__(WG) svgp_grad_kernel(gpx_kernel_params p, int 
   DkSums<DMAX> sums;
   sums.zero();
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  double* gb = kv + MT * KVP;                  // [MT][KVP] (ZLIN only)
+  double* za = gb + (ZLIN ? MT * KVP : 0);     // [MT][XP]  (ZG only)
+  [[maybe_unused]] double* czs = za + MT * XP; // [DMAX]    (CZS only)
+  const int zrow = threadIdx.x & (MT - 1), zh = threadIdx.x >> 7;
+  [[maybe_unused]] double cz[ZLIN && !CZS ? DMAX : 1];
+  if constexpr (ZG) {
+    for (int e = threadIdx.x; e < MT * XP; e += WG) za[e] = 0.0;
+  }
+  if constexpr (ZLIN && !CZS) dz_consts<DMAX>(p, true, cz);
+  if constexpr (CZS) {
+    if ((int)threadIdx.x < DMAX) {
+      const int k = threadIdx.x;
+      czs[k] = k < d ? -(p.outputscale * p.linear_variance[k]) * (p.lengthscale[k] * p.lengthscale[k]) : 0.0;
+    }
+  }
   // Eight 16-column slabs: the two waves owning the slab's columns park their accumulators in LDS, then all 256 threads
   // contract the slab element by element (a rolled loop keeps register pressure flat).
 #pragma unroll
@@ -345,11 +470,61 @@ __global__ void __launch_bounds__(WG) svgp_grad_kernel(gpx_kernel_params p, int 
 #pragma unroll 1
     for (int e = threadIdx.x; e < MT * SW; e += WG) {
       const int ri = e / SW, cj = sl * SW + e % SW;
-      if (a0 + ri >= M || c0 + cj >= mc) continue;
+      if (a0 + ri >= M || c0 + cj >= mc) {
+        if constexpr (ZG) kv[ri * KVP + e % SW] = 0.0;
+        if constexpr (ZLIN) gb[ri * KVP + e % SW] = 0.0;
+        continue;
+      }
       const double G = (kv[ri * KVP + e % SW] + ci[ri] * ej[cj]) * is2;
-      dk_add<DMAX, KIND>(p, kind, il, G, zi + ri * XP, xj + cj * XP, sums);
+      const double gk = dk_add<DMAX, KIND>(p, kind, il, G, zi + ri * XP, xj + cj * XP, sums);
+      if constexpr (ZG) kv[ri * KVP + e % SW] = gk;  // (this thread alone reads the element above)
+      if constexpr (ZLIN) gb[ri * KVP + e % SW] = G;
     }
     __syncthreads();
+    if constexpr (ZG) {
+      constexpr int KB = DMAX > 16 ? 16 : DMAX;  // dimensions per sweep of the slab (two sweeps for d > 16)
+#pragma unroll 1
+      for (int kb = 0; kb < DMAX; kb += KB) {
+        double zr[KB], gz[KB];
+#pragma unroll
+        for (int k = 0; k < KB; ++k) {
+          zr[k] = zi[zrow * XP + kb + k];
+          gz[k] = 0.0;
+        }
+#pragma unroll 1
+        for (int c = zh * (SW / 2); c < (zh + 1) * (SW / 2); ++c) {
+          const double gk = kv[zrow * KVP + c];
+          const double* xc = xj + (sl * SW + c) * XP + kb;
+          if constexpr (ZLIN) {
+            const double G = gb[zrow * KVP + c];
+#pragma unroll
+            for (int k = 0; k < KB; ++k) gz[k] += gk * (zr[k] - xc[k]) + (G * (CZS ? czs[kb + k] : cz[k])) * xc[k];
+          } else {
+#pragma unroll
+            for (int k = 0; k < KB; ++k) gz[k] += gk * (zr[k] - xc[k]);
+          }
+        }
+        if (zh == 0) {
+#pragma unroll
+          for (int k = 0; k < KB; ++k) za[zrow * XP + kb + k] += gz[k];
+        }
+        __syncthreads();
+        if (zh == 1) {
+#pragma unroll
+          for (int k = 0; k < KB; ++k) za[zrow * XP + kb + k] += gz[k];
+        }
+        __syncthreads();
+      }
+    }
+  }
+  if constexpr (ZG) {  // the row partial: -il_k^2 times the running sums (dz_consts' arrangement)
+    double* dst = zpart + (int64_t)blockIdx.x * MT * DMAX;
+    for (int e = threadIdx.x; e < MT * DMAX; e += WG) {
+      const int r = e / DMAX, k = e % DMAX;
+      const double ilk = (k < d) ? 1.0 / p.lengthscale[k] : 0.0;
+      dst[e] = -(ilk * ilk) * za[r * XP + k];
+    }
+    __syncthreads();  // (dk_store reuses the LDS image from its start)
   }
   dk_store<DMAX>(p, kind, il, sums, smem, part + (int64_t)blockIdx.x * NROW);
 }
@@ -367,6 +542,27 @@ __global__ void __launch_bounds__(WG) svgp_partsum_kernel(const double* __restri
   }
   __syncthreads();
   if ((int)threadIdx.x < NROW) acc[threadIdx.x] += (st[0][threadIdx.x] + st[1][threadIdx.x]) + st[2][threadIdx.x];
+}
+
+// zacc[128 I + r][k] += sum over the chunk's column blocks, ascending, of the row partials zpart[I ncb + cb][r][k]: one
+// thread per element of row tile I = blockIdx.x (dmax: the row length the tile kernel was instantiated with)
+__global__ void __launch_bounds__(WG) svgp_zsum_kernel(const double* __restrict__ zpart, int ncb, int dmax,
+                                                       double* __restrict__ zacc) {
+  const int64_t blk = (int64_t)MT * dmax;
+  for (int e = threadIdx.x; e < blk; e += WG) {
+    double v = 0.0;
+    for (int cb = 0; cb < ncb; ++cb) v += zpart[((int64_t)blockIdx.x * ncb + cb) * blk + e];
+    zacc[(int64_t)blockIdx.x * blk + e] += v;
+  }
+}
+
+// dZ[a][k] = -zacc[a][k] = d(-F)/dz_ak for a < M, k < d (rows of dmax doubles in, of lddz out)
+__global__ void __launch_bounds__(WG) svgp_zfinish_kernel(int M, int d, int dmax, const double* __restrict__ zacc,
+                                                          double* __restrict__ dZ, int64_t lddz) {
+  const int64_t e = (int64_t)blockIdx.x * WG + threadIdx.x;
+  const int64_t a = e / d;
+  const int k = (int)(e % d);
+  if (a < M) dZ[a * lddz + k] = -zacc[a * dmax + k];
 }
 
 // The output vector of one task: the bound's six values, then the GPX_MLL_* block of -F and its gradient.
@@ -428,12 +624,16 @@ hipError_t launch_svgp_grad_unreverse(Context* c, int ntask, int Mpad, int64_t t
 
 // gacc += sum G_A dK_ZZ/dtheta of one task (part: (Mpad / 128)^2 rows of GPX_MLL_NOUT doubles)
 hipError_t launch_svgp_grad_kzz(Context* c, const gpx_kernel_params& p, int M, int Mpad, const double* Z, int64_t ldz,
-                                const double* GA, double* part, double* gacc) {
+                                const double* GA, double* part, double* gacc, double* zacc) {
   const int nI = Mpad / MT;
   with_dmax(p.d, [&](auto D) {
     svgp_kzz_kernel<decltype(D)::value><<<nI * nI, WG, 0, c->stream>>>(p, M, Mpad, Z, ldz, GA, part);
   });
   svgp_partsum_kernel<<<1, WG, 0, c->stream>>>(part, nI * nI, gacc);
+  if (zacc)  // (writes every row of the task's accumulator: the chunks' sums are added to it)
+    with_dmax(p.d, [&](auto D) {
+      svgp_kzz_z_kernel<decltype(D)::value><<<nI, WG, 0, c->stream>>>(p, M, Mpad, Z, ldz, GA, zacc);
+    });
   return hipGetLastError();
 }
 
@@ -442,36 +642,47 @@ hipError_t launch_svgp_grad_kzz(Context* c, const gpx_kernel_params& p, int M, i
 hipError_t launch_svgp_grad_chunk(Context* c, const gpx_kernel_params& p, int M, int Mpad, const double* Z, int64_t ldz,
                                   const double* H, const double* kc, const double* mu, int64_t ldk, const double* X,
                                   int64_t ldx, const double* Y, int64_t ldy, int mc, const double* cv, double* ev,
-                                  double* sc2, double* part, double* gacc) {
+                                  double* sc2, double* part, double* gacc, double* zpart, double* zacc) {
   const int nI = Mpad / MT, ncb = (mc + MT - 1) / MT;
   // (part is free until the tile contraction below writes it: the residual's per-workgroup sums pass through it)
   const int neb = (ncb * MT + WG - 1) / WG;
   svgp_echunk_kernel<<<neb, WG, 0, c->stream>>>(p, Mpad / NB, mu, ldk, X, ldx, Y, ldy, mc, ncb * MT, ev, part);
   svgp_esum_kernel<<<1, WG, 0, c->stream>>>(part, neb, sc2);
   const int grid = nI * ncb;
-#define GPX_SG_K(D, K) \
-  svgp_grad_kernel<D, K><<<grid, WG, 0, c->stream>>>(p, M, Mpad, Z, ldz, H, kc, ldk, ncb, X, ldx, mc, cv, ev, part)
+#define GPX_SG_K(D, K)                                                                                                \
+  (zacc ? svgp_grad_kernel<D, K, true><<<grid, WG, 0, c->stream>>>(p, M, Mpad, Z, ldz, H, kc, ldk, ncb, X, ldx, mc,  \
+                                                                   cv, ev, part, zpart)                              \
+        : svgp_grad_kernel<D, K><<<grid, WG, 0, c->stream>>>(p, M, Mpad, Z, ldz, H, kc, ldk, ncb, X, ldx, mc, cv, ev, \
+                                                             part, nullptr))
 #define GPX_SG(D)                                                       \
   (p.kind == GPX_KERNEL_RBF        ? GPX_SG_K(D, GPX_KERNEL_RBF)        \
    : p.kind == GPX_KERNEL_MATERN52 ? GPX_SG_K(D, GPX_KERNEL_MATERN52)   \
                                    : GPX_SG_K(D, -1))
+  int dmax;
   if (p.d <= 4)
-    GPX_SG(4);
+    dmax = 4, GPX_SG(4);
   else if (p.d <= 8)
-    GPX_SG(8);
+    dmax = 8, GPX_SG(8);
   else if (p.d <= 16)
-    GPX_SG(16);
+    dmax = 16, GPX_SG(16);
   else
-    GPX_SG(32);
+    dmax = 32, GPX_SG(32);
 #undef GPX_SG
 #undef GPX_SG_K
   svgp_partsum_kernel<<<1, WG, 0, c->stream>>>(part, grid, gacc);
+  if (zacc) svgp_zsum_kernel<<<nI, WG, 0, c->stream>>>(zpart, ncb, dmax, zacc);
   return hipGetLastError();
 }
 
 hipError_t launch_svgp_grad_finish(Context* c, const gpx_kernel_params& p, int M, int64_t n, const double* bound,
-                                   const double* scal, const double* sc2, const double* gacc, double* out) {
+                                   const double* scal, const double* sc2, const double* gacc, double* out,
+                                   const double* zacc, double* dZ, int64_t lddz) {
   svgp_grad_finish_kernel<<<1, WG, 0, c->stream>>>(p, M, n, bound, scal, sc2, gacc, out);
+  if (zacc) {
+    const int dmax = p.d <= 4 ? 4 : p.d <= 8 ? 8 : p.d <= 16 ? 16 : 32;
+    svgp_zfinish_kernel<<<(unsigned)(((int64_t)M * p.d + WG - 1) / WG), WG, 0, c->stream>>>(M, p.d, dmax, zacc, dZ,
+                                                                                             lddz);
+  }
   return hipGetLastError();
 }
 

@@ -1094,14 +1094,21 @@ class GPEngine:
         return vmean, vchol, bound
 
     def svgp_bound_value_grad(self, params: Sequence[KernelParams], Z, X, Y, jitter: float = 1e-4,
-                              chunk: Optional[int] = None):
+                              chunk: Optional[int] = None, inducing_grad: bool = False):
         """The collapsed bound F of ``svgp_fit_collapsed`` and the gradient of -F with respect to the natural
         hyperparameters of every task (gpx_svgp_bound_grad_f64: the fit's pass over X and a second one).  Arguments as
         ``svgp_fit_collapsed``.  Returns a list of T host dicts with the keys ``mll._loss_grad`` reads: ``nll`` = -F,
         ``noise``, ``outputscale``, ``const_mean``, ``lengthscale``, ``linear_variance`` (gradients of -F), and
-        ``bound`` (F and its five terms).  Raises NotPositiveDefiniteError naming the task whose K_ZZ failed.
-        Synchronises; the workspace is the engine's, reused across evaluations."""
-        out, info = self.svgp_bound_grad(params, Z, X, Y, jitter=jitter, chunk=chunk)
+        ``bound`` (F and its five terms).  ``inducing_grad``: every dict also carries ``inducing``, the M x d gradient
+        of -F with respect to the task's inducing locations (gpx_svgp_bound_grad_z_f64).  Raises
+        NotPositiveDefiniteError naming the task whose K_ZZ failed.  Synchronises; the workspace is the engine's,
+        reused across evaluations."""
+        dZ = None
+        if inducing_grad:
+            out, dZ, info = self.svgp_bound_grad_z(params, Z, X, Y, jitter=jitter, chunk=chunk)
+            dZ = dZ.cpu().numpy()
+        else:
+            out, info = self.svgp_bound_grad(params, Z, X, Y, jitter=jitter, chunk=chunk)
         v = out.cpu().numpy()
         bad = info.cpu().numpy()
         for t in range(len(bad)):
@@ -1119,12 +1126,25 @@ class GPEngine:
                 "linear_variance": g[_capi.MLL_D_LINVAR:_capi.MLL_D_LINVAR + d].copy(),
                 "bound": r[_capi.SVGP_GRAD_BOUND:_capi.SVGP_GRAD_BOUND + _capi.SVGP_BOUND_NOUT].copy(),
             })
+            if dZ is not None:
+                res[-1]["inducing"] = dZ[len(res) - 1]
         return res
 
     def svgp_bound_grad(self, params: Sequence[KernelParams], Z, X, Y, jitter: float = 1e-4,
                         chunk: Optional[int] = None):
         """The device side of ``svgp_bound_value_grad``: (out T x SVGP_GRAD_NOUT, info T) on the device, unchecked
         (a task whose info is not 0 holds unspecified values) and without a synchronisation."""
+        out, _, info = self._svgp_bound_grad(params, Z, X, Y, jitter, chunk, False)
+        return out, info
+
+    def svgp_bound_grad_z(self, params: Sequence[KernelParams], Z, X, Y, jitter: float = 1e-4,
+                          chunk: Optional[int] = None):
+        """``svgp_bound_grad`` together with the gradient of -F with respect to the inducing locations
+        (gpx_svgp_bound_grad_z_f64): (out T x SVGP_GRAD_NOUT, dZ T x M x d, info T) on the device, unchecked and
+        without a synchronisation.  ``out`` holds the bits ``svgp_bound_grad`` returns for the same chunk width."""
+        return self._svgp_bound_grad(params, Z, X, Y, jitter, chunk, True)
+
+    def _svgp_bound_grad(self, params, Z, X, Y, jitter, chunk, want_z):
         Z = torch.as_tensor(Z).to(device=self.device, dtype=torch.float64)
         if Z.dim() != 3:
             raise ValueError("Z must be T x M x d")
@@ -1143,14 +1163,21 @@ class GPEngine:
         out = torch.empty((T, _capi.SVGP_GRAD_NOUT), dtype=torch.float64, device=self.device)
         info = torch.zeros((T,), dtype=torch.int32, device=self.device)
         nbytes = ctypes.c_size_t()
-        self._check(self.lib.gpx_svgp_bound_grad_workspace_size(M, n, T, int(chunk or 0), ctypes.byref(nbytes)))
-        ws = self.workspace("svgp_grad", nbytes.value)
+        size = self.lib.gpx_svgp_bound_grad_z_workspace_size if want_z else self.lib.gpx_svgp_bound_grad_workspace_size
+        self._check(size(M, n, T, int(chunk or 0), ctypes.byref(nbytes)))
+        ws = self.workspace("svgp_grad_z" if want_z else "svgp_grad", nbytes.value)
         self._bind_stream()
         # (the library derives the chunk width from the size it is told, not from the cached buffer's)
-        self._check(self.lib.gpx_svgp_bound_grad_f64(
+        if not want_z:
+            self._check(self.lib.gpx_svgp_bound_grad_f64(
+                self.handle, pcs, T, M, float(jitter), _ptr(Z), Z.stride(1), Z.stride(0), _ptr(X), n, X.stride(0),
+                _ptr(Y), Y.stride(0), _ptr(out), _ptr(info), _ptr(ws), nbytes.value))
+            return out, None, info
+        dZ = torch.empty((T, M, d), dtype=torch.float64, device=self.device)
+        self._check(self.lib.gpx_svgp_bound_grad_z_f64(
             self.handle, pcs, T, M, float(jitter), _ptr(Z), Z.stride(1), Z.stride(0), _ptr(X), n, X.stride(0), _ptr(Y),
-            Y.stride(0), _ptr(out), _ptr(info), _ptr(ws), nbytes.value))
-        return out, info
+            Y.stride(0), _ptr(out), _ptr(dZ), d, M * d, _ptr(info), _ptr(ws), nbytes.value))
+        return out, dZ, info
 
     def topk(self, scores: torch.Tensor, k: int):
         """(values, indices) of the k largest scores, descending, ties -> lower index first (gpx_topk_f64)."""

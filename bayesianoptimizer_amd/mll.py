@@ -322,6 +322,7 @@ class MLLFitOutputsResult:
     success: bool
     message: str
     raw: np.ndarray = field(default_factory=lambda: np.zeros(0))
+    Z: Optional[np.ndarray] = None  # fit_hyperparameters_sparse(learn_inducing=True): the fitted T x M x d locations
 
 
 def fit_hyperparameters_outputs(engine, X, Y, kind: str = "rbf", prior_set: str = "dim_scaled",
@@ -366,13 +367,27 @@ def fit_hyperparameters_outputs(engine, X, Y, kind: str = "rbf", prior_set: str 
 def fit_hyperparameters_sparse(engine, X, Y, Z, kind: str = "scale_linear_matern52", prior_set: str = "none",
                                bases: Optional[Sequence[KernelParams]] = None, fit_mean: bool = True,
                                options: Optional[dict] = None, value_grad_all: Optional[Callable] = None,
-                               x0: Optional[Sequence[float]] = None, jitter: float = 1e-4) -> MLLFitOutputsResult:
+                               x0: Optional[Sequence[float]] = None, jitter: float = 1e-4,
+                               learn_inducing: bool = False) -> MLLFitOutputsResult:
     """``fit_hyperparameters_outputs`` with the collapsed SVGP bound F in the place of the marginal likelihood: the
     hyperparameters of T sparse models on inducing points Z (M x d shared, or T x M x d) that maximise F over all n
     points.  F is the ELBO of optimization/Bayesian7.py:451-538 with q(u) already at its optimum, so its maximiser is
     the fixed point of that joint training.  ONE L-BFGS-B over the concatenated raw vectors on the summed loss
     (-F_t - log priors) / n; every evaluation is one batched GPU evaluation (GPEngine.svgp_bound_value_grad), a failed
-    K_ZZ scores +inf.  ``result.nll[t]`` = -F_t.  Tests inject a CPU reference through ``value_grad_all``."""
+    K_ZZ scores +inf.  ``result.nll[t]`` = -F_t.  Tests inject a CPU reference through ``value_grad_all``.
+
+    ``learn_inducing``: Z moves too, as the reference's ``learn_inducing_locations=True`` lets it
+    (optimization/Bayesian7.py:152).  The L-BFGS-B vector is the raw hyperparameters followed by the T M d entries of Z
+    (unbounded; every task its own copy, also of a shared Z, as the reference's expanded parameter becomes), the Z part
+    of the gradient the evaluation's ``"inducing"`` arrays / n (GPEngine.svgp_bound_value_grad(inducing_grad=True)).
+    Points that collide make K_ZZ fail: +inf, like any failed K_ZZ.  The search has two legs with the same ``options``:
+    the hyperparameters alone on the given Z (the ``learn_inducing=False`` search), then the joint vector from that
+    point.  L-BFGS-B does not leave a point for a worse one, so the loss never ends above the fixed-Z fit's.  (A joint
+    search from the raw start spends its first steps on the T M d location entries, which dominate the gradient's norm,
+    and within a small iteration budget ended behind the fixed-Z fit: 520 points, M = 130, 15 iterations, F = 438.64
+    against 439.36.)  ``n_evals`` counts both legs.  An injected ``value_grad_all`` is then called as
+    ``value_grad_all(params, Z)`` with the current T x M x d array.  ``result.Z`` is the fitted array (None when Z is
+    not learned), ``result.raw`` the hyperparameters' part of the vector."""
     from scipy.optimize import minimize
 
     Xn = np.asarray(X.cpu() if hasattr(X, "cpu") else X, dtype=np.float64)
@@ -384,6 +399,15 @@ def fit_hyperparameters_sparse(engine, X, Y, Z, kind: str = "scale_linear_matern
     if len(bases) != T:
         raise ValueError(f"expected {T} base parameter sets, got {len(bases)}")
     specs = [default_spec(kind, d, prior_set, bases[t], fit_mean) for t in range(T)]
+    if learn_inducing:
+        Zn = np.array(Z.detach().cpu().numpy() if hasattr(Z, "cpu") else Z, dtype=np.float64)
+        Zn = np.repeat(Zn[None], T, axis=0) if Zn.ndim == 2 else Zn
+        if Zn.ndim != 3 or Zn.shape[0] != T:
+            raise ValueError(f"Z must be M x d or {T} x M x d")
+        at_start = None if value_grad_all is None else (lambda ps: value_grad_all(ps, Zn))
+        first = fit_hyperparameters_sparse(engine, X, Yn, Zn, kind, prior_set, bases=bases, fit_mean=fit_mean,
+                                           options=options, value_grad_all=at_start, x0=x0, jitter=jitter)
+        return _fit_sparse_with_inducing(engine, X, Yn, Zn, specs, n, options, value_grad_all, first, jitter)
     if value_grad_all is None:
         import torch
 
@@ -407,3 +431,51 @@ def fit_hyperparameters_sparse(engine, X, Y, Z, kind: str = "scale_linear_matern
         nll = [float(g["nll"]) for g in value_grad_all(ps)]
     return MLLFitOutputsResult(params=ps, loss=float(loss), nll=nll, n_evals=int(res.nfev), success=bool(res.success),
                                message=str(res.message), raw=res.x.copy())
+
+
+def _fit_sparse_with_inducing(engine, X, Yn, Zn, specs, n, options, value_grad_all, first,
+                              jitter) -> MLLFitOutputsResult:
+    """fit_hyperparameters_sparse(learn_inducing=True), second leg: the vector is [raw hyperparameters, Z.ravel()],
+    started at the fixed-Z fit ``first`` on Zn (T x M x d)."""
+    from scipy.optimize import minimize
+
+    T = len(specs)
+    if value_grad_all is None:
+        import torch
+
+        Xd = torch.as_tensor(X).to(device=engine.device, dtype=torch.float64)
+        Yd = torch.as_tensor(Yn).to(device=engine.device, dtype=torch.float64)
+
+        def value_grad_all(ps, Zc):
+            return engine.svgp_bound_value_grad(ps, torch.as_tensor(Zc).to(engine.device), Xd, Yd, jitter=jitter,
+                                                inducing_grad=True)
+
+    sizes = np.concatenate([[0], np.cumsum([len(sp.hypers) for sp in specs])])
+    nh = int(sizes[-1])
+
+    def f(x):
+        x = np.asarray(x, dtype=np.float64)
+        Zc = x[nh:].reshape(Zn.shape)
+        seen = {}
+
+        def at_z(ps):
+            seen["g"] = value_grad_all(ps, Zc)
+            return seen["g"]
+
+        loss, gh = objective_outputs(specs, at_z, n)(x[:nh])
+        if not np.isfinite(loss):
+            return np.inf, np.zeros_like(x)
+        gz = np.concatenate([np.asarray(g["inducing"], dtype=np.float64).ravel() for g in seen["g"]]) / n
+        return loss, np.concatenate([gh, gz])
+
+    bounds = [b for sp in specs for b in sp.bounds()] + [(None, None)] * Zn.size
+    res = minimize(f, np.concatenate([first.raw, Zn.ravel()]), jac=True, method="L-BFGS-B", bounds=bounds,
+                   options=options or {})
+    ps = [sp.params_from_raw(res.x[sizes[t]:sizes[t + 1]]) for t, sp in enumerate(specs)]
+    Zfit = res.x[nh:].reshape(Zn.shape).copy()
+    loss, _ = f(res.x)
+    nll = [float("inf")] * T
+    if np.isfinite(loss):
+        nll = [float(g["nll"]) for g in value_grad_all(ps, Zfit)]
+    return MLLFitOutputsResult(params=ps, loss=float(loss), nll=nll, n_evals=first.n_evals + int(res.nfev),
+                               success=bool(res.success), message=str(res.message), raw=res.x[:nh].copy(), Z=Zfit)

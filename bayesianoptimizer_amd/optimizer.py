@@ -110,6 +110,10 @@ class GPConfig:
     # ELBO training converges to, Bayesian7.py:451-538), started from the previous round's values or, in the first
     # sparse round, from the subsample fit
     sparse_hyperparameters: str = "subsample"
+    # the sparse model's inducing points: "fixed" where select_inducing_points puts them each round, or "learned":
+    # moved together with the hyperparameters to maximise the bound, every output its own copy (the reference's
+    # learn_inducing_locations=True, Bayesian7.py:152).  "learned" needs sparse_hyperparameters = "bound".
+    sparse_inducing: str = "fixed"
     max_inducing_points: int = 2048
     inducing_subset_size: int = 10000
     # acquisition="qlogei": optimize_acqf settings of optimization/Bayesian.py:100-112
@@ -234,6 +238,11 @@ class BayesianOptimizer:
             raise ValueError(f"unknown GPConfig.large_n_model '{self.config.large_n_model}'")
         if self.config.sparse_hyperparameters not in ("subsample", "bound"):
             raise ValueError(f"unknown GPConfig.sparse_hyperparameters '{self.config.sparse_hyperparameters}'")
+        if self.config.sparse_inducing not in ("fixed", "learned"):
+            raise ValueError(f"unknown GPConfig.sparse_inducing '{self.config.sparse_inducing}'")
+        if self.config.sparse_inducing == "learned" and self.config.sparse_hyperparameters != "bound":
+            raise ValueError("GPConfig.sparse_inducing='learned' requires sparse_hyperparameters='bound': the inducing "
+                             "points are learned by maximising the collapsed bound")
         if self._sparse_policy() and self.acquisition != "variance":
             raise ValueError(f"acquisition '{self.acquisition}' is not available with GPConfig.large_n_model='sparse': "
                              "the sparse surrogate serves acquisition='variance' (the pool scan) only")
@@ -420,7 +429,8 @@ class BayesianOptimizer:
 
     def _bound_hyperparameters(self, n: int, Xs: torch.Tensor, Ys: torch.Tensor, params, Z):
         """GPConfig.sparse_hyperparameters = "bound": the collapsed bound of the sparse model on Z, maximised over all n
-        points from ``params`` (one set per output)."""
+        points from ``params`` (one set per output).  Returns (parameters, Z): with GPConfig.sparse_inducing = "learned"
+        the inducing points are optimised too and Z is the fitted T x M x d array, else the Z given."""
         from .mll import default_spec, fit_hyperparameters_sparse
 
         cfg = self.config
@@ -428,10 +438,13 @@ class BayesianOptimizer:
         plist = [params] * T if isinstance(params, KernelParams) else list(params)
         x0 = np.concatenate([default_spec(cfg.kernel, d, cfg.prior_set, p).raw_from_params(p) for p in plist])
         res = fit_hyperparameters_sparse(self.engine, Xs, Ys, Z, cfg.kernel, cfg.prior_set, bases=plist,
-                                         options=cfg.mll_options, x0=x0, jitter=cfg.jitter_val)
+                                         options=cfg.mll_options, x0=x0, jitter=cfg.jitter_val,
+                                         learn_inducing=cfg.sparse_inducing == "learned")
         print(f"[gpx] n={n}: sparse hyperparameters from the collapsed bound on all points ({res.n_evals} evaluations)")
         self.sparse_hyper_result = res
-        return res.params if np.isfinite(res.loss) else plist
+        if not np.isfinite(res.loss):
+            return plist, Z
+        return res.params, (Z if res.Z is None else torch.as_tensor(res.Z, dtype=torch.float64, device=Xs.device))
 
     def _fit_sparse(self, n: int, Ys: torch.Tensor):
         """n > svgp_threshold with GPConfig.large_n_model = "sparse": hyperparameters as in _fit_large_n, inducing points
@@ -458,7 +471,7 @@ class BayesianOptimizer:
             Z = inducing()
             if not have_prev:
                 params = self._subsample_hyperparameters(n, Xs, Ys, params, reference_jitter_schedule(cfg.jitter_val))
-            params = self._bound_hyperparameters(n, Xs, Ys, params, Z)
+            params, Z = self._bound_hyperparameters(n, Xs, Ys, params, Z)
         else:
             if cfg.fit_hyperparameters:
                 params = self._subsample_hyperparameters(n, Xs, Ys, params, reference_jitter_schedule(cfg.jitter_val))

@@ -9,7 +9,9 @@ comes from one of two places: a checkpoint the reference trained (``batch_svgp.p
 variational distribution the reference's Adam loop on the ELBO (``:451-538``) descends towards is known in closed form
 (Gaussian likelihood: Titsias' collapsed posterior), and ``gpx_svgp_fit_collapsed_f64`` computes it.
 ``SVGPModel.fit`` also chooses the hyperparameters, by maximising that bound over all n points
-(``gpx_svgp_bound_grad_f64``).  Learning Z, minibatch training and non-Gaussian likelihoods stay out of scope.
+(``gpx_svgp_bound_grad_f64``) and, with ``learn_inducing_locations=True``, moves Z along with them
+(``gpx_svgp_bound_grad_z_f64``), as the reference's ``learn_inducing_locations=True`` does.  Minibatch training and
+non-Gaussian likelihoods stay out of scope.
 
 All arithmetic is fp64 (the reference model is float32; its variational jitter, 1e-4, is kept as the default).
 """
@@ -74,12 +76,15 @@ class SVGPModel:
     @classmethod
     def fit(cls, X, Y, Z, params0: Union[KernelParams, Sequence[KernelParams]], prior_set: str = "none",
             fit_mean: bool = True, options: Optional[dict] = None, jitter: float = VARIATIONAL_JITTER_F32,
-            engine: Optional[GPEngine] = None, value_grad_all=None) -> "SVGPModel":
+            engine: Optional[GPEngine] = None, value_grad_all=None,
+            learn_inducing_locations: bool = False) -> "SVGPModel":
         """Hyperparameters and variational distribution together: the hyperparameters that maximise the collapsed
         bound over all n points, starting from ``params0`` (``mll.fit_hyperparameters_sparse``: L-BFGS-B on
         ``GPEngine.svgp_bound_value_grad``), then ``fit_collapsed`` at the result: the fixed point of the reference's
-        joint ELBO training (``optimization/Bayesian7.py:451-538``) for the given inducing points.  The optimiser's
-        result is kept as ``model.hyper_result``."""
+        joint ELBO training (``optimization/Bayesian7.py:451-538``) for the given inducing points.  With
+        ``learn_inducing_locations`` the inducing points are optimised too, every task its own copy starting from
+        ``Z``, and the model stands on the fitted ones (``model.hyper_result.Z``).  The optimiser's result is kept as
+        ``model.hyper_result``."""
         from .mll import default_spec, fit_hyperparameters_sparse
         import numpy as np
 
@@ -93,8 +98,9 @@ class SVGPModel:
             {0: "rbf", 1: "matern52", 2: "scale_linear_matern52"}[int(plist[0].kind)]
         x0 = np.concatenate([default_spec(kind, d, prior_set, p, fit_mean).raw_from_params(p) for p in plist])
         res = fit_hyperparameters_sparse(eng, X, Y, Z, kind, prior_set, bases=plist, fit_mean=fit_mean, options=options,
-                                         value_grad_all=value_grad_all, x0=x0, jitter=jitter)
-        model = cls.fit_collapsed(X, Y, res.params, Z, jitter=jitter, engine=eng)
+                                         value_grad_all=value_grad_all, x0=x0, jitter=jitter,
+                                         learn_inducing=learn_inducing_locations)
+        model = cls.fit_collapsed(X, Y, res.params, Z if res.Z is None else res.Z, jitter=jitter, engine=eng)
         model.hyper_result = res
         return model
 

@@ -659,6 +659,24 @@ gpx_status gpx_svgp_bound_grad_f64(gpx_handle h, const gpx_kernel_params* p, int
                                    int64_t ldx, const double* Y, int64_t ldy, double* out, int32_t* info, void* ws,
                                    size_t ws_bytes);
 
+/* The same evaluation together with the gradient with respect to the inducing locations.  Per task, with G_u =
+ * dF/dK(Z, X) and G_A = dF/dK_ZZ as above and d1 the derivative in the first argument,
+ *   dF/dz_ak = sum_i G_u[a][i] d1 k(z_a, x_i)_k + 2 sum_b G_A[a][b] d1 k(z_a, z_b)_k :
+ * every tile of G_u, formed once, is contracted against dK/dtheta and against d1 k before it is dropped.
+ * dZ (ntask x M x d; rows lddz >= d apart, tasks stride_dz >= M lddz apart when ntask > 1): dZ[t][a][k] =
+ * d(-F_t)/dz_ak, the sign of the GPX_MLL block; columns k >= d of a wider row are not written.  out and info as
+ * gpx_svgp_bound_grad_f64: for equal inputs and an equal chunk width out holds the bits that call writes.  A task whose
+ * info is not 0 has unspecified dZ; the other tasks are computed.  The chunk rule and the determinism are those of
+ * gpx_svgp_bound_grad_f64.  Workspace: gpx_svgp_bound_grad_z_workspace_size(M, n, ntask, chunk): the gradient's and
+ * ntask Mpad GPX_MAX_DIM 8 + (Mpad / 128) max(Mpad / 128, C / 128) 128 GPX_MAX_DIM 8 bytes (the accumulators of dF/dZ
+ * and the row partials of one launch).  A workspace of the size either call's size function reports for `chunk` gives
+ * both calls the same chunk width. */
+gpx_status gpx_svgp_bound_grad_z_workspace_size(int64_t M, int64_t n, int64_t ntask, int64_t chunk, size_t* bytes);
+gpx_status gpx_svgp_bound_grad_z_f64(gpx_handle h, const gpx_kernel_params* p, int64_t ntask, int64_t M, double jitter,
+                                     const double* Z, int64_t ldz, int64_t stride_z, const double* X, int64_t n,
+                                     int64_t ldx, const double* Y, int64_t ldy, double* out, double* dZ, int64_t lddz,
+                                     int64_t stride_dz, int32_t* info, void* ws, size_t ws_bytes);
+
 /* The k largest scores in descending order (replaces torch.topk, Bayesian7.py:681): stable, so equal scores keep
  * the lower index first; NaN ranks last.  idx_out: int64[k], val_out: double[k] (NULL = skip). */
 gpx_status gpx_topk_workspace_size(int64_t m, size_t* bytes);

@@ -1,0 +1,131 @@
+"""Host checks of the inducing-location gradient of the collapsed SVGP bound (gpx_svgp_bound_grad_z_f64): the two CPU
+references of tests/sgpr_zgrad_ref.py against each other (which fixes the suite's tolerance TAUZ) and against a finite
+difference of F, the L-BFGS-B driver mll.fit_hyperparameters_sparse(learn_inducing=True) with reference (a) injected,
+GPConfig.sparse_inducing's validation, and the C ABI's new symbols."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from bayesianoptimizer_amd import _capi
+from bayesianoptimizer_amd.mll import fit_hyperparameters_sparse
+from tests import sgpr_grad_ref as G
+from tests import sgpr_zgrad_ref as ZR
+
+
+def test_formula_equals_autograd_and_fixes_the_tolerance():
+    """(b) against (a), entrywise against the sum of the absolute summands: TAUZ0 is the largest ratio."""
+    tau0, where = 0.0, None
+    for shape in ZR.SHAPES:
+        for kind in G.KINDS:
+            pb, kps, refs = ZR.reference(shape, kind)
+            for t, (a, scale) in enumerate(refs):
+                b, scale_b = ZR.formula_dz(pb.Z[t], pb.X, pb.Y[:, t], kps[t])
+                assert a.shape == b.shape == pb.Z[t].shape and np.all(scale > 0.0)
+                r = ZR.ratio(b, a, scale)
+                if r > tau0:
+                    tau0, where = r, (shape, kind, t)
+    print(f"tauz0 = {tau0:.3e} at (shape, kind, task) = {where}; recorded TAUZ0 = {ZR.TAUZ0:.2e}, TAUZ = {ZR.TAUZ:.2e}")
+    assert tau0 <= ZR.TAUZ0, "the recorded TAUZ0 no longer covers the references' disagreement"
+
+
+@pytest.mark.parametrize("kind", G.KINDS)
+def test_finite_difference_of_the_bound_along_random_directions(kind):
+    """Central differences of the NumPy F along three random unit directions D of Z against <dZ, D>.  The step comes
+    from F's curvature along D: with F'' estimated from a probe, x_c = sqrt(|F| / |F''|) is F's length scale along D and
+    h = eps^(1/3) x_c balances the difference's truncation against its rounding.  The tolerance is the sum of the two,
+    each with a factor 4: the truncation by Richardson's estimate |d(2h) - d(h)| / 3, and the rounding as noise / h,
+    where the noise of one evaluation of F (a sum of cancelling terms behind two factorisations: far above eps |F|) is
+    measured as the second difference of F over a step 1e-6 h, at which the true second difference is below eps |F|."""
+    pb = G.problem(1)
+    p = G.with_kind(pb.kps[0], kind)
+    Z, X, y = pb.Z[0], pb.X, pb.Y[:, 0]
+    dZ = -ZR.formula_dz(Z, X, y, p)[0]  # dF/dZ
+    F = lambda h, D: ZR.bound_value(Z + h * D, X, y, p)  # noqa: E731
+    eps = np.finfo(np.float64).eps
+    rng = np.random.default_rng(7)
+    for _ in range(3):
+        D = rng.standard_normal(Z.shape)
+        D /= np.linalg.norm(D)
+        F0, probe = F(0.0, D), 1e-3
+        curv = abs(F(probe, D) - 2.0 * F0 + F(-probe, D)) / probe ** 2
+        h = eps ** (1.0 / 3.0) * np.sqrt(abs(F0) / curv)
+        d1 = (F(h, D) - F(-h, D)) / (2.0 * h)
+        d2 = (F(2.0 * h, D) - F(-2.0 * h, D)) / (4.0 * h)
+        tiny = 1e-6 * h
+        noise = max(abs(F(tiny, D) - 2.0 * F0 + F(-tiny, D)), eps * abs(F0))
+        tol = 4.0 * abs(d2 - d1) / 3.0 + 4.0 * noise / h
+        want = float((dZ * D).sum())
+        print(f"{kind}: h = {h:.2e}, FD {d1:.9e}, <dZ, D> {want:.9e}, |d| = {abs(d1 - want):.2e}, "
+              f"noise = {noise:.1e}, tol = {tol:.2e}")
+        assert abs(d1 - want) <= tol
+
+
+def test_fit_with_learned_inducing_points_is_no_worse_than_fixed():
+    """Shape 1 (T = 1, M = 130, n = 520) with reference (a) injected: from the same start the fit that also moves Z
+    ends at a loss not above the fixed-Z fit's; the fixed path is what it was."""
+    pb = G.problem(1)
+    kind, opts = "rbf", {"maxiter": 6}
+    fixed_vg = G.value_grad_all(pb.Z, pb.X, pb.Y)
+    fixed = fit_hyperparameters_sparse(None, pb.X, pb.Y, pb.Z, kind, "none", value_grad_all=fixed_vg, options=opts)
+    again = fit_hyperparameters_sparse(None, pb.X, pb.Y, pb.Z, kind, "none", value_grad_all=fixed_vg, options=opts,
+                                       learn_inducing=False)
+    assert fixed.Z is None and again.Z is None
+    assert fixed.loss == again.loss and np.array_equal(fixed.raw, again.raw) and fixed.n_evals == again.n_evals
+    learned = fit_hyperparameters_sparse(None, pb.X, pb.Y, pb.Z[0], kind, "none", options=opts,  # (Z given shared)
+                                         value_grad_all=ZR.value_grad_all(pb.X, pb.Y), learn_inducing=True)
+    print(f"loss: fixed Z {fixed.loss:.9f}, learned Z {learned.loss:.9f}; |dZ|max = "
+          f"{np.abs(learned.Z - pb.Z).max():.3e}")
+    assert learned.Z.shape == pb.Z.shape == (1, 130, 3)
+    assert np.isfinite(learned.loss) and learned.loss <= fixed.loss
+    assert np.abs(learned.Z - pb.Z).max() > 0.0
+    assert learned.raw.shape == fixed.raw.shape and np.isclose(learned.loss, sum(learned.nll) / 520, rtol=1e-12)
+
+
+def test_failed_kzz_scores_inf_when_learning_inducing_points():
+    pb = G.problem(1)
+
+    def failing(ps, Z):
+        raise np.linalg.LinAlgError("K_ZZ is not positive definite")
+
+    res = fit_hyperparameters_sparse(None, pb.X, pb.Y, pb.Z, "rbf", "none", value_grad_all=failing,
+                                     learn_inducing=True)
+    assert res.loss == np.inf and res.Z.shape == pb.Z.shape and all(v == np.inf for v in res.nll)
+
+
+def test_gpconfig_validates_sparse_inducing(tmp_path):
+    from bayesianoptimizer_amd.optimizer import BayesianOptimizer, GPConfig
+    from tests.oracle_engine import OracleEngine
+    from tests.stubs import BOUNDS, StubSimulator
+
+    def make(**kw):
+        return BayesianOptimizer(StubSimulator(), BOUNDS, str(tmp_path), n_initial_points=8, n_batches=1, batch_size=4,
+                                 engine=OracleEngine(), gp_config=GPConfig(**kw))
+
+    assert GPConfig().sparse_inducing == "fixed"
+    with pytest.raises(ValueError, match="sparse_inducing"):
+        make(sparse_inducing="nonsense")
+    with pytest.raises(ValueError, match="sparse_hyperparameters='bound'"):
+        make(sparse_inducing="learned")
+    with pytest.raises(ValueError, match="sparse_hyperparameters='bound'"):
+        make(sparse_inducing="learned", sparse_hyperparameters="subsample")
+    make(sparse_inducing="learned", sparse_hyperparameters="bound")
+
+
+NEW_SYMBOLS = ("gpx_svgp_bound_grad_z_workspace_size", "gpx_svgp_bound_grad_z_f64")
+
+
+def test_header_declares_and_library_exports_the_new_symbols():
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    header = open(os.path.join(root, "include", "gpx.h")).read()
+    for name in NEW_SYMBOLS:
+        assert re.search(r"gpx_status\s+" + name + r"\s*\(", header), name
+        assert name in _capi._PROTOS
+    if not os.path.exists(_capi.LIB_PATH):
+        pytest.skip("libgpx.so not built")
+    out = subprocess.run(["nm", "-D", "--defined-only", _capi.LIB_PATH], capture_output=True, text=True, check=True)
+    exported = {line.split()[-1] for line in out.stdout.splitlines() if line.strip()}
+    for name in NEW_SYMBOLS:
+        assert name in exported, name

@@ -1,7 +1,9 @@
 """Time of one evaluation of the collapsed SVGP bound and its hyperparameter gradient (default T = 8 tasks, M = 2048
-inducing points, d = 5, scale_linear_matern52; n = 10,000 and 100,000), three arms on the same GPU and data:
+inducing points, d = 5, scale_linear_matern52; n = 10,000 and 100,000), up to four arms on the same GPU and data:
 
   grad      GPEngine.svgp_bound_grad (gpx_svgp_bound_grad_f64): the fit's pass over X and the gradient's second pass
+  gradz     GPEngine.svgp_bound_grad_z (gpx_svgp_bound_grad_z_f64): the same with the inducing locations' gradient
+            (not in the default arms: --arms grad,gradz,fit gives gradz_over_grad and gradz_over_fit)
   fit       GPEngine.svgp_fit_collapsed (gpx_svgp_fit_collapsed_f64) alone
   autograd  the same value and gradient by torch autograd on the device, task after task (K(Z, X) and the graph of
             one task are all it holds at a time); its gradient is compared with the grad arm's
@@ -121,6 +123,8 @@ def timed(fn):
 work = {}
 if "grad" in arms:
     work["grad"] = lambda: eng.svgp_bound_grad(params, Z, X, Y, jitter=JITTER)
+if "gradz" in arms:
+    work["gradz"] = lambda: eng.svgp_bound_grad_z(params, Z, X, Y, jitter=JITTER)
 if "fit" in arms:
     work["fit"] = lambda: eng.svgp_fit_collapsed(params, Z, X, Y, jitter=JITTER)
 if "autograd" in arms:
@@ -136,6 +140,10 @@ rec = {"n": n, "M": M, "d": d, "T": T, "kernel": a.kernel, "steps": a.steps}
 for name, ts in times.items():
     rec[name + "_ms"] = round(statistics.median(ts), 3)
     rec[name + "_min_ms"] = round(min(ts), 3)
+if "gradz" in work:
+    for other in ("grad", "fit"):
+        if other in work:
+            rec["gradz_over_" + other] = round(rec["gradz_min_ms"] / rec[other + "_min_ms"], 3)
 if "grad" in work:
     Mpad = -(-M // _capi.GPX_TILE) * _capi.GPX_TILE
     # projection (triangular: half), rank update (lower tiles: half) and the second pass's full product, per task
