@@ -70,11 +70,13 @@ def mu_bound(engine, kp, X, alpha, Xs):
 
 
 class Geometry:
-    """The centre, max |a|^2, Y_c and eps1_32(c) of the factorised forms, restated in numpy."""
+    """The centre, max |a|^2, Y_c and eps1_32(c) of the factorised forms, restated in numpy.  ls: one lengthscale, or
+    one per dimension (the kernels scale coordinate k by 1 / ls[k]; a scalar divides as it always did)."""
 
     def __init__(self, X, ls):
         self.n, self.d = X.shape
-        self.ls = ls
+        self.ls = ls if np.ndim(ls) == 0 else np.asarray(ls, dtype=np.float64)
+        assert np.ndim(ls) == 0 or self.ls.shape == (self.d,)
         s = X / ls
         self.c = s.mean(axis=0)
         self.m2 = float(((s - self.c) ** 2).sum(axis=1).max())
@@ -137,7 +139,17 @@ def mixed_candidates(X, ls, rng):
     assert float(y[elig].max()) <= 0.996 * Y_LIMIT
     if 4 < d <= 8:  # the fp32 form is built for DMAX = 8 only
         fp64 = [w for w in groups if w not in slow and not bool((e[w * WG:(w + 1) * WG] <= EPS32_LIMIT).all())]
-        assert fp64 == [3, 4], fp64
+        if np.ndim(ls) == 0:
+            assert fp64 == [3, 4], fp64
+        else:
+            # per-dimension lengthscales below the default stretch the unit cube: some of its workgroups leave the
+            # fp32 form as well.  The rings stay where they were put, and every workgroup's largest eps1_32 is clear
+            # of the limit, so that the device decides as these formulas do.
+            assert 2 not in fp64 and 3 in fp64 and 4 in fp64, fp64
+            for w in groups:
+                if w not in slow:
+                    worst = float(e[w * WG:(w + 1) * WG].max())
+                    assert not 0.996 * EPS32_LIMIT < worst < 1.004 * EPS32_LIMIT, (w, worst / EPS32_LIMIT)
         on32 = elig.copy()
         for w in fp64:
             on32[w * WG:(w + 1) * WG] = False

@@ -13,6 +13,7 @@ import scipy.linalg as sla
 
 from bayesianoptimizer_amd import KernelParams, botorch_default_lengthscale
 from oracle import gp_oracle as O
+from tests.ard_util import ard_values
 from tests.oracle_engine import to_oracle_params
 
 KINDS = ["rbf", "matern52", "scale_linear_matern52"]
@@ -23,9 +24,11 @@ SEED_BLOCK, HEAD_ROWS = 1024, 128  # PRUNE_SEED, PRUNE_HEAD_ROWS of csrc/gpx_swe
 
 
 @lru_cache(maxsize=None)
-def problem(n, T=3, d=D, kinds=None, cov_fp32=()):
+def problem(n, T=3, d=D, kinds=None, cov_fp32=(), ard=False):
     """dict(X, Y, params, w, ym, ys, best_f): never modified by its users.  kinds: a tuple of kernel kinds to cycle
-    instead of KINDS; cov_fp32: the outputs built with the fp32 covariance."""
+    instead of KINDS; cov_fp32: the outputs built with the fp32 covariance; ard: output t takes the per-dimension
+    lengthscales and linear variances of tests/ard_util.py with seed d + t (a different set per output) in place of
+    the scalar ones."""
     X, y0 = O.synthetic_problem(n, d, 21)
     rng = np.random.default_rng(5)
     cols = [y0] + [np.cos(4.0 * X @ rng.random(d) + t) + 0.3 * y0 for t in range(1, T)]
@@ -34,6 +37,10 @@ def problem(n, T=3, d=D, kinds=None, cov_fp32=()):
     params = [KernelParams(kinds[t % len(kinds)], botorch_default_lengthscale(d) * (0.8 + 0.2 * t),
                            outputscale=1.0 + 0.25 * t, noise=1e-4 * (1 + t), const_mean=0.05 * t, linear_variance=0.3,
                            cov_fp32=t in cov_fp32) for t in range(T)]
+    if ard:
+        for t in range(T):
+            ls, lv = ard_values(d, d + t)
+            params[t] = params[t].replace(lengthscale=[float(v) for v in ls], linear_variance=[float(v) for v in lv])
     w = [1.0 / T] * T
     ym = [0.1 * t for t in range(T)]
     ys = [1.0 + 0.5 * t for t in range(T)]

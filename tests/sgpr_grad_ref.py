@@ -20,6 +20,7 @@ import scipy.linalg as sla
 import torch
 
 from bayesianoptimizer_amd import KernelParams
+from oracle import gp_oracle as O
 from tests import sgpr_ref as R
 
 # (b) against (a), entrywise |dg_i| / scale_i, largest over sgpr_ref's four shapes, the three kinds and all tasks
@@ -29,6 +30,16 @@ TAU0 = 6.5e-10
 TAU = 32 * TAU0
 # the extra shape of the DMAX = 16 kernels (n, M, d, T, input scale, noise), beside sgpr_ref.SHAPES
 SHAPE16 = (300, 64, 12, 1, 0.3, lambda t: 1e-2)
+# one shape per edge of the d-dispatched instances (DMAX = 4, 8, 16, 32): d = 4, 16, 32 fill theirs (no k < d guard is ever
+# false), d = 9 and 17 are the narrowest of the next (d = 17: a single real coordinate in the second 16-dimension sweep).
+# M = 130: the second row tile has two rows; n = 300 with chunk = 128: three chunks, the last of 44 columns.  Seeds 1000 d.
+DSHAPES = {
+    104: (300, 130, 4, 1, 0.3, lambda t: 1e-2),
+    109: (300, 64, 9, 1, 0.3, lambda t: 1e-2),
+    116: (300, 64, 16, 2, 0.3, lambda t: 1e-2),
+    117: (300, 130, 17, 1, 0.3, lambda t: 1e-2),
+    132: (300, 64, 32, 2, 0.3, lambda t: 1e-3 * (t + 1)),
+}
 
 KINDS = ("rbf", "matern52", "scale_linear_matern52")
 ENTRIES = ("noise", "outputscale", "const_mean", "lengthscale", "linear_variance")
@@ -227,21 +238,26 @@ def make_problem(n, M, d, T, s, noise_of, seed) -> R.Problem:
     X = s * rng.standard_normal((n, d))
     Z = np.repeat(X[rng.choice(n, size=M, replace=False)][None], T, axis=0)
     Y = np.empty((n, T))
-    kps = []
+    kps, ops = [], []
     for t in range(T):
         ls, lv = 0.8 + rng.random(d), 0.05 + 0.1 * rng.random(d)
         os_, noise, c = 0.5 + rng.random(), noise_of(t), 0.1 * t - 0.2
         kps.append(KernelParams("scale_linear_matern52", list(ls), outputscale=os_, noise=noise, const_mean=c,
                                 linear_variance=list(lv)))
+        ops.append(O.KernelParams(O.SCALE_LINEAR_MATERN52, ls, outputscale=os_, noise=noise, const_mean=c,
+                                  linear_variance=lv))
         w = rng.standard_normal(d)
         Y[:, t] = c + np.sin(X @ w) + 0.3 * (X @ rng.standard_normal(d)) + np.sqrt(noise) * rng.standard_normal(n)
-    return R.Problem(X, Y, Z, kps, [])
+    return R.Problem(X, Y, Z, kps, ops)
 
 
 @functools.lru_cache(maxsize=None)
 def problem(shape) -> R.Problem:
-    """sgpr_ref.problem(shape) for its shapes 1-4; shape 16: SHAPE16."""
-    pb = make_problem(*SHAPE16, seed=16000) if shape == 16 else R.problem(shape)
+    """sgpr_ref.problem(shape) for its shapes 1-4; shape 16: SHAPE16; the DSHAPES by their keys."""
+    if shape in DSHAPES:
+        pb = make_problem(*DSHAPES[shape], seed=1000 * DSHAPES[shape][2])
+    else:
+        pb = make_problem(*SHAPE16, seed=16000) if shape == 16 else R.problem(shape)
     for a in (pb.X, pb.Y, pb.Z):
         a.setflags(write=False)
     return pb

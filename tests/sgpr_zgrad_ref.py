@@ -20,12 +20,12 @@ import torch
 from tests import sgpr_grad_ref as G
 from tests import sgpr_ref as R
 
-# (b) against (a), entrywise |d| / scale, largest over sgpr_grad_ref.problem's shapes 1-4 and 16, the three kinds and all
-# tasks: tests/test_svgp_zgrad_host.py measures and prints it (4.76e-12, attained at shape 2, rbf, task 0).  The GPU tests leave the
-# project's factor 32 for the different summation order (sgpr_grad_ref.TAU).
+# (b) against (a), entrywise |d| / scale, largest over sgpr_grad_ref.problem's shapes (1-4, 16 and its DSHAPES), the
+# three kinds and all tasks: tests/test_svgp_zgrad_host.py measures and prints it (4.76e-12, attained at shape 2, rbf,
+# task 0).  The GPU tests leave the project's factor 32 for the different summation order (sgpr_grad_ref.TAU).
 TAUZ0 = 4.8e-12
 TAUZ = 32 * TAUZ0
-SHAPES = (1, 2, 3, 4, 16)
+SHAPES = (1, 2, 3, 4, 16) + tuple(G.DSHAPES)
 
 
 def _bound_t(Zt, Xt, yt, p, kind, jitter):

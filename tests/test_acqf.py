@@ -9,22 +9,39 @@ from bayesianoptimizer_amd import acqf
 from bayesianoptimizer_amd.models import ExactGP
 from bayesianoptimizer_amd.transforms import Standardize
 from oracle import gp_oracle as O
+from tests.ard_util import ard_params
 from tests.test_gpu_parity import DEV, pair, t
 
 pytestmark = pytest.mark.gpu
 
 
+# Every DMAX instance of moments_grad_kernel (4, 8, 16, 32) at its widest d and the next at its narrowest, and d = 1, with
+# ARD parameters.  n = 70: most of the 256 threads idle in block_sum; 257: one element on the second pass of the thread
+# loop.  m = 4 q candidates, two of them degenerate (see the test).
+D_LADDER = [pytest.param(n, q, 4 * q, d, True, id=f"{n}-{q}-{4 * q}-d{d}-ard")
+            for d in (1, 4, 9, 16, 17, 32) for n in (70, 257) for q in (1, 3)]
+
+
 @pytest.mark.parametrize("kind", ["rbf", "matern52", "scale_linear_matern52"])
-@pytest.mark.parametrize("n,q,m", [(200, 1, 37), (700, 3, 30), (1500, 4, 64)])
-def test_moments_grad_matches_oracle(engine, kind, n, q, m):
-    d = 5
+@pytest.mark.parametrize("n,q,m,d,ard", [pytest.param(200, 1, 37, 5, False, id="200-1-37"),
+                                         pytest.param(700, 3, 30, 5, False, id="700-3-30"),
+                                         pytest.param(1500, 4, 64, 5, False, id="1500-4-64")] + D_LADDER)
+def test_moments_grad_matches_oracle(engine, kind, n, q, m, d, ard):
+    """The ARD cases put two degenerate rows among the candidates: candidate 0 equals a training row (r = 0 against it),
+    and for q > 1 two candidates of the second batch are equal (r = 0 inside the batch's covariance block)."""
     X, y = O.synthetic_problem(n, d, n + q)
-    kp, op = pair(kind, d, noise=1e-3, outputscale=1.4, const_mean=0.2)
+    kw = dict(noise=1e-3, outputscale=1.4, const_mean=0.2)
+    kp, op = ard_params(kind, d, d, **kw) if ard else pair(kind, d, **kw)
     st = engine.fit(t(X), t(y), kp)
     ost = O.fit(X, y, op)
     Xs = np.random.default_rng(m).random((m, d))
+    if ard:
+        Xs[0] = X[n // 2]
+        if q > 1:
+            Xs[q + 1] = Xs[q]
     mean, dmean, cov, dcov = (v.cpu().numpy() for v in engine.moments_grad(st, t(Xs), q))
     rm, rdm, rc, rdc = O.moments_grad(ost, Xs, q)
+    assert np.isfinite(rdm).all() and np.isfinite(rdc).all()
     assert np.abs(mean - rm).max() <= 1e-9 * np.abs(rm).max()
     assert np.abs(dmean - rdm).max() <= 1e-8 * np.abs(rdm).max()
     assert np.abs(cov - rc).max() <= 1e-9 * op.outputscale

@@ -39,10 +39,16 @@ def _compare_states(engine, st, ref, n, atol_scale=1e-9):
 @pytest.mark.parametrize("kind", ["rbf", "matern52", "scale_linear_matern52"])
 @pytest.mark.parametrize("n_old,q", [(100, 5), (256, 1), (300, 64), (1000, 200), (1024, 130), (2000, 700)])
 def test_append_matches_refit_and_oracle(engine, kind, n_old, q):
-    d, nrhs = 6, 2
+    d = 6
+    kp, op = pair(kind, d, noise=2e-4, outputscale=1.3)
+    check_append_matches_refit_and_oracle(engine, kp, op, n_old, q, d, kind)
+
+
+def check_append_matches_refit_and_oracle(engine, kp, op, n_old, q, d, what):
+    """The check of test_append_matches_refit_and_oracle for one (engine, oracle) parameter pair."""
+    nrhs = 2
     n = n_old + q
     X, Y = _problem(n, d, nrhs, n_old + 7 * q)
-    kp, op = pair(kind, d, noise=2e-4, outputscale=1.3)
     st = engine.fit(t(X[:n_old]), t(Y[:n_old]), kp, capacity=n)
     ld0 = st.L.stride(0)
     st = engine.append(st, t(X), t(Y))
@@ -59,7 +65,7 @@ def test_append_matches_refit_and_oracle(engine, kind, n_old, q):
     bv, bi, sg = engine.acquire(st, t(Xq), "logei", best_f=float(Y[:, 0].max()), return_scores=True)
     sref = O.acquisition(*O.posterior(O.GPState(X, ost.L, ost.alpha[:, 0], op), Xq), O.ACQ_LOGEI,
                          best_f=float(Y[:, 0].max()))
-    check_argmax(int(bi.item()), sref, sg.cpu().numpy(), f"append {kind}")
+    check_argmax(int(bi.item()), sref, sg.cpu().numpy(), f"append {what}")
 
 
 def test_append_sequence_grows_buffers(engine):

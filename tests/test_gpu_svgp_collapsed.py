@@ -16,6 +16,7 @@ from bayesianoptimizer_amd import NotPositiveDefiniteError, _capi
 from bayesianoptimizer_amd.engine import KernelParamsC
 from bayesianoptimizer_amd.svgp import SVGPModel, SVGPPredictor
 from oracle import gp_oracle as O
+from tests import sgpr_grad_ref as G
 from tests import sgpr_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -26,9 +27,9 @@ NQ = 500
 @functools.lru_cache(maxsize=None)
 def reference(shape, jitter=R.JITTER):
     """(problem, reference vmean / vchol / bound, query points, reference predictive), computed once per shape."""
-    pb = R.problem(shape)
+    pb = G.problem(shape) if shape in G.DSHAPES else R.problem(shape)
     vmean, vchol, bound = R.fit_collapsed(pb, jitter)
-    s = R.SHAPES[shape][4]
+    s = (G.DSHAPES[shape] if shape in G.DSHAPES else R.SHAPES[shape])[4]
     Xq = s * np.random.default_rng(77 + shape).standard_normal((NQ, pb.X.shape[1]))
     mu, var, _ = O.svgp_predict(pb.Z, vmean, vchol, pb.ops, Xq, jitter=jitter)
     for a in (vmean, vchol, bound, Xq, mu, var, pb.X, pb.Y, pb.Z):
@@ -101,8 +102,10 @@ def raw_fit(engine, kps, Z, X, Y, jitter, chunk=0):
 
 
 # ---- 1 + 2: parity of the predictive and of the bound, every shape --------------------------------------------------
-@pytest.mark.parametrize("shape", [1, 2, 3, 4])
+@pytest.mark.parametrize("shape", [1, 2, 3, 4] + list(G.DSHAPES))
 def test_fit_collapsed_predictive_and_bound_match_reference(engine, shape):
+    """sgpr_grad_ref.DSHAPES (d = 4, 9, 16, 17, 32) beside sgpr_ref's: the K_ZZ and chunk kernels and the predictive's
+    K* build at the widest and the narrowest d of every DMAX instance."""
     pb, _, _, bound_r, Xq, mu_r, var_r = reference(shape)
     model = SVGPModel.fit_collapsed(dev(engine, pb.X), dev(engine, pb.Y), pb.kps, dev(engine, pb.Z), engine=engine)
     assert model.num_tasks == len(pb.kps) and model.bound.shape == (len(pb.kps), 6) and not model.bound.is_cuda

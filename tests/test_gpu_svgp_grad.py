@@ -53,9 +53,11 @@ def raw_grad(engine, kps, Z, X, Y, jitter, chunk=0, ws_bytes=None):
 
 
 # ---- 1: the gradient against autograd, every shape and kind ---------------------------------------------------------
-@pytest.mark.parametrize("shape", [1, 2, 3, 4, 16])
+@pytest.mark.parametrize("shape", [1, 2, 3, 4, 16] + list(G.DSHAPES))
 @pytest.mark.parametrize("kind", G.KINDS)
 def test_gradient_matches_autograd(engine, shape, kind):
+    """sgpr_grad_ref.DSHAPES (d = 4, 9, 16, 17, 32): every DMAX instance at its widest d and the next at its narrowest;
+    d = 17 and 32 run the two 16-dimension sweeps of the DMAX = 32 instance."""
     pb, kps, refs = G.reference(shape, kind)
     got = engine.svgp_bound_value_grad(kps, dev(engine, pb.Z), dev(engine, pb.X), dev(engine, pb.Y), jitter=R.JITTER)
     assert len(got) == len(refs)

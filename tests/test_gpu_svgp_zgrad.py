@@ -59,11 +59,14 @@ def raw_grad_z(engine, kps, Z, X, Y, jitter, chunk=0, ws_bytes=None, dZ="new", l
 
 
 # ---- 1: dZ against autograd ---------------------------------------------------------------------------------------
-@pytest.mark.parametrize("shape,chunk", [(1, 128), (1, None), (2, None), (3, None), (16, None)])
+@pytest.mark.parametrize("shape,chunk", [(1, 128), (1, None), (2, None), (3, None), (16, None)]
+                         + [(s, None) for s in G.DSHAPES] + [(117, 128), (132, 128)])
 @pytest.mark.parametrize("kind", G.KINDS)
 def test_dz_matches_autograd(engine, shape, chunk, kind):
     """Shape 1 (M = 130): two row tiles, the second of 2 rows; with chunk 128 five column blocks over five chunks, the
-    last of 8 columns.  Shape 2 (M = 200, T = 3): per-task parameters.  Shape 16 (d = 12): the DMAX = 16 kernels."""
+    last of 8 columns.  Shape 2 (M = 200, T = 3): per-task parameters.  Shape 16 (d = 12): the DMAX = 16 kernels.
+    sgpr_grad_ref.DSHAPES (d = 4, 9, 16, 17, 32): each instance at its widest and its narrowest d; the DMAX = 32 ones
+    (117, 132) also with chunk 128: n = 300 in three chunks, the last of 44 columns."""
     pb, kps, refs = ZR.reference(shape, kind)
     out, dZ, info = engine.svgp_bound_grad_z(kps, dev(engine, pb.Z), dev(engine, pb.X), dev(engine, pb.Y),
                                              jitter=R.JITTER, chunk=chunk)
@@ -74,9 +77,11 @@ def test_dz_matches_autograd(engine, shape, chunk, kind):
 
 
 # ---- 2: out is the hyperparameter gradient call's, bit for bit ------------------------------------------------------
-@pytest.mark.parametrize("chunk", [128, None])
-def test_out_bits_equal_the_hyperparameter_gradient_call(engine, chunk):
-    pb = G.problem(2)
+@pytest.mark.parametrize("shape,chunk", [pytest.param(2, 128, id="128"), pytest.param(2, None, id="None"),
+                                         pytest.param(132, 128, id="132-128"), pytest.param(132, None, id="132-None")])
+def test_out_bits_equal_the_hyperparameter_gradient_call(engine, chunk, shape):
+    """Shape 132 (d = 32): the ZG instance keeps the other instance's sums bit for bit at DMAX = 32 too."""
+    pb = G.problem(shape)
     Z, X, Y = dev(engine, pb.Z), dev(engine, pb.X), dev(engine, pb.Y)
     base, ib = engine.svgp_bound_grad(pb.kps, Z, X, Y, chunk=chunk)
     out, dZ, info = engine.svgp_bound_grad_z(pb.kps, Z, X, Y, chunk=chunk)

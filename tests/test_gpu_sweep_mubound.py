@@ -119,11 +119,15 @@ def test_fast_exponential_against_the_device_exp(engine):
 # ---- the gather build's mean partials ------------------------------------------------------------------------------
 @pytest.mark.parametrize("d", [4, 8, 16])
 def test_gather_partials_have_the_bits_of_the_full_build(engine, d):
-    n, m, cap, cnt = 300, 3000, 1500, 1061  # padded n = 384; the count is no multiple of 128
     rng = np.random.default_rng(7 + d)
+    kp = KernelParams("rbf", list(0.3 + rng.random(d)), outputscale=1.3)
+    check_gather_partials(engine, d, kp, rng)
+
+
+def check_gather_partials(engine, d, kp, rng):
+    n, m, cap, cnt = 300, 3000, 1500, 1061  # padded n = 384; the count is no multiple of 128
     X, _ = O.synthetic_problem(n, d, 21)
     Xs = rng.random((m, d))
-    kp = KernelParams("rbf", list(0.3 + rng.random(d)), outputscale=1.3)
     alpha = t(np.concatenate([rng.standard_normal(n) * 50.0, np.zeros(84)]))
     idx = rng.permutation(m)[:cap].astype(np.int32)
     Xd, Xsd = t(X), t(Xs)

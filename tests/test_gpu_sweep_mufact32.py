@@ -19,6 +19,7 @@ import torch
 
 from bayesianoptimizer_amd import KernelParams, botorch_default_lengthscale
 from oracle import gp_oracle as O
+from tests.ard_util import ard_params
 from tests.mu_bound_util import DEV, M, kstar_mu, mixed_candidates, mu_bound, mu_exact, t
 
 pytestmark = pytest.mark.gpu
@@ -27,13 +28,21 @@ _cands = {}
 _cases = {}
 
 
-def fitted(engine, n, d):
-    """One RBF fit per shape for the whole module; never modified."""
-    if (n, d) not in _fits:
+def fitted(engine, n, d, ard=False):
+    """One RBF fit per shape for the whole module; never modified.  ard: a lengthscale per dimension
+    (tests/ard_util.py, seed d) in place of the default one."""
+    if (n, d, ard) not in _fits:
         X, y = O.synthetic_problem(n, d, 21)
         kp = KernelParams("rbf", botorch_default_lengthscale(d), noise=1e-4)
-        _fits[(n, d)] = (engine.fit(t(X), t(y), kp), X, y, kp)
-    return _fits[(n, d)]
+        if ard:
+            kp = ard_params("rbf", d, d, noise=1e-4)[0]
+        _fits[(n, d, ard)] = (engine.fit(t(X), t(y), kp), X, y, kp)
+    return _fits[(n, d, ard)]
+
+
+def lengthscale(kp, d, ard):
+    """What the numpy restatements divide by: the scalar of the default fits, the vector of the ARD ones."""
+    return np.array(kp.lengthscales(d)) if ard else botorch_default_lengthscale(d)
 
 
 def candidates(m, d):
@@ -55,12 +64,12 @@ def alpha_cases(st, n, rng):
             "zero": torch.zeros_like(alt)}
 
 
-def run_case(engine, n, d):
+def run_case(engine, n, d, ard=False):
     """One shape's mixed candidates through every alpha case, once per module: name -> (mu_approx, mu_slack, mu,
     fallback, fp64form), and the candidates' layout."""
-    if (n, d) not in _cases:
-        st, X, y, kp = fitted(engine, n, d)
-        ls = botorch_default_lengthscale(d)
+    if (n, d, ard) not in _cases:
+        st, X, y, kp = fitted(engine, n, d, ard)
+        ls = lengthscale(kp, d, ard)
         rng = np.random.default_rng(1000 * n + d)
         Xs, slow, fp64, on32, on64 = mixed_candidates(X, ls, rng)
         Xd, Xsd = t(X), t(Xs)
@@ -69,8 +78,8 @@ def run_case(engine, n, d):
             mu = mu_exact(kstar_mu(engine, kp, Xd, alpha, Xsd, M)[1], M)
             ma, sl, fallback, fp64form = mu_bound(engine, kp, Xd, alpha, Xsd)
             res[name] = (alpha, ma, sl, mu, fallback, fp64form)
-        _cases[(n, d)] = (res, X, Xs, slow, fp64, on32, on64)
-    return _cases[(n, d)]
+        _cases[(n, d, ard)] = (res, X, Xs, slow, fp64, on32, on64)
+    return _cases[(n, d, ard)]
 
 
 def path_ratios(err, sl, masks):
@@ -84,7 +93,11 @@ def path_ratios(err, sl, masks):
 
 @pytest.mark.parametrize("n,d", [(300, 5), (300, 8), (640, 5), (640, 8), (300, 3), (300, 16)])
 def test_bound_holds_on_all_three_paths(engine, n, d):
-    res, X, Xs, slow, fp64, on32, on64 = run_case(engine, n, d)
+    check_bound_on_all_three_paths(engine, n, d)
+
+
+def check_bound_on_all_three_paths(engine, n, d, ard=False):
+    res, X, Xs, slow, fp64, on32, on64 = run_case(engine, n, d, ard)
     fin = np.isfinite(Xs).all(axis=1)
     finite = torch.tensor(fin, device=DEV)
     masks = {"fp32 form": on32, "fp64 form": on64, "unfactorised": fin & ~on32 & ~on64}
@@ -104,10 +117,15 @@ def test_bound_holds_on_all_three_paths(engine, n, d):
 @pytest.mark.parametrize("n", [300, 640])
 def test_slack_size_on_the_factorised_forms(engine, n, d):
     """mu_slack <= 2^-18 sum |alpha_j| k_j + 2^-20 outputscale |alpha|_1 for every candidate on a factorised form."""
-    res, X, Xs, slow, fp64, on32, on64 = run_case(engine, n, d)
+    check_slack_size_on_the_factorised_forms(engine, n, d)
+
+
+def check_slack_size_on_the_factorised_forms(engine, n, d, ard=False, only=None):
+    """only: a boolean mask that narrows the factorised candidates checked (None: all of them)."""
+    res, X, Xs, slow, fp64, on32, on64 = run_case(engine, n, d, ard)
     alpha, ma, sl, mu, _, _ = res["fitted"]
-    fact = on32 | on64
-    okp = O.KernelParams(O.RBF, np.full(d, botorch_default_lengthscale(d)))
+    fact = (on32 | on64) if only is None else (on32 | on64) & only
+    okp = O.KernelParams(O.RBF, np.array(fitted(engine, n, d, ard)[3].lengthscales(d)))
     a = alpha[:n].cpu().numpy()
     A = np.abs(a) @ O.kernel_matrix(X, Xs[fact], okp)
     cap = t(2.0 ** -18 * A + 2.0 ** -20 * 1.0 * np.abs(a).sum())

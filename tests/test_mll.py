@@ -135,7 +135,10 @@ def test_fit_hyperparameters_oracle_reaches_stationary_point():
 # ---- GPU: kernel parity and the GPU-driven fit ---------------------------------------------------------
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind", list(KINDS))
-@pytest.mark.parametrize("n,d", [(1, 1), (100, 3), (257, 8), (700, 5), (300, 20)])
+@pytest.mark.parametrize("n,d", [(1, 1), (100, 3), (257, 8), (700, 5), (300, 20),
+                                 # the DMAX instances' edges: 4 and 16 fill theirs, 17 is the last one's narrowest d,
+                                 # 32 fills it
+                                 (130, 4), (130, 16), (130, 17), (130, 32)])
 def test_mll_grad_gpu_vs_oracle(engine, kind, n, d):
     X, y = problem(n, d, 100 + n + d)
     rng = np.random.default_rng(n)

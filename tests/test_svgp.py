@@ -14,7 +14,10 @@ from bayesianoptimizer_amd.svgp import NOISE_LOWER_BOUND, SVGPModel
 from oracle import gp_oracle as O
 
 
-def svgp_problem(T=3, M=300, d=5, seed=0):
+ORACLE_KIND = {"rbf": O.RBF, "matern52": O.MATERN52, "scale_linear_matern52": O.SCALE_LINEAR_MATERN52}
+
+
+def svgp_problem(T=3, M=300, d=5, seed=0, kind="scale_linear_matern52"):
     rng = np.random.default_rng(seed)
     Z = rng.standard_normal((T, M, d))
     vmean = rng.standard_normal((T, M))
@@ -27,9 +30,8 @@ def svgp_problem(T=3, M=300, d=5, seed=0):
         ls = 0.8 + rng.random(d)
         lv = 0.05 + 0.1 * rng.random(d)
         os_, noise, c = 0.5 + rng.random(), 1e-3 * (t + 1), 0.1 * t - 0.2
-        kps.append(KernelParams("scale_linear_matern52", list(ls), outputscale=os_, noise=noise, const_mean=c,
-                                linear_variance=list(lv)))
-        ops.append(O.KernelParams(O.SCALE_LINEAR_MATERN52, ls, outputscale=os_, noise=noise, const_mean=c,
+        kps.append(KernelParams(kind, list(ls), outputscale=os_, noise=noise, const_mean=c, linear_variance=list(lv)))
+        ops.append(O.KernelParams(ORACLE_KIND[kind], ls, outputscale=os_, noise=noise, const_mean=c,
                                   linear_variance=lv))
     return Z, vmean, vchol, kps, ops
 
@@ -94,10 +96,22 @@ def test_svgp_model_from_gpytorch_state_dict():
 
 
 # ---- GPU: the HIP path against the oracle ---------------------------------------------------------------------
+# the d-ladder: every DMAX instance (4, 8, 16, 32) of the SVGP-mode K* build at its widest d and the next at its narrowest;
+# M = 130: the second row tile has two rows; per-dimension lengthscales and linear variances as in every svgp_problem
+D_LADDER = [(1, 130, 4, 300), (1, 64, 9, 300), (2, 64, 16, 300), (2, 130, 17, 300), (1, 64, 32, 300)]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("T,M,d,m", [(3, 300, 5, 700), (8, 128, 5, 2500), (1, 1000, 8, 300)])
-def test_svgp_predict_matches_oracle(engine, T, M, d, m):
-    Z, vmean, vchol, kps, ops = svgp_problem(T, M, d, seed=T + M)
+@pytest.mark.parametrize("T,M,d,m,kind", [
+    pytest.param(3, 300, 5, 700, "scale_linear_matern52", id="3-300-5-700"),
+    pytest.param(8, 128, 5, 2500, "scale_linear_matern52", id="8-128-5-2500"),
+    pytest.param(1, 1000, 8, 300, "scale_linear_matern52", id="1-1000-8-300"),
+    pytest.param(3, 300, 5, 700, "rbf", id="3-300-5-700-rbf"),
+    pytest.param(3, 300, 5, 700, "matern52", id="3-300-5-700-matern52"),
+] + [pytest.param(*c, k, id="-".join(map(str, c)) + "-" + k) for c in D_LADDER
+     for k in ("rbf", "matern52", "scale_linear_matern52")])
+def test_svgp_predict_matches_oracle(engine, T, M, d, m, kind):
+    Z, vmean, vchol, kps, ops = svgp_problem(T, M, d, seed=T + M, kind=kind)
     Xs = np.random.default_rng(9).standard_normal((m, d))
     prep = engine.svgp_prepare(kps, Z, vmean, vchol)
     mu, var, score = engine.svgp_predict(prep, torch.tensor(Xs, device=engine.device))

@@ -21,7 +21,7 @@ from tests.oracle_engine import OracleEngine, to_oracle_params
 ORACLE_KIND = {"rbf": O.RBF, "matern52": O.MATERN52, "scale_linear_matern52": O.SCALE_LINEAR_MATERN52}
 
 
-@pytest.mark.parametrize("shape", [1, 2, 3, 4])
+@pytest.mark.parametrize("shape", [1, 2, 3, 4] + list(G.DSHAPES))
 @pytest.mark.parametrize("kind", G.KINDS)
 def test_autograd_bound_equals_the_fit_reference(shape, kind):
     pb, kps, refs = G.reference(shape, kind)
@@ -36,18 +36,42 @@ def test_formulas_equal_autograd_and_fix_the_tolerance():
     32 tau0 (sgpr_grad_ref.TAU) must cover it with that margin and stay below 1e-6, or the H arrangement is the wrong
     one to build."""
     tau0, where = 0.0, None
-    for shape in (1, 2, 3, 4):
+    per_shape = {}
+    for shape in (1, 2, 3, 4) + tuple(G.DSHAPES):
         for kind in G.KINDS:
             pb, kps, refs = G.reference(shape, kind)
             for t, a in enumerate(refs):
                 b = G.formula_task(pb.Z[t], pb.X, pb.Y[:, t], kps[t])
                 ratio = G.entry_ratio(b, a)
                 assert abs(b["nll"] - a["nll"]) <= 1e-11 * np.abs(a["bound"][1:]).sum()
+                per_shape[shape] = max(per_shape.get(shape, 0.0), ratio)
                 if ratio > tau0:
                     tau0, where = ratio, (shape, kind, t)
     print(f"tau0 = {tau0:.3e} at (shape, kind, task) = {where}; recorded TAU0 = {G.TAU0:.2e}, tau = {G.TAU:.2e}")
+    print("per shape: " + ", ".join(f"{s}: {r:.1e}" for s, r in per_shape.items()))
     assert G.TAU <= 1e-6
     assert tau0 <= 2.0 * G.TAU0, "the recorded tau0 no longer describes the references"
+    for shape in G.DSHAPES:  # the d-ladder's shapes sit below the recorded tau0: the tolerance does not move for them
+        assert per_shape[shape] <= G.TAU0, (shape, per_shape[shape])
+
+
+@pytest.mark.parametrize("shape", list(G.DSHAPES))
+def test_d_ladder_shapes_are_well_conditioned(shape):
+    """cond(K_ZZ + jitter) <= 4e5 and cond(B) <= 1.1e4 with the problems' own kind and with matern52, every task.  The
+    smoother RBF kernel on the same Z is the worst case (5.2e5 and 1.2e4, both at shape 104): it is held to 1e6 and 2e4,
+    where eps cond is still an order below the suite's 1e-9.  So the references' disagreement measured above is rounding
+    of a well-posed problem, not the conditioning of these shapes."""
+    pb = G.problem(shape)
+    for kind in G.KINDS:
+        worst_a = worst_b = 0.0
+        for t, p in enumerate(pb.ops):
+            op = dataclasses.replace(p, kind=ORACLE_KIND[kind])
+            A = O.kernel_matrix(pb.Z[t], pb.Z[t], op) + R.JITTER * np.eye(pb.Z.shape[1])
+            worst_a = max(worst_a, np.linalg.cond(A))
+            worst_b = max(worst_b, np.linalg.cond(R.fit_collapsed_task(pb.Z[t], pb.X, pb.Y[:, t], op)["B"]))
+        print(f"shape {shape} {kind}: cond(K_ZZ + jitter) <= {worst_a:.2e}, cond(B) <= {worst_b:.2e}")
+        cap_a, cap_b = (1e6, 2e4) if kind == "rbf" else (4e5, 1.1e4)
+        assert worst_a <= cap_a and worst_b <= cap_b, kind
 
 
 # ---- the driver ---------------------------------------------------------------------------------------------------
