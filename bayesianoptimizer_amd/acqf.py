@@ -39,6 +39,7 @@ import numpy as np
 import torch
 
 from . import _capi
+from .engine import SVGPTaskState
 
 TAU_RELU = 1e-6
 TAU_MAX = 1e-2
@@ -57,6 +58,10 @@ class _Moments(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, Xs, engine, state, q, alpha):
+        if isinstance(state, SVGPTaskState) and not ctx.needs_input_grad[0]:
+            # scoring (raw samples, end points): the sparse model's call has a value-only form with the same bits
+            mean, _, cov, _ = engine.svgp_moments_grad(state.prep, state.task, Xs.detach(), q, need_grad=False)
+            return mean, cov
         mean, dmean, cov, dcov = engine.moments_grad(state, Xs.detach(), q, alpha)
         ctx.save_for_backward(dmean, dcov)
         ctx.q = q
@@ -101,7 +106,9 @@ class _Objective:
     offset.  Shared covariance (one factorisation): ONE term, the objective's mean sum_t w_t (y_mean_t + s_t mu_t) from
     the combined alpha and its covariance (sum_t w_t^2 s_t^2) Sigma_std.  Independent outputs (ExactGP independent
     mode, the multi-output SingleTaskGP): one term per output with a non-zero weight — mean sum_t w_t s_t mu_t + sum_t
-    w_t y_mean_t, covariance sum_t w_t^2 s_t^2 Sigma_t (the outputs are independent a posteriori)."""
+    w_t y_mean_t, covariance sum_t w_t^2 s_t^2 Sigma_t (the outputs are independent a posteriori).  A models.SparseGP is
+    such a model: its states are SVGPTaskStates (latent moments from gpx_svgp_moments_grad_f64) in the outputs' own
+    units."""
 
     def __init__(self, model, weights: Optional[Sequence[float]] = None, output: int = 0):
         T = model.num_outputs
@@ -121,7 +128,8 @@ class _Objective:
             for t in range(T):
                 if float(ws[t]) != 0.0:
                     st = model.states[t]
-                    self.terms.append((st, st.alpha[:, 0].contiguous(), float(ws[t]), float(ws[t]) ** 2))
+                    alpha = st.alpha if isinstance(st, SVGPTaskState) else st.alpha[:, 0].contiguous()
+                    self.terms.append((st, alpha, float(ws[t]), float(ws[t]) ** 2))
             self.offset = float((w * ym).sum())
             self.var_scale = float((ws * ws).sum())
             return

@@ -1610,6 +1610,42 @@ gpx_status gpx_svgp_predict_f64(gpx_handle h, const gpx_kernel_params* p, int64_
   return GPX_OK;
 }
 
+gpx_status gpx_svgp_moments_grad_workspace_size(int64_t M, int64_t m, size_t* bytes) {
+  if (!bytes || M < 1 || M > 65536 || m < 1 || m > GPX_MAX_GRAD_CANDIDATES) return GPX_INVALID_ARG;
+  *bytes = gpx::svgp_moments_ws_doubles((int)padded(M), (int)m) * sizeof(double) + 256;
+  return GPX_OK;
+}
+
+gpx_status gpx_svgp_moments_grad_f64(gpx_handle h, const gpx_kernel_params* p, int64_t M, const double* Z, int64_t ldz,
+                                     const double* W, const double* W2, const double* alpha, const double* Xs,
+                                     int64_t m, int64_t q, int64_t ldxs, double* mean, double* dmean, double* cov,
+                                     double* dcov, void* ws, size_t ws_bytes) {
+  Context* c = reinterpret_cast<Context*>(h);
+  if (!c) return GPX_INVALID_ARG;
+  GPX_TRY(check_svgp(c, p, 1, M));
+  if (m < 1 || m > GPX_MAX_GRAD_CANDIDATES) return fail(c, GPX_INVALID_ARG, "m must be in [1, GPX_MAX_GRAD_CANDIDATES]");
+  if (q < 1 || q > GPX_MAX_Q || m % q != 0) return fail(c, GPX_INVALID_ARG, "q must be in [1, GPX_MAX_Q] and divide m");
+  GPX_NONNULL(c, Z);
+  GPX_NONNULL(c, W);
+  GPX_NONNULL(c, W2);
+  GPX_NONNULL(c, alpha);
+  GPX_NONNULL(c, Xs);
+  GPX_NONNULL(c, mean);
+  GPX_NONNULL(c, cov);
+  GPX_NONNULL(c, ws);
+  if ((dmean == nullptr) != (dcov == nullptr))
+    return fail(c, GPX_INVALID_ARG, "dmean and dcov must both be set or both be NULL");
+  GPX_TRY(check_ld(c, ldz, p->d, "Z", false));
+  GPX_TRY(check_ld(c, ldxs, p->d, "Xs", false));
+  size_t need = 0;
+  GPX_TRY(gpx_svgp_moments_grad_workspace_size(M, m, &need));
+  if (ws_bytes < need) return fail(c, GPX_INVALID_ARG, "svgp moments_grad workspace too small");
+  GPX_USE_DEVICE(c);
+  return hip_check(c, gpx::launch_svgp_moments(c, *p, (int)M, (int)padded(M), Z, ldz, W, W2, alpha, Xs, ldxs, (int)m,
+                                               (int)q, mean, dmean, cov, dcov, align256(ws)),
+                   "svgp moments_grad");
+}
+
 // ---- SVGP variational posterior in closed form (gpx_svgpfit.hip) and the hyperparameter gradient of its
 // ---- bound (gpx_svgpgrad.hip): the gradient call is the fit's launches up to m', then a second pass over X ----------
 namespace {

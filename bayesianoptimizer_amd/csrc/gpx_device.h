@@ -18,6 +18,42 @@ __device__ __forceinline__ double cov_from_r2(int kind, double outputscale, doub
   return outputscale * (lin + m);
 }
 
+// k(a, b) and d1k(a, b)/da_j for j < d (a = the candidate, b = a training point or another candidate).
+template <int DMAX>
+__device__ __forceinline__ double cov_and_grad(const gpx_kernel_params& p, const double* a, const double* b,
+                                               double (&g)[DMAX]) {
+  double r2 = 0.0, lv = 0.0;
+  const bool lin = p.kind == GPX_KERNEL_SCALE_LINEAR_MATERN52;
+#pragma unroll
+  for (int k = 0; k < DMAX; ++k) {
+    g[k] = 0.0;
+    if (k < p.d) {
+      const double df = b[k] / p.lengthscale[k] - a[k] / p.lengthscale[k];
+      r2 += df * df;
+      if (lin) lv += b[k] * p.linear_variance[k] * a[k];
+    }
+  }
+  const double kv = cov_from_r2(p.kind, p.outputscale, r2, lv);
+  // d/da_j of the stationary part = coef * (a_j - b_j) / l_j^2
+  double coef;
+  if (p.kind == GPX_KERNEL_RBF) {
+    coef = -kv;
+  } else {
+    const double r = sqrt(r2);
+    const double s5r = 2.23606797749978969640917366873128 * r;
+    coef = -p.outputscale * (5.0 / 3.0) * (1.0 + s5r) * exp(-s5r);
+  }
+#pragma unroll
+  for (int k = 0; k < DMAX; ++k) {
+    if (k < p.d) {
+      const double l = p.lengthscale[k];
+      g[k] = coef * (a[k] / l - b[k] / l) / l;
+      if (lin) g[k] += p.outputscale * p.linear_variance[k] * b[k];
+    }
+  }
+  return kv;
+}
+
 // fp32 evaluation (gpx_kernel_params.cov_fp32, BASELINE configs[4]): r2 accumulated in fp32 from fp32-rounded
 // scaled inputs, exp / sqrt / Matern polynomial in fp32, widened to fp64 before the outputscale and linear part.
 __device__ __forceinline__ double cov_from_r2_f32(int kind, double outputscale, float r2, double lin) {

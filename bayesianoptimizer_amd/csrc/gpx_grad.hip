@@ -37,42 +37,6 @@ __global__ void __launch_bounds__(WG) kstar_plain_kernel(gpx_kernel_params p, in
   Ks[e] = v;
 }
 
-// k(a, b) and d1k(a, b)/da_j for j < d (a = the candidate, b = a training point or another candidate).
-template <int DMAX>
-__device__ __forceinline__ double cov_and_grad(const gpx_kernel_params& p, const double* a, const double* b,
-                                               double (&g)[DMAX]) {
-  double r2 = 0.0, lv = 0.0;
-  const bool lin = p.kind == GPX_KERNEL_SCALE_LINEAR_MATERN52;
-#pragma unroll
-  for (int k = 0; k < DMAX; ++k) {
-    g[k] = 0.0;
-    if (k < p.d) {
-      const double df = b[k] / p.lengthscale[k] - a[k] / p.lengthscale[k];
-      r2 += df * df;
-      if (lin) lv += b[k] * p.linear_variance[k] * a[k];
-    }
-  }
-  const double kv = cov_from_r2(p.kind, p.outputscale, r2, lv);
-  // d/da_j of the stationary part = coef * (a_j - b_j) / l_j^2
-  double coef;
-  if (p.kind == GPX_KERNEL_RBF) {
-    coef = -kv;
-  } else {
-    const double r = sqrt(r2);
-    const double s5r = 2.23606797749978969640917366873128 * r;
-    coef = -p.outputscale * (5.0 / 3.0) * (1.0 + s5r) * exp(-s5r);
-  }
-#pragma unroll
-  for (int k = 0; k < DMAX; ++k) {
-    if (k < p.d) {
-      const double l = p.lengthscale[k];
-      g[k] = coef * (a[k] / l - b[k] / l) / l;
-      if (lin) g[k] += p.outputscale * p.linear_variance[k] * b[k];
-    }
-  }
-  return kv;
-}
-
 // Deterministic 256-thread sum of `cnt` per-thread values (wave shuffles, then the 4 wave partials in order).
 template <int CNT>
 __device__ __forceinline__ void block_sum(double (&v)[CNT], double* red) {

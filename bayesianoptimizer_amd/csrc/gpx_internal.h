@@ -426,6 +426,20 @@ hipError_t launch_moments_grad(Context* c, const gpx_kernel_params& p, int n, in
                                const double* W, int64_t ldw, const double* alpha, const double* Xs, int64_t ldxs,
                                int m, int q, double* mean, double* dmean, double* cov, double* dcov, double* ws);
 
+// K*[i][c] = k(X_i, Xs_c) for i < n, c < m; 0 elsewhere (npad x mpad, row length mpad).  Defined in gpx_grad.hip; also
+// launched by gpx_svgpmom.hip.
+__global__ void __launch_bounds__(WG) kstar_plain_kernel(gpx_kernel_params p, int n, int npad, int m, int mpad,
+                                                         const double* __restrict__ X, int64_t ldx,
+                                                         const double* __restrict__ Xs, int64_t ldxs,
+                                                         double* __restrict__ Ks);
+
+// The same for one task of an SVGP (gpx_svgpmom.hip): W, W2 (Mpad x Mpad) and alpha (Mpad) are the task's blocks of
+// gpx_svgp_prepare_f64.  dmean / dcov both null: values only (the same bits of mean and cov).
+size_t svgp_moments_ws_doubles(int Mpad, int m);
+hipError_t launch_svgp_moments(Context* c, const gpx_kernel_params& p, int M, int Mpad, const double* Z, int64_t ldz,
+                               const double* W, const double* W2, const double* alpha, const double* Xs, int64_t ldxs,
+                               int m, int q, double* mean, double* dmean, double* cov, double* dcov, double* ws);
+
 // MC q-batch acquisition from the moments (gpx_mcacq.hip); gmean / gcov both null: value only
 size_t mc_acq_ws_doubles(int64_t B, int64_t q, int64_t S);
 hipError_t launch_mc_acq(Context* c, const gpx_mcacq_params& a, int B, int q, int S, const double* mean,

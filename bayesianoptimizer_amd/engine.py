@@ -138,6 +138,21 @@ class GPState:
             raise err
 
 
+@dataclass
+class SVGPTaskState:
+    """One output of a prepared SVGP (``GPEngine.svgp_prepare``) where the acquisition code expects a fitted state:
+    ``GPEngine.moments_grad`` dispatches on it to ``svgp_moments_grad``.  ``alpha`` is the task's alpha' = W m."""
+
+    prep: dict
+    task: int
+    d: int
+    params: KernelParams
+
+    @property
+    def alpha(self) -> torch.Tensor:
+        return self.prep["alpha"][self.task]
+
+
 def _ptr(t: Optional[torch.Tensor]):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
@@ -703,11 +718,15 @@ class GPEngine:
             ctypes.byref(ap), int(index_offset), k, _ptr(val), _ptr(idx), _ptr(ws), ws.numel()))
         return val, idx
 
-    def moments_grad(self, state: GPState, Xs, q: int = 1, alpha: Optional[torch.Tensor] = None):
+    def moments_grad(self, state, Xs, q: int = 1, alpha: Optional[torch.Tensor] = None):
         """Posterior mean / q-batch covariance of candidates Xs (m x d, consecutive q-batches) and their derivatives
         w.r.t. the candidates (gpx_moments_grad_f64), in the engine's standardised units:
         mean (m), dmean (m x d), cov (m x q: row a of its batch's q x q covariance), dcov (m x d x q, first-argument
         partials; see include/gpx.h for the chain rule).  ``alpha``: padded_n objective column (default output 0)."""
+        if isinstance(state, SVGPTaskState):
+            if alpha is not None and alpha.data_ptr() != state.alpha.data_ptr():
+                raise ValueError("an SVGP task's objective column is its own alpha'")
+            return self.svgp_moments_grad(state.prep, state.task, Xs, q)
         Xs = self._as_f64(Xs, "Xs")
         m, d = Xs.shape
         if d != state.d:
@@ -1043,6 +1062,38 @@ class GPEngine:
             _ptr(prep["alpha"]), _ptr(Xs), m, Xs.stride(0), float(min_var), _ptr(mean), T, _ptr(var), T, _ptr(score),
             _ptr(ws), ws.numel()))
         return mean, var, score
+
+    def svgp_moments_grad(self, prep: dict, task: int, Xs, q: int = 1, need_grad: bool = True):
+        """``moments_grad`` for task ``task`` of a prepared SVGP (gpx_svgp_moments_grad_f64): the latent posterior mean
+        (m) and q-batch covariance (m x q) of candidates Xs (m x d, consecutive q-batches) with their derivatives
+        w.r.t. the candidates, dmean (m x d) and dcov (m x d x q), in the engine's units; no likelihood noise and no
+        variance floor.  ``need_grad=False``: dmean and dcov are None, mean and cov keep their bits."""
+        Xs = self._as_f64(Xs, "Xs")
+        Z = prep["Z"]
+        T, M, d = Z.shape
+        task = int(task)
+        if not 0 <= task < T:
+            raise ValueError(f"task {task} outside [0, {T})")
+        m = Xs.shape[0]
+        if Xs.shape[1] != d:
+            raise ValueError(f"Xs has {Xs.shape[1]} columns, model has d={d}")
+        if m % q:
+            raise ValueError(f"{m} candidates do not form q-batches of {q}")
+        dev = self.device
+        mean = torch.empty((m,), dtype=torch.float64, device=dev)
+        cov = torch.empty((m, q), dtype=torch.float64, device=dev)
+        dmean = torch.empty((m, d), dtype=torch.float64, device=dev) if need_grad else None
+        dcov = torch.empty((m, d, q), dtype=torch.float64, device=dev) if need_grad else None
+        nbytes = ctypes.c_size_t()
+        self._check(self.lib.gpx_svgp_moments_grad_workspace_size(M, m, ctypes.byref(nbytes)))
+        ws = self.workspace("moments_grad", nbytes.value)
+        pc = prep["params"][task].to_c(d)
+        Zt, W, W2, alpha = Z[task], prep["W"][task], prep["W2"][task], prep["alpha"][task]
+        self._bind_stream()
+        self._check(self.lib.gpx_svgp_moments_grad_f64(
+            self.handle, ctypes.byref(pc), M, _ptr(Zt), Zt.stride(0), _ptr(W), _ptr(W2), _ptr(alpha), _ptr(Xs), m, q,
+            Xs.stride(0), _ptr(mean), _ptr(dmean), _ptr(cov), _ptr(dcov), _ptr(ws), ws.numel()))
+        return mean, dmean, cov, dcov
 
     def _rows_f64(self, t, name: str) -> torch.Tensor:
         """A 2-D fp64 device tensor with unit column stride; a row stride larger than the row length is kept."""

@@ -23,7 +23,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from ._capi import GPXTimeoutError, NotPositiveDefiniteError
-from .engine import KERNEL_KINDS, GPEngine, GPState, KernelParams, botorch_default_lengthscale
+from .engine import KERNEL_KINDS, GPEngine, GPState, KernelParams, SVGPTaskState, botorch_default_lengthscale
 from .transforms import Standardize
 
 
@@ -354,6 +354,17 @@ class SparseGP:
     def posterior(self, X) -> Posterior:
         mean, var = self.predictor.predict(X, transformed=True)
         return Posterior(mean=mean, variance=var)
+
+    @property
+    def states(self):
+        """One SVGPTaskState per output: what acqf's moment-based acquisitions (qLogExpectedImprovement,
+        qPosteriorStandardDeviation under optimize_acqf) read in place of an ExactGP's per-output states."""
+        prep = self.predictor.prep
+        d = prep["Z"].shape[2]
+        return [SVGPTaskState(prep, t, d, prep["params"][t]) for t in range(self.num_outputs)]
+
+    def _untransform(self):
+        return None, None  # the SVGP is fitted to the outcomes as they are given
 
 
 class _Analytic:

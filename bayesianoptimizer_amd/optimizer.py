@@ -17,7 +17,9 @@ hyperparameters are tied), in which case new observations are folded in by the b
 (``ExactGP.append_observations``) instead of a refit.  Opt-in above ``svgp_threshold`` points
 (``GPConfig.large_n_policy`` with ``large_n_model="sparse"``): Bayesian7's batched SVGP itself, its variational
 distribution in closed form for the fitted hyperparameters (``SVGPModel.fit_collapsed``, ``models.SparseGP``), serving
-``predict``, ``evaluate_model`` and the pool scan.  Acquisition modes (``acquisition=``):
+``predict``, ``evaluate_model``, the pool scan and, through its q-batch moments (``gpx_svgp_moments_grad_f64``),
+``"qpsd"`` (Bayesian6's large-n mode, ``Bayesian6.py:492-577,896-919``) and ``"qlogei"`` up to ``GPX_MAX_Q`` points per
+round; the other modes raise on it.  Acquisition modes (``acquisition=``):
 
 * ``"variance"`` (default, Bayesian7's pool scan ``:646-688``): Latin-hypercube pool -> summed posterior variance on
   the device -> top-K on the device (``gpx_topk_f64``, deterministic ties) -> farthest-point sampling on the device
@@ -54,6 +56,9 @@ from .models import ExactGP, SparseGP, reference_jitter_schedule
 from .transforms import LogInputStandardizer, LogOutputStandardizer
 
 INPUT_COLUMNS = ("n", "eta", "sigma_y", "width", "height")  # simulator parameters, config/config.py order
+# what the sparse surrogate (GPConfig.large_n_model = "sparse") serves: the pool scan, and optimize_acqf on the MC
+# acquisitions that need only q-batch moments (gpx_svgp_moments_grad_f64)
+SPARSE_ACQUISITIONS = ("variance", "qpsd", "qlogei")
 
 
 @dataclass
@@ -101,8 +106,9 @@ class GPConfig:
     # max_inducing_points inducing points (farthest-point sampled from a random inducing_subset_size-row subsample of
     # the training inputs, Bayesian7.py:45,48,109-123) whose variational distribution is the closed-form optimum for
     # the hyperparameters (SVGPModel.fit_collapsed), refitted every round in O(n M^2) time and O(T M^2) memory.  The
-    # hyperparameters come as in the exact mode (subsample marginal likelihood, or the fixed values).  Only
-    # acquisition="variance" (the reference's pool scan) runs on the sparse surrogate.
+    # hyperparameters come as in the exact mode (subsample marginal likelihood, or the fixed values).  The sparse
+    # surrogate serves acquisition="variance" (the reference's pool scan), "qpsd" (Bayesian6's acquisition on its
+    # per-output SVGPs) and "qlogei" (at most GPX_MAX_Q points per round: it has no kriging believer).
     large_n_model: str = "exact"
     # where the sparse model's hyperparameters come from (with fit_hyperparameters): "subsample", the exact marginal
     # likelihood on the svgp_threshold-point subsample (above), or "bound": the collapsed bound of the sparse model
@@ -243,7 +249,7 @@ class BayesianOptimizer:
         if self.config.sparse_inducing == "learned" and self.config.sparse_hyperparameters != "bound":
             raise ValueError("GPConfig.sparse_inducing='learned' requires sparse_hyperparameters='bound': the inducing "
                              "points are learned by maximising the collapsed bound")
-        if self._sparse_policy() and self.acquisition != "variance":
+        if self._sparse_policy() and self.acquisition not in SPARSE_ACQUISITIONS:
             raise ValueError(f"acquisition '{self.acquisition}' is not available with GPConfig.large_n_model='sparse': "
                              "the sparse surrogate serves acquisition='variance' (the pool scan) only")
         self.seed = kwargs.get("seed", None)
@@ -555,7 +561,7 @@ class BayesianOptimizer:
             return torch.empty((0, self.dim), dtype=self.dtype, device=self.gp_device)
         if self.acquisition == "variance":
             return self._pool_scan(k)
-        if isinstance(self.gp_model, SparseGP):
+        if isinstance(self.gp_model, SparseGP) and self.acquisition not in SPARSE_ACQUISITIONS:
             raise ValueError(f"acquisition '{self.acquisition}' is not available on the sparse surrogate "
                              "(GPConfig.large_n_model='sparse' serves acquisition='variance' only)")
         if self.acquisition == "qlogei":
@@ -604,16 +610,20 @@ class BayesianOptimizer:
     def _acquire_qlogei(self, k: int) -> torch.Tensor:
         """optimize_acqf on MC qLogEI (Bayesian.py:96-113: 512 Sobol base samples, 10 restarts, 1024 raw samples,
         batch_limit 5, maxiter 200) in the unit cube through the log-input transform.  Chunks of at most GPX_MAX_Q
-        points; after each, the model is conditioned on the chunk with its posterior mean (kriging believer)."""
+        points; after each, the model is conditioned on the chunk with its posterior mean (kriging believer).  The
+        sparse surrogate has no such conditioning: it serves k <= GPX_MAX_Q, one joint q-batch."""
         from .acqf import LinearMCObjective, SobolQMCNormalSampler, optimize_acqf, qLogExpectedImprovement
 
         cfg = self.config
+        model = self.gp_model
+        if isinstance(model, SparseGP) and k > _capi.GPX_MAX_Q:
+            raise ValueError(f"acquisition 'qlogei' on the sparse surrogate serves at most {_capi.GPX_MAX_Q} points per "
+                             f"round (asked for {k}): the sparse model cannot be conditioned on a chunk")
         w = self._acq_weights()
         best_f = self._incumbent(w)
         objective = LinearMCObjective(w.cpu())
         unit_box = torch.stack([torch.zeros(self.dim), torch.ones(self.dim)]).to(self.dtype)
         x_tf = self.x_tf
-        model = self.gp_model
         picked: List[torch.Tensor] = []
         remaining = k
         while remaining > 0:
@@ -683,7 +693,8 @@ class BayesianOptimizer:
         evenly as possible, the first k mod T outputs taking one more (the reference's quota heuristic,
         Bayesian6.py:771-788, is not restated), in chunks of at most GPX_MAX_Q.  Points picked for earlier outputs
         do not enter later ones: the reference sets them as X_pending, which its custom forward never reads
-        [upstream, unverified]."""
+        [upstream, unverified].  On the sparse surrogate this is Bayesian6's large-n mode (:492-577, 589-596): the
+        same acquisition on the per-output SVGPs."""
         from .acqf import SobolQMCNormalSampler, optimize_acqf, qPosteriorStandardDeviation
 
         cfg = self.config

@@ -599,6 +599,29 @@ gpx_status gpx_svgp_predict_f64(gpx_handle h, const gpx_kernel_params* p, int64_
                                 int64_t ldmean, double* var_out, int64_t ldvar, double* score_out, void* ws,
                                 size_t ws_bytes);
 
+/* Posterior moments of m candidates Xs (m x d, consecutive q-batches) under ONE task of a prepared SVGP, and their
+ * derivatives w.r.t. the candidates: gpx_moments_grad_f64 for the sparse model (optimize_acqf on the per-output SVGPs of
+ * optimization/Bayesian6.py:492-577, 896-919).  p: the task's parameters; Z (M x d): its inducing points; W, W2
+ * (Mpad x Mpad each) and alpha (Mpad): the task's blocks of gpx_svgp_prepare_f64.  With k_a = K(Z, x_a) and c ranging over
+ * a's batch:
+ *   v_c = W^T k_c,  u_c = W2^T k_c,  h_c = W v_c - W2 u_c          (= L^{-T} (I - S S^T) L^{-1} k_c)
+ *   mean[a]       = const_mean + k_a^T alpha                  dmean[a*d + j]         = sum_i d1 k(x_a, z_i)/dx_aj alpha_i
+ *   cov[a*q + c'] = k(x_a, x_c) - k_a^T h_c                   dcov[(a*d + j)*q + c'] = d1 k(x_a, x_c)/dx_aj - sum_i d1 k(x_a, z_i)/dx_aj h_c[i]
+ * Shapes, the first-argument derivative d1 and the chain rule are gpx_moments_grad_f64's (W (I - S S^T) W^T is
+ * symmetric).  K* is projected first and contracted afterwards; S S^T <= I is not assumed.  The covariance is the latent
+ * one: no likelihood noise and no variance floor (gpx_svgp_predict_f64 adds the noise and clamps).  dmean and dcov may
+ * both be NULL: values only, with the same bits of mean and cov.  Limits: 1 <= q <= GPX_MAX_Q, m % q == 0,
+ * m <= GPX_MAX_GRAD_CANDIDATES.  Asynchronous on the handle's stream, deterministic, no allocation.
+ * Workspace (doubles from the 256-byte aligned start; mpad = m rounded up to 64, blk = Mpad * mpad):
+ *   [0, blk) K(Z, Xs), then H (K* is dead once V and U exist);  [blk, 2 blk) V = W^T K*;  [2 blk, 3 blk) U = W2^T K*;
+ *   from 3 blk on the fp64-MFMA products' split-K partials. */
+gpx_status gpx_svgp_moments_grad_workspace_size(int64_t M, int64_t m, size_t* bytes);
+gpx_status gpx_svgp_moments_grad_f64(gpx_handle h, const gpx_kernel_params* p /* one task */, int64_t M,
+                                     const double* Z, int64_t ldz, const double* W, const double* W2,
+                                     const double* alpha, const double* Xs, int64_t m, int64_t q, int64_t ldxs,
+                                     double* mean, double* dmean /* or NULL */, double* cov,
+                                     double* dcov /* or NULL, with dmean */, void* ws, size_t ws_bytes);
+
 /* ---- SVGP variational posterior in closed form (the collapsed bound of Titsias 2009) ------------------------------ */
 /* For given hyperparameters p[t] and inducing points Z, the optimum of the whitened variational distribution
  * q(u) = N(m, S) of Bayesian7.py's model (Gaussian likelihood) under the full-batch ELBO, per task t, all fp64:
