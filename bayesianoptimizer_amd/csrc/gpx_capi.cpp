@@ -1141,7 +1141,7 @@ static gpx_status acquire_impl(gpx_handle h, const gpx_kernel_params* p, int64_t
   // [3]: the tiles of the full sweep, with the full path's chunking
   c->sweep_stats[3] = fused ? 0 : m / b.chunk * tiles(b.chunk) + tiles(m % b.chunk);
   c->sweep_stats_dev = prune ? w.ps.stats : nullptr;
-  // spans of a chunk, or on the lazy path of a super-chunk (sweep_span_size: the call's first is one chunk long)
+  // spans of a chunk, or on the lazy path of a super-chunk (sweep_span_size)
   const gpx::SweepModel M{c, *p, (int)n, (int)npad, X, ldx, W, ldw, alpha, 1};
   int64_t rec = 0;
   for (int64_t s = 0, ms = 0; s < m; s += ms) {

@@ -318,8 +318,8 @@ struct MultiModel {  // one output of the objective
 hipError_t launch_topk_multi_chunk(Context* c, int T, const MultiModel* outs, int n, int npad, const double* X,
                                    int64_t ldx, const SweepCands& q, const SweepWorkspace& w, const gpx_acq_params& a,
                                    bool first, int64_t* host_stats);
-// One super-chunk of gpx_acquire_argmax_f64; first: the call's first (resets the incumbent and the counters, scores the
-// seed block in full).  *recs: the records written so far, advanced.  host_stats as above.
+// One super-chunk of gpx_acquire_argmax_f64; first: the call's first (resets the incumbent and the counters and makes the
+// first incumbent: the leading block in full, or in a call longer than one chunk the head bound's best of every slice).  *recs: the records written so far, advanced.  host_stats as above.
 hipError_t launch_sweep_super_pruned(const SweepModel& M, const SweepCands& q, const SweepBuffers& b,
                                      const PruneState& ps, const PruneHead& ph, const gpx_acq_params* a, int64_t* recs,
                                      bool first, int64_t* host_stats, const TopkSweep* tk = nullptr);

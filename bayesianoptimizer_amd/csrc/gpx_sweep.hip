@@ -20,7 +20,8 @@
 // mode 4 drops the candidates whose score bound cannot reach the best score computed in full so far, and
 // prune_compact_kernel gathers the surviving K* columns; the (value, index) pair has the bits of the full sweep.  Where
 // the MFMA K* build applies the pruned form is lazy (launch_sweep_super_pruned): K* rows 0 .. 127 for every candidate,
-// full-height columns rebuilt from the survivor list.  Both share launch_seed_block and launch_stages;
+// full-height columns rebuilt from the survivor list; a call longer than one chunk takes its first incumbent from the
+// head's bound (seed_select_kernel, seed_prune_kernel).  Both share launch_seed_block and launch_stages;
 // gpx_acquire_topk_f64 is the same sweep with the k-th best exact score as its incumbent (topk_pool_kernel), and
 // gpx_acquire_topk_multi_f64 (launch_topk_multi_chunk) its form for a linear objective over independent outputs: one
 // head tile per output, the variance bounds summed in the accumulators before one bound pass.
@@ -888,6 +889,9 @@ struct PruneSel {
   double* sc_val;
   int64_t* sc_idx;
   int* sc_count;
+  // mode 4 without an incumbent (the seeded order's bound pass): the bound of column c goes to u_out[c], nothing is
+  // selected; seed_select_kernel and seed_prune_kernel read it
+  double* u_out;
 };
 constexpr double PRUNE_EPS = 1e-9;  // margin of the bound test over acq_score's rounding
 
@@ -969,6 +973,10 @@ __global__ void __launch_bounds__(WG) finalize_kernel(FinalizeArgs fa, int mode,
     if (score != score && mode != 4) score = -INFINITY;
   }
   if (mode == 0 || mode == 2) return;
+  if (mode == 4 && ps.u_out) {
+    if (valid) ps.u_out[c] = score;
+    return;
+  }
   if (mode == 4) {
     // survivors as a compact list: one ballot and one atomic add per wave; the slot order may vary from run to run,
     // no result depends on it
@@ -1052,6 +1060,68 @@ __global__ void __launch_bounds__(WG) multi_bound_select_kernel(FinalizeArgs fa,
   if (lane == 0) base = atomicAdd(count, __popcll(mask));
   base = __shfl(base, 0);
   if (keep) survivors[base + __popcll(mask & ((1ull << lane) - 1))] = make_int2((int)c, t);
+}
+
+// ---- the seeded order of the lazy form (launch_sweep_super_pruned) ---------------------------------------
+// The span's m >= PRUNE_SEED columns in PRUNE_SEED contiguous slices: slice s is [s m / PRUNE_SEED, (s + 1) m /
+// PRUNE_SEED), rounded down.  None is empty and none longer than ceil(m / PRUNE_SEED), so one column per slice is
+// exactly PRUNE_SEED distinct columns in ascending order, whatever m.
+__device__ __forceinline__ int64_t seed_slice_begin(int64_t s, int64_t m) { return s * m / PRUNE_SEED; }
+__device__ __forceinline__ int seed_slice_of(int64_t c, int64_t m) { return (int)(((c + 1) * PRUNE_SEED - 1) / m); }
+
+// The seed of a span: per slice (one workgroup each) the column with the largest score bound U, the lowest such column
+// on ties; a NaN bound counts as -inf, so it wins only a slice without a larger one.  seed[s] = {column, s}; workgroup 0
+// also writes the list's length where the gather build reads it.  Plain reductions in a fixed order: deterministic.
+__global__ void __launch_bounds__(WG) seed_select_kernel(const double* __restrict__ U, int64_t m,
+                                                         int2* __restrict__ seed, int* __restrict__ count) {
+  const int s = blockIdx.x;
+  const int64_t c1 = seed_slice_begin(s + 1, m);
+  double bv = -INFINITY;
+  int64_t bi = INT64_MAX;
+  for (int64_t c = seed_slice_begin(s, m) + threadIdx.x; c < c1; c += WG) {
+    const double u = U[c];
+    argmax_merge(bv, bi, u != u ? -INFINITY : u, c);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double v2 = __shfl_xor(bv, o);
+    const int64_t i2 = __shfl_xor(bi, o);
+    argmax_merge(bv, bi, v2, i2);
+  }
+  __shared__ double wv[4];
+  __shared__ int64_t wi[4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lane == 0) {
+    wv[w] = bv;
+    wi[w] = bi;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int q = 1; q < 4; ++q) argmax_merge(bv, bi, wv[q], wi[q]);
+    seed[s] = make_int2((int)bi, s);
+    if (s == 0) *count = PRUNE_SEED;
+  }
+}
+
+// The seeded order's prune pass: mode 4's test of the stored bounds U against the incumbent the seed left (a NaN bound
+// survives), the seed's own columns left out (they are scored already); survivors {column, column} to the list as mode
+// 4 appends them: one ballot and one atomic add per wave, any slot order.
+__global__ void __launch_bounds__(WG) seed_prune_kernel(const double* __restrict__ U, int64_t m,
+                                                        const int2* __restrict__ seed,
+                                                        const unsigned long long* __restrict__ tau_key_in,
+                                                        int2* __restrict__ survivors, int* __restrict__ count) {
+  const int64_t c = (int64_t)blockIdx.x * WG + threadIdx.x;
+  const bool valid = c < m && seed[seed_slice_of(c, m)].x != (int)c;
+  const double score = valid ? U[c] : -INFINITY;
+  const double tau = tau_value(*tau_key_in);
+  const bool keep = valid && !(score + PRUNE_EPS * (fabs(score) + fabs(tau) + 1.0) < tau);
+  const unsigned long long mask = __ballot(keep);
+  if (mask == 0) return;
+  const int lane = threadIdx.x & 63;
+  int base = 0;
+  if (lane == 0) base = atomicAdd(count, __popcll(mask));
+  base = __shfl(base, 0);
+  if (keep) survivors[base + __popcll(mask & ((1ull << lane) - 1))] = make_int2((int)c, (int)c);
 }
 
 // The pruned sweep's per-chunk reset (one thread): the first stage's column set (the chunk's columns from col0 on, in
@@ -1662,11 +1732,20 @@ hipError_t launch_sweep_chunk_pruned(const SweepModel& M, const SweepCands& q, c
 
 // The lazy form of the pruned sweep, for the configurations of kstar_mfma_kernel: K* is built in full only
 // for the candidates that survive the first row tile.  Per super-chunk of ph.super candidates:
-//  seed   (first super-chunk of a call) the leading PRUNE_SEED candidates through the full path: the first incumbent.
 //  head   KSTAR_FULL over the head rows (K* rows 0 .. 127), then the mean of every candidate: for the RBF kernel its bound
 //         (gpx_mubound.hip; the bound pass scores its upper end), else or with sweep_prune = -2 KSTAR_MU over the other
 //         row blocks (every mean partial); the first stage of the product and its bound pass as one launch each; the
 //         survivors land in ph.survivors.
+//  seed   the call's first incumbent, in one of two orders.
+//         A call of one chunk or less: BEFORE the head, its leading PRUNE_SEED candidates through the full path
+//         (launch_seed_block); the head's bound pass selects against their best.
+//         A longer call (its first super-chunk): the leading block is a weak seed (on the bench problem its best logEI
+//         is -38.7, the optimum -0.66), and the head's bound ranks the candidates without any incumbent.  So the bound
+//         pass runs first and keeps every column's bound U (finalize mode 4 with u_out); seed_select_kernel takes the
+//         column of the largest U in each of PRUNE_SEED contiguous slices of the span (seed_slice_begin); those columns
+//         go through a round like the tail's (gather build, row tiles 1 .. nI - 1 in one stage, finalize mode 1:
+//         records, incumbent, for top-k the scored list and the pool); seed_prune_kernel then tests every other
+//         column's U against that incumbent.  No column is scored twice.  Later super-chunks have no seed.
 //  tail   rounds of at most C survivors: KSTAR_GATHER rebuilds their full-height columns into the chunk buffer (the bits
 //         of the full build) and, after a mean bound, their exact mean partials into ph.mu_part, then the staged pipeline
 //         of launch_sweep_chunk_pruned (launch_stages) from row tile 1 on, the partials
@@ -1687,12 +1766,14 @@ hipError_t launch_sweep_super_pruned(const SweepModel& M, const SweepCands& q, c
   const int S = prune_stage_bounds(nI, R);  // (nI >= 3: S >= 3, R[1] = 1 = the head's row tile)
   static_assert(PRUNE_HEAD_ROWS == TT, "the head phase is the product's first row tile");
   const FinalizeArgs fa = finalize_args(M.p, a, 1, nullptr, nullptr);
-  const SeedPlan sp = seed_plan(first, q.m, C);
+  // the seeded order: the call's first span when the call is longer than one chunk (a list of PRUNE_SEED fits a chunk's)
+  const bool seeded = first && q.m > C && C >= PRUNE_SEED;
+  const SeedPlan sp = seed_plan(first && !seeded, q.m, C);  // (seeded: no leading block, every column is staged)
   launch_seed_block(M, q, b, ps, fa, sp, R[1], false, first, true, ph.rec_val + *recs, ph.rec_idx + *recs, host_stats,
                     tk);
   *recs += sp.seed_blocks;
   if (sp.ncols == 0) return hipGetLastError();
-  // head: the columns of the whole super-chunk (the seed block's again: the head kernel has no column offset)
+  // head: the columns of the whole super-chunk (a leading seed block's again: the head kernel has no column offset)
   {
     SweepBuffers hb = b;
     hb.kstar = ph.head;
@@ -1712,6 +1793,13 @@ hipError_t launch_sweep_super_pruned(const SweepModel& M, const SweepCands& q, c
       launch_kstar(M, q, hb, KSTAR_MU, aux);
     }
   }
+  // The seeded order keeps every column's score bound U in the variance partials' row of tile 1: no stage writes it before
+  // the seed's and the survivors' own, each at its columns only and before any pass reads them there.  The seed list is
+  // the second index list: a round of one stage has no bound pass, so neither list is written before the prune pass.
+  static_assert(PRUNE_MIN_NPAD / TT >= 2 && 4 * (PRUNE_MAX_STAGES + 1) <= 256, "partial row 1; a slot behind the counts");
+  double* U = ph.ss_part + MA;
+  int2* seed = ps.list[1];
+  int* nseed = ps.count + PRUNE_MAX_STAGES;
   {
     LaunchTimer tm(c, GPX_TIMER_TRMM);
     const PruneStage st{prune_bufs(ph.head, MA, ps), ps.desc, 0, R[1], 0};
@@ -1722,9 +1810,38 @@ hipError_t launch_sweep_super_pruned(const SweepModel& M, const SweepCands& q, c
     sel.count = ps.count;
     sel.list0 = ph.survivors;  // (the descriptor's list is -1: the survivors go to list0)
     sel.mu_bound = mu_bound ? ph.mu_part + 2 * MA : nullptr;
+    sel.u_out = seeded ? U : nullptr;  // (seeded: no incumbent yet, the bounds are kept)
     finalize_kernel<<<(sp.ncols + WG - 1) / WG, WG, 0, c->stream>>>(fa, 4, q.Xs, q.ldxs, q.m, MA, 1, nJB, R[1],
                                                                     ph.mu_part, ph.ss_part, nullptr, 0, nullptr, nullptr,
                                                                     nullptr, nullptr, q.index_offset, sel);
+    if (seeded) seed_select_kernel<<<PRUNE_SEED, WG, 0, c->stream>>>(U, q.m, seed, nseed);
+  }
+  if (seeded) {
+    // seed: the best bound of each slice through the gather build and the rest of the product (tile 0's partial is the
+    // head's) as one round of one stage: exact scores, records, the incumbent (top-k: the scored list and the pool)
+    const int Rs[2] = {1, nI};
+    KstarAux aux{};
+    aux.list = reinterpret_cast<const int*>(seed);
+    aux.lstride = 2;
+    aux.count = nseed;
+    aux.first = 0;
+    aux.cap = PRUNE_SEED;
+    aux.desc = ps.desc + 1;
+    aux.rcount = ps.count + 1;
+    aux.stats = ps.stats;
+    aux.rows0 = nI - 1;
+    aux.last = 1;
+    aux.mu_out = mu_bound ? ph.mu_part : nullptr;
+    aux.ldmu = MA;
+    launch_kstar(M, q.first(PRUNE_SEED), b, KSTAR_GATHER, aux);
+    launch_stages(M, q, ps, fa,
+                  StagePlan{prune_bufs(b.kstar, C, ps, seed), ph.mu_part, ph.ss_part, MA, Rs, 1, 1, false, PRUNE_SEED,
+                            ph.rec_val + *recs, ph.rec_idx + *recs},
+                  C, tk);
+    *recs += PRUNE_SEED / WG;
+    // prune: every other column's bound against the seed's incumbent
+    LaunchTimer tm(c, GPX_TIMER_ACQ);
+    seed_prune_kernel<<<(sp.ncols + WG - 1) / WG, WG, 0, c->stream>>>(U, q.m, seed, ps.tau, ph.survivors, ps.count);
   }
   // tail (its passes read the survivors' exact partials, written by their gather)
   for (int64_t r0 = 0; r0 < sp.ncols; r0 += C) {

@@ -57,19 +57,20 @@ inline int64_t sweep_super_size(int64_t npad, int64_t m) {
   if (cap < C) cap = C;  // (never at the sizes the library accepts: a column of K* outweighs the per-candidate arrays)
   return sweep_blocks_of(m) < cap ? sweep_blocks_of(m) : cap;
 }
-// The candidates of the span a call's chunk loop starts at s: a chunk, or on the lazy pruned path a super-chunk.  The
-// lazy call's first span is one chunk long: everything after it is bounded against the best of a chunk's scores instead
-// of the seed block's alone (one super-chunk of 2^20 from the seed on: 23537 product tiles and 17.6 ms on the bench
-// problem instead of 9121 and 10.2, profiles/r08_variants_probe.jsonl).
+// The candidates of the span a call's chunk loop starts at s: a chunk, or on the lazy pruned path a super-chunk, the
+// call's first one included.  Where that one is longer than a chunk its incumbent comes from the head bound's best
+// column in each of PRUNE_SEED slices of the span (launch_sweep_super_pruned), not from the leading block, so a short
+// first span has nothing to add.  (With the leading block as the seed a first span of 2^20 cost 23537 product tiles on
+// the bench problem and a first span of one chunk 9121, profiles/r08_variants_probe.jsonl.)
 inline int64_t sweep_span_size(bool lazy, int64_t s, int64_t m, int64_t C, int64_t MA) {
-  const int64_t lim = (lazy && !(s == 0 && C < MA)) ? MA : C;
+  const int64_t lim = lazy ? MA : C;
   return (m - s) < lim ? (m - s) : lim;
 }
 // Records of the lazy pruned sweep: per super-chunk the seed block's and one 256-candidate block per 256 columns of every
 // tail round it can need.
 inline int64_t sweep_lazy_records(int64_t npad, int64_t m) {
   const int64_t C = sweep_chunk_size(npad, m), MA = sweep_super_size(npad, m);
-  const int64_t supers = (m + MA - 1) / MA + 1, rounds = (MA + C - 1) / C;  // (+ 1: the call's short first one)
+  const int64_t supers = (m + MA - 1) / MA + 1, rounds = (MA + C - 1) / C;  // (+ 1: room the spans no longer need since the first became a whole one; the reported sizes are pinned)
   return PRUNE_SEED / WG + supers * rounds * (C / WG);
 }
 // The compact K* buffers hold C/2 and C/4 columns, rounded up to the tile (a compaction at least halves the active

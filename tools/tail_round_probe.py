@@ -1,11 +1,11 @@
 """The columns the live tail rounds of the lazy pruned sweep handle, read from the stage descriptors and
 survivor counts a call leaves in its workspace (gpx_sweep_layout.h: SR_DESC, SR_COUNT behind the main part).
 
-A call's first span is one chunk long and has one tail round, so a call over the first chunk's candidates alone leaves
-that round's descriptors (slot 1: the gather's set, then one per compaction: buf, col0, ncols, ntiles, list) and the
-survivors after every stage (count[0]: the head's).  After the whole call the later rounds have overwritten them, but
-count[0] is still the last span's head survivors, and sweep_stats[1] - 1024 - the first round's last set is what the
-last span computed to the end.  One JSON line per case.  The library is the tree's, or GPX_LIB's.
+A call over one chunk's candidates has one tail round (and the leading block as its seed), so it leaves that round's
+descriptors (slot 1: the gather's set, then one per compaction: buf, col0, ncols, ntiles, list) and the survivors after
+every stage (count[0]: the head's).  After the whole call (one span of 2^20, seeded from the head's bound) the later
+rounds have overwritten them, but count[0] is still the survivors of the last span's prune pass, the seed's columns
+left out, and sweep_stats[1] - 1024 is what the tail computed to the end.  One JSON line per case.  The library is the tree's, or GPX_LIB's.
 """
 import argparse
 import json
