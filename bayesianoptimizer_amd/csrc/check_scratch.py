@@ -12,6 +12,8 @@ import sys
 ASM_TILE_KERNELS = ("trmm_sumsq_kernel", "trmm_stage_kernel", "trmm_stage_dual_kernel", "potrf_step_kernel",
                     "mll_grad_kernel", "svgp_w2_kernel", "trtri_t_kernel", "trtri_w_kernel", "svgp_project_kernel",
                     "svgp_syrk_kernel", "svgp_mm_kernel", "svgp_grad_kernel")
+# No asm loads, but 128 accumulator registers per lane at two waves per SIMD: a spill would sit in the k loop.
+NO_SPILL_KERNELS = ("head_product_kernel",)
 
 
 def main(path: str) -> int:
@@ -19,7 +21,7 @@ def main(path: str) -> int:
     for line in text.splitlines():
         if "warning:" in line or "error:" in line:
             print(line)
-    bad = []
+    bad, spilled = [], []
     name = None
     for line in text.splitlines():
         m = re.search(r"Function Name: (\S+)", line)
@@ -30,9 +32,13 @@ def main(path: str) -> int:
         if m and name is not None and int(m.group(1)) > 0:
             if any(k in name for k in ASM_TILE_KERNELS):
                 bad.append((name, int(m.group(1))))
+            elif any(k in name for k in NO_SPILL_KERNELS):
+                spilled.append((name, int(m.group(1))))
     for name, size in bad:
         print(f"{path}: {name} uses {size} bytes/lane of scratch; the hand-placed asm k loop requires none")
-    return 1 if bad else 0
+    for name, size in spilled:
+        print(f"{path}: {name} uses {size} bytes/lane of scratch; it is built to hold its accumulators without any")
+    return 1 if bad or spilled else 0
 
 
 if __name__ == "__main__":

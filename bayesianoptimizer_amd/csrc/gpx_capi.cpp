@@ -1256,6 +1256,39 @@ gpx_status gpx_debug_kstar_mu_f64(gpx_handle h, const gpx_kernel_params* p, int6
                    "debug_kstar_mu");
 }
 
+gpx_status gpx_debug_set_sweep_head(gpx_handle h, int32_t value) {
+  Context* c = reinterpret_cast<Context*>(h);
+  if (!c) return GPX_INVALID_ARG;
+  if (value != 0 && value != 1) return fail(c, GPX_INVALID_ARG, "sweep_head must be 0 or 1");
+  c->sweep_head = value;
+  return GPX_OK;
+}
+
+gpx_status gpx_debug_get_sweep_head(gpx_handle h, int32_t* value_host) {
+  Context* c = reinterpret_cast<Context*>(h);
+  if (!c) return GPX_INVALID_ARG;
+  GPX_NONNULL(c, value_host);
+  *value_host = c->sweep_head;
+  return GPX_OK;
+}
+
+gpx_status gpx_debug_head_product_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X, int64_t ldx,
+                                      const double* alpha, const double* Xs, int64_t m, int64_t ldxs, const double* W,
+                                      int64_t ldw, double* ss, double* mu_part, int64_t ldmu) {
+  Context* c = reinterpret_cast<Context*>(h);
+  if (!c) return GPX_INVALID_ARG;
+  GPX_TRY(check_sweep_sizes(c, p, n, m, kDebugMaxM));
+  GPX_TRY(check_sweep_arrays(c, {{X, "X"}, {alpha, "alpha"}, {Xs, "Xs"}, {W, "W"}, {ss, "ss"}, {mu_part, "mu_part"}}, p,
+                             ldx, ldxs));
+  const int64_t npad = padded(n);
+  if (ldw < npad) return fail(c, GPX_INVALID_ARG, "ldw must be >= padded n");
+  if (ldmu < (m + 255) / 256 * 256) return fail(c, GPX_INVALID_ARG, "ldmu must be >= m rounded up to 256");
+  if (!gpx::sweep_lazy_ok(*p)) return fail(c, GPX_INVALID_ARG, "the fused head covers the fp64 covariance with d <= 16");
+  GPX_USE_DEVICE(c);
+  const gpx::SweepModel M{c, *p, (int)n, (int)npad, X, ldx, W, ldw, alpha, 1};
+  return hip_check(c, gpx::launch_debug_head_product(M, {Xs, ldxs, m, 0}, ss, mu_part, ldmu), "debug_head_product");
+}
+
 gpx_status gpx_debug_stage_product_workspace_size(int64_t ncols, size_t* bytes) {
   if (!bytes || ncols < 1 || ncols > ((int64_t)1 << 20)) return GPX_INVALID_ARG;
   *bytes = gpx::debug_stage_product_bytes(ncols) + 256;

@@ -59,6 +59,8 @@ struct Context {
   int potrf_split = -1;    // panel split policy (gpx_potrf.hip step_plan): -1 fits the slots, 1 never, 3 one per CU
   int sweep_prune = 1;     // pruned acquisition sweep: 1 where it pays, 0 never, 2 at every padded n >= 384, -2 as 2
                            // with the lazy head's exact means instead of their bound
+  int sweep_head = 1;      // (gpx_debug_set_sweep_head, no option slot) lazy pruned sweep's head: 1 K* rows 0 .. 127 and row tile 0 of the product in one kernel,
+                           // 0 the K* launch and the first stage apart
   // gpx_sweep_stats of the last acquire call: the host-known parts, plus the device counters of the pruned path
   // ({candidates computed to the last row tile, product tiles executed}; they live in that call's workspace)
   int64_t sweep_stats[4] = {0, 0, 0, 0};
@@ -336,6 +338,9 @@ size_t debug_stage_product_bytes(int64_t ncols);
 hipError_t launch_debug_stage_product(Context* c, int npad, const double* W, int64_t ldw, const double* kstar,
                                       int64_t ldk, int ncols, const int* list, int I0, int nrows, int shape, double* ss,
                                       int64_t ldss, void* ws);
+// The lazy pruned sweep's fused head through the production kernel (gpx_debug_head_product_f64): ss[c] = row tile 0's
+// variance partial and mu_part[jb * ld + c], jb = 0, 1, for every column up to q.m rounded up to 256 (ld at least that).
+hipError_t launch_debug_head_product(const SweepModel& M, const SweepCands& q, double* ss, double* mu_part, int64_t ld);
 // The lazy pruned sweep's bound of the posterior mean (gpx_mubound.hip; RBF, fp64 covariance, d <= 16):
 // mu_approx[c] +- mu_slack[c] holds the exact path's mean of candidate c.  prep: mu_prep_doubles(npad, d) doubles,
 // 256-byte aligned; its first int64 ends up as the count of 256-candidate workgroups on the unfactorised path.

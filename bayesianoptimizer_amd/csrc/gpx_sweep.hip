@@ -20,8 +20,9 @@
 // mode 4 drops the candidates whose score bound cannot reach the best score computed in full so far, and
 // prune_compact_kernel gathers the surviving K* columns; the (value, index) pair has the bits of the full sweep.  Where
 // the MFMA K* build applies the pruned form is lazy (launch_sweep_super_pruned): K* rows 0 .. 127 for every candidate,
-// full-height columns rebuilt from the survivor list; a call longer than one chunk takes its first incumbent from the
-// head's bound (seed_select_kernel, seed_prune_kernel).  Both share launch_seed_block and launch_stages;
+// built in registers and multiplied into row tile 0 by one kernel (head_product_kernel; gpx_debug_set_sweep_head 0:
+// stored by a K* launch and read back by the first stage), full-height columns rebuilt from the survivor list; a call
+// longer than one chunk takes its first incumbent from the head's bound (seed_select_kernel, seed_prune_kernel).  Both share launch_seed_block and launch_stages;
 // gpx_acquire_topk_f64 is the same sweep with the k-th best exact score as its incumbent (topk_pool_kernel), and
 // gpx_acquire_topk_multi_f64 (launch_topk_multi_chunk) its form for a linear objective over independent outputs: one
 // head tile per output, the variance bounds summed in the accumulators before one bound pass.
@@ -710,6 +711,180 @@ trmm_stage_narrow_kernel(const double* __restrict__ W, int64_t ldw, int64_t C, i
                          PruneStage st) {
   __shared__ double red[TNW];
   trmm_sumsq_body<true, TRMM_NARROW>(W, ldw, nullptr, C, nI, 0, ss_part, 0, nullptr, nullptr, st, red);
+}
+
+// ---- the head of the lazy pruned sweep: K* rows 0 .. 127 and row tile 0 of the product in one kernel -----------------
+// The head needs, of every candidate, the mean partials of row blocks 0 and 1 and |W11^T k*[0..127]|^2; K* itself is
+// read by nothing else (the gathers rebuild their columns at full height).  So the K* entries never leave the registers:
+// a wave owns 32 candidates (two 16-column blocks) and all eight 16-row blocks of the tile, walks the two row blocks
+// jb = 0, 1 of K* with kstar_mfma_unit's arithmetic (the block's own centre, the cross term on the MFMA,
+// sqdist_expanded, cov_from_r2, zero for rows >= n, the mean partials' fma order and lane reduction), and after
+// cov_from_r2 its kv[r][cb] of lane (kq, m) = K*[k0 + kq][16 cb + m], k0 = 64 jb + rs + 4 r, is the B fragment of
+// v_mfma_f64_16x16x4 for that k-step as it stands: acc[ib][cb] += W[k0 + kq][16 ib + m] * kv[r][cb] for the row blocks
+// ib >= k0 / 16 and only those (run_tri's rule: row block ib is skipped for every k-tile J > ib, the diagonal 16 x 16
+// block runs in full).  Every accumulator block's chain is k ascending in steps of 4 from zero, the chain of the wide
+// and the narrow tile, so the bits are theirs, NaN and infinite candidates included.  The column sums of squares
+// reproduce trmm_colsum_store<128>: rows 0-63 and 64-127 apart (the tile's two wave rows), each i outer, r inner over
+// the lane's rows, + xor-16, + xor-32, then low + high.
+// The A fragments come from L2 (W11's 36 nonzero blocks are 72 KB, read alike by every workgroup), one k-tile's at a
+// time and before the tile's covariance arithmetic, which covers their latency.  The workgroups are persistent: they
+// stride over the groups of 128 candidates, and the training rows' part of the setup (scaled rows, centres, norms,
+// alpha, for both row blocks) is done once per workgroup.  One instruction stream: the k-tile loop is not unrolled, the
+// row-block skip is a uniform branch on its counter.
+// ss goes to ss_part[c] (row tile 0) for the staged columns c0s <= c < c1s only, mu_part blocks 0 and 1 for every
+// column of the grid's groups, as the two launches this replaces wrote them.
+constexpr int HP_COLS = 128;  // candidates per workgroup trip
+template <int DMAX, int KIND>
+__global__ void __launch_bounds__(WG, 2)
+head_product_kernel(gpx_kernel_params p, int n, const double* __restrict__ X, int64_t ldx,
+                    const double* __restrict__ alpha, const double* __restrict__ Xs, int64_t ldxs, int64_t m_chunk,
+                    int64_t C, const double* __restrict__ W, int64_t ldw, int ngroups, int64_t c0s, int64_t c1s,
+                    double* __restrict__ mu_part, double* __restrict__ ss_part) {
+  constexpr bool lin = (KIND == GPX_KERNEL_SCALE_LINEAR_MATERN52);
+  constexpr int KS = DMAX / 4;
+  constexpr int NJB = PRUNE_HEAD_ROWS / NB;
+  static_assert(NJB == 2 && PRUNE_HEAD_ROWS == TT, "two row blocks, one row tile");
+  __shared__ double sa[NJB][NB][DMAX + 1], ra[lin ? NJB : 1][lin ? NB : 1][DMAX + 1];
+  __shared__ double sb[HP_COLS][DMAX + 1], rb[lin ? HP_COLS : 1][DMAX + 1];
+  __shared__ double na[NJB][NB], sal[NJB][NB], nb[HP_COLS], cen[NJB][DMAX];
+  const int t = threadIdx.x, d = p.d;
+  // the training rows' side, once per workgroup
+  for (int e = t; e < NJB * NB * DMAX; e += WG) {
+    const int r = e / DMAX, k = e % DMAX;  // r: row 0 .. 127
+    const double v = (k < d && r < n) ? X[(int64_t)r * ldx + k] : 0.0;
+    sa[r / NB][r % NB][k] = (k < d) ? v / p.lengthscale[k] : 0.0;
+    if constexpr (lin) ra[r / NB][r % NB][k] = (k < d) ? v * p.linear_variance[k] : 0.0;
+  }
+  if (t < NJB * NB) sal[t / NB][t % NB] = t < n ? alpha[t] : 0.0;
+  __syncthreads();
+  if (t < NJB * DMAX) {
+    const int jb = t / DMAX, k = t % DMAX;
+    const int nv = n - jb * NB < NB ? n - jb * NB : NB;
+    double s = 0.0;
+    for (int r = 0; r < nv; ++r) s += sa[jb][r][k];
+    cen[jb][k] = nv > 0 ? s / nv : 0.0;
+  }
+  __syncthreads();
+  for (int e = t; e < NJB * NB * DMAX; e += WG) {
+    const int r = e / DMAX, k = e % DMAX;
+    sa[r / NB][r % NB][k] -= cen[r / NB][k];
+  }
+  __syncthreads();
+  if (t < NJB * NB) {
+    double u = 0.0;
+#pragma unroll
+    for (int k = 0; k < DMAX; ++k) u = fma(sa[t / NB][t % NB][k], sa[t / NB][t % NB][k], u);
+    na[t / NB][t % NB] = u;
+  }
+#pragma unroll 1
+  for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
+    const int64_t c0 = (int64_t)g * HP_COLS;
+    d4 acc[8][2];
+#pragma unroll
+    for (int ib = 0; ib < 8; ++ib)
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb) acc[ib][cb] = (d4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll 1
+    for (int jb = 0; jb < NJB; ++jb) {
+      const int nv = n - jb * NB < NB ? n - jb * NB : NB;  // valid training rows of the block (<= 0: all padding)
+      // (an opaque thread index per trip keeps the compiler from hoisting every address that depends on it out of the
+      // loops, which spilled them: the accumulators leave no room for loop invariants)
+      int t = threadIdx.x;
+      asm volatile("" : "+v"(t));
+      int lane = t & 63;
+      const int w = t >> 6;
+      __syncthreads();  // the row block before this one has read sb / nb to the end (and na is written)
+      for (int e = t; e < HP_COLS * DMAX; e += WG) {
+        const int r = e / DMAX, k = e % DMAX;
+        const double v = (k < d && c0 + r < m_chunk) ? Xs[(c0 + r) * ldxs + k] : 0.0;
+        const double s = (k < d) ? v / p.lengthscale[k] : 0.0;
+        sb[r][k] = s - cen[jb][k];
+        if constexpr (lin) rb[r][k] = v;
+      }
+      __syncthreads();
+      if (t < HP_COLS) {
+        double v = 0.0;
+#pragma unroll
+        for (int k = 0; k < DMAX; ++k) v = fma(sb[t][k], sb[t][k], v);
+        nb[t] = v;
+      }
+      __syncthreads();
+      double mu[2] = {0.0, 0.0}, nbc[2];
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb) nbc[cb] = nb[32 * w + 16 * cb + (lane & 15)];
+#pragma unroll 1
+      for (int rs = 0; rs < NB; rs += 16) {
+        const int J = (jb * NB + rs) / 16;  // the k-tile: row blocks ib < J of W are zero in it
+        asm volatile("" : "+v"(lane));       // (per k-tile too: the scaled-linear kind's four LDS images)
+        const int m = lane & 15, kq = lane >> 4;
+        // the tile's A fragments W[16 J + 4 r + kq][16 ib + m], one k-step's at a time and one k-step ahead: the first
+        // before the covariance arithmetic, which covers its latency, the others behind the MFMAs of the step before
+        double a[2][8];
+        const double* Wj = W + (int64_t)(16 * J + kq) * ldw + m;  // W[16 J + kq][m]
+        auto load_a = [&](double(&f)[8], int r) {
+#pragma unroll
+          for (int ib = 0; ib < 8; ++ib) f[ib] = ib >= J ? Wj[(int64_t)(4 * r) * ldw + 16 * ib] : 0.0;
+        };
+        load_a(a[0], 0);
+        double kv[4][2];  // [r][cb]: row rs + kq + 4 r of the block, candidate 32 w + 16 cb + m
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) {
+          d4 dot = {0.0, 0.0, 0.0, 0.0}, lac = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+          for (int k = 0; k < KS; ++k) {
+            dot = mfma16x16x4(sa[jb][rs + m][4 * k + kq], sb[32 * w + 16 * cb + m][4 * k + kq], dot);
+            if constexpr (lin)
+              lac = mfma16x16x4(ra[jb][rs + m][4 * k + kq], rb[32 * w + 16 * cb + m][4 * k + kq], lac);
+          }
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int j = rs + kq + 4 * r;
+            double v =
+                cov_from_r2(KIND, p.outputscale, sqdist_expanded(na[jb][j], nbc[cb], dot[r]), lin ? lac[r] : 0.0);
+            v = j < nv ? v : 0.0;
+            kv[r][cb] = v;
+            mu[cb] = fma(sal[jb][j], v, mu[cb]);
+          }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          if (r < 3) load_a(a[(r + 1) & 1], r + 1);
+#pragma unroll
+          for (int ib = 0; ib < 8; ++ib)
+            if (ib >= J) {
+#pragma unroll
+              for (int cb = 0; cb < 2; ++cb) acc[ib][cb] = mfma16x16x4(a[r & 1][ib], kv[r][cb], acc[ib][cb]);
+            }
+        }
+      }
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb) {
+        double v = mu[cb];
+        v += __shfl_xor(v, 16);
+        v += __shfl_xor(v, 32);
+        if (lane < 16) mu_part[(int64_t)jb * C + c0 + 32 * w + 16 * cb + lane] = v;
+      }
+    }
+    // trmm_colsum_store<128>'s sums: the tile's two wave rows apart, then low + high
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, m = lane & 15, kq = lane >> 4;
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb) {
+      double s[2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        double v = 0.0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v += acc[4 * h + i][cb][r] * acc[4 * h + i][cb][r];
+        v += __shfl_xor(v, 16);
+        v += __shfl_xor(v, 32);
+        s[h] = v;
+      }
+      const int64_t c = c0 + 32 * w + 16 * cb + m;
+      if (kq == 0 && c >= c0s && c < c1s) ss_part[c] = s[0] + s[1];
+    }
+  }
 }
 
 // ---- 1+2 fused, small n (npad <= 256) ----------------------------------------------------------
@@ -1484,6 +1659,31 @@ static void launch_kstar(const SweepModel& M, const SweepCands& q, const SweepBu
   });
 }
 
+// The fused head of the lazy form (head_product_kernel): mean partials of row blocks 0 and 1 for the columns the head's
+// K* launch covers (whole 256-column blocks of q.m), row tile 0's variance partial for the staged columns' tiles (from
+// col0 on, ncols of them), both at pitch C.  The grid is what the device holds at once; the workgroups stride.
+static void launch_head_product(const SweepModel& M, const SweepCands& q, int64_t C, double* mu_part, double* ss_part,
+                                int col0, int64_t ncols) {
+  const gpx_kernel_params& p = M.p;
+  const int ngroups = (int)((q.m + WG - 1) / WG) * (WG / HP_COLS);
+  const int64_t c1s = col0 + (ncols + TT - 1) / TT * TT;
+  with_dmax(p.d, [&](auto D) {
+    constexpr int DM = decltype(D)::value;
+    if constexpr (DM <= 16) {  // (sweep_lazy_ok: d <= 16)
+      with_kind(p.kind, [&](auto K) {
+        auto kernel = head_product_kernel<DM, decltype(K)::value>;
+        static const int resident = [&] {  // workgroups of this instance a CU holds; 0: unknown
+          int r = 0;
+          return hipOccupancyMaxActiveBlocksPerMultiprocessor(&r, kernel, WG, 0) == hipSuccess ? r : 0;
+        }();
+        kernel<<<tail_grid(M.c, resident, ngroups), WG, 0, M.c->stream>>>(p, M.n, M.X, M.ldx, M.alpha, q.Xs, q.ldxs, q.m,
+                                                                         C, M.W, M.ldw, ngroups, col0, c1s, mu_part,
+                                                                         ss_part);
+      });
+    }
+  });
+}
+
 // finalize_kernel's arguments of a posterior (a = nullptr: per-output y_mean / y_scale, nullptr = identity) or of an
 // acquisition (a's y_mean / y_scale for the one output)
 static FinalizeArgs finalize_args(const gpx_kernel_params& p, const gpx_acq_params* a, int nrhs, const double* y_mean,
@@ -1735,7 +1935,9 @@ hipError_t launch_sweep_chunk_pruned(const SweepModel& M, const SweepCands& q, c
 //  head   KSTAR_FULL over the head rows (K* rows 0 .. 127), then the mean of every candidate: for the RBF kernel its bound
 //         (gpx_mubound.hip; the bound pass scores its upper end), else or with sweep_prune = -2 KSTAR_MU over the other
 //         row blocks (every mean partial); the first stage of the product and its bound pass as one launch each; the
-//         survivors land in ph.survivors.
+//         survivors land in ph.survivors.  With sweep_head (the default) the KSTAR_FULL launch and the first stage are
+//         one launch of head_product_kernel in the first stage's place: the same mean partials of row blocks 0 and 1
+//         and the same partial of row tile 0, K* rows 0 .. 127 never stored (ph.head stays unused).
 //  seed   the call's first incumbent, in one of two orders.
 //         A call of one chunk or less: BEFORE the head, its leading PRUNE_SEED candidates through the full path
 //         (launch_seed_block); the head's bound pass selects against their best.
@@ -1779,7 +1981,8 @@ hipError_t launch_sweep_super_pruned(const SweepModel& M, const SweepCands& q, c
     hb.kstar = ph.head;
     hb.mu_part = ph.mu_part;
     hb.chunk = MA;
-    launch_kstar(M, q, hb, KSTAR_FULL, KstarAux{}, PRUNE_HEAD_ROWS);
+    // (sweep_head: head_product_kernel below builds these rows in registers, in the first stage's place)
+    if (!c->sweep_head) launch_kstar(M, q, hb, KSTAR_FULL, KstarAux{}, PRUNE_HEAD_ROWS);
     if (mu_bound) {
       // the mean's bound instead of the mean.  Its two values per candidate go to the mean partials' rows of blocks 2
       // and 3 (the head rows' launch wrote blocks 0 and 1; nothing writes the others before the gather), the row
@@ -1802,8 +2005,12 @@ hipError_t launch_sweep_super_pruned(const SweepModel& M, const SweepCands& q, c
   int* nseed = ps.count + PRUNE_MAX_STAGES;
   {
     LaunchTimer tm(c, GPX_TIMER_TRMM);
-    const PruneStage st{prune_bufs(ph.head, MA, ps), ps.desc, 0, R[1], 0};
-    trmm_stage_kernel<<<(sp.ncols + TT - 1) / TT * st.nrows, WG, 0, c->stream>>>(M.W, M.ldw, MA, nI, ph.ss_part, st);
+    if (c->sweep_head) {
+      launch_head_product(M, q, MA, ph.mu_part, ph.ss_part, sp.col0, sp.ncols);
+    } else {
+      const PruneStage st{prune_bufs(ph.head, MA, ps), ps.desc, 0, R[1], 0};
+      trmm_stage_kernel<<<(sp.ncols + TT - 1) / TT * st.nrows, WG, 0, c->stream>>>(M.W, M.ldw, MA, nI, ph.ss_part, st);
+    }
     PruneSel sel{};
     sel.tau = ps.tau;
     sel.desc = ps.desc;
@@ -2031,6 +2238,11 @@ hipError_t launch_debug_stage_product(Context* c, int npad, const double* W, int
     trmm_stage_kernel<<<ntiles * nrows, WG, 0, c->stream>>>(W, ldw, ldss, nI, ss, st);
   else
     trmm_stage_narrow_kernel<<<4 * ntiles * nrows, WG, 0, c->stream>>>(W, ldw, ldss, nI, ss, st);
+  return hipGetLastError();
+}
+
+hipError_t launch_debug_head_product(const SweepModel& M, const SweepCands& q, double* ss, double* mu_part, int64_t ld) {
+  launch_head_product(M, q, ld, mu_part, ss, 0, (q.m + WG - 1) / WG * WG);
   return hipGetLastError();
 }
 

@@ -747,6 +747,23 @@ gpx_status gpx_debug_mu_bound_workspace_size(int64_t n, size_t* bytes);
 gpx_status gpx_debug_mu_bound_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X, int64_t ldx,
                                   const double* alpha, const double* Xs, int64_t m, int64_t ldxs, double* mu_approx,
                                   double* mu_slack, void* ws, size_t ws_bytes);
+/* Which head the lazy pruned sweep of this handle runs (fp64 covariance, d <= 16; A/B measurements and tests, not a
+ * tuning option: it has no slot among GPX_OPT_* and no GPX_OPTIONS name).  1 (default): K* rows 0 .. 127 are built in
+ * registers and multiplied into row tile 0 of the product by one kernel.  0: a K* launch that stores them and the
+ * product's first stage that reads them back.  The same bits and the same gpx_sweep_stats either way.  Any other value
+ * is GPX_INVALID_ARG. */
+gpx_status gpx_debug_set_sweep_head(gpx_handle h, int32_t value);
+gpx_status gpx_debug_get_sweep_head(gpx_handle h, int32_t* value_host);
+/* The lazy pruned sweep's fused head through the production kernel, for bit checks (fp64 covariance, d <= 16; DESIGN
+ * §3): of every candidate c < m rounded up to 256 (candidates >= m are the origin), from training rows 0 .. 127 alone,
+ * ss[c] = the sum over rows 0 .. 127 of V[.][c]^2, V = W^T K*, and mu_part[jb * ldmu + c], jb = 0, 1, the mean partials
+ * of row blocks 0 and 1.  W: device, upper triangular, at least 128 x 128 of pitch ldw >= padded_n (its leading 128 x
+ * 128 block is read); ss: ldmu values; mu_part: 2 rows of pitch ldmu >= m rounded up to 256.  The bits are those of
+ * gpx_debug_kstar_mu_f64's full build followed by gpx_debug_stage_product_f64 of row tile 0.  Any n >= 1.
+ * Asynchronous on the handle's stream, no allocation, no workspace. */
+gpx_status gpx_debug_head_product_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X, int64_t ldx,
+                                      const double* alpha, const double* Xs, int64_t m, int64_t ldxs, const double* W,
+                                      int64_t ldw, double* ss, double* mu_part, int64_t ldmu);
 /* One stage of the pruned sweep's product in a named tile shape, for bit checks (no production path uses it; DESIGN
  * §3): row tiles I0 .. I0 + nrows - 1 of V = W^T K* over slots 0 .. ncols - 1 of a caller's K* buffer.  W: device,
  * padded_n x padded_n upper triangular (pitch ldw), kstar: device, padded_n rows of pitch ldk >= ncols rounded up to
