@@ -68,6 +68,9 @@ hipError_t launch_append(Context* c, const gpx_kernel_params& p, int n_old, int 
     if (e != hipSuccess) return e;
     e = launch_gemm64<false, true, KR_A_UPPER>(c, n0, q, n0, W, ldw, T, q, nullptr, 0, W + n0, ldw, -1.0, 0, P);
     if (e != hipSuccess) return e;
+    // W21 = 0: the new rows of W left of the refactored block (all of W is defined, include/gpx.h)
+    e = hipMemset2DAsync(W + (int64_t)n0 * ldw, (size_t)ldw * sizeof(double), 0, (size_t)n0 * sizeof(double), q, c->stream);
+    if (e != hipSuccess) return e;
   }
   return hipGetLastError();
 }

@@ -4,6 +4,7 @@
 //
 // TRTRI by recursive doubling over the 64x64 diagonal inverses D_k produced by potrf:
 //   level 0: W_kk = D_k^T, and the 64x64 block below the diagonal inside every 128-tile is zeroed;
+//            the other blocks below the diagonal are zeroed by the level that writes their transposed position;
 //   level l: for groups of 2h blocks (h = 2^(l-1)), with first half (off1, b1) and second half (off2, b2):
 //       T   = L21^T W22          (b1 x b2; W22 upper: k <= c)
 //       W12 = -W11 T             (b1 x b2; W11 upper: k >= r)
@@ -180,12 +181,19 @@ __global__ void __launch_bounds__(WG) trtri_w_kernel(double* __restrict__ W, int
         for (int j = 0; j < Tile::WN; ++j) acc[i][j] = tile.acc[i][j];
     }
     double* Wo = W + (off1 + rb * TS) * ldw + off2 + cb * TS;
+    // All of W is defined (include/gpx.h: the strict lower part is zero), and nothing else writes the tiles below the
+    // diagonal 128-tiles: the workgroup of a W12 tile also writes the zeros of the tile at its transposed position.
+    // Every block pair is split between the halves of a group at exactly one level, so each such tile is written once.
+    double* Wz = W + (off2 + cb * TS) * ldw + off1 + rb * TS;
 #pragma unroll
     for (int i = 0; i < Tile::WM; ++i)
 #pragma unroll
       for (int j = 0; j < Tile::WN; ++j)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) Wo[(int64_t)Tile::row_of(i, r) * ldw + Tile::col_of(j)] = -acc[i][j][r];
+        for (int r = 0; r < 4; ++r) {
+          Wo[(int64_t)Tile::row_of(i, r) * ldw + Tile::col_of(j)] = -acc[i][j][r];
+          Wz[(int64_t)Tile::row_of(i, r) * ldw + Tile::col_of(j)] = 0.0;
+        }
   };
   if constexpr (PAIRED) {
     const int cb = blockIdx.x, y = blockIdx.y;

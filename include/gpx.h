@@ -9,12 +9,15 @@
  * Conventions
  *  - Every array pointer is a DEVICE pointer owned by the caller (PyTorch tensors serve as containers).
  *    Host pointers are only the parameter structs and the out-scalars named *_host.
- *  - All matrices are row-major fp64 with an explicit leading dimension (in elements).
+ *  - All matrices are row-major fp64 with an explicit leading dimension (in elements).  The leading dimensions of the
+ *    matrix arguments (K, L, W, Sb) must be even and at most GPX_MAX_LD.  Bytes of an output outside its defined
+ *    region (pitch gaps, rows past the padded size, gaps between the problems of a batch) are never written.
  *  - Training size n is padded internally to gpx_padded_n(n) (a multiple of GPX_TILE); padded rows of K are
  *    the identity, so L, L^{-1} and alpha are exact block extensions of the unpadded ones.  Buffers named
  *    "padded" must have gpx_padded_n(n) rows/cols.
  *  - Calls are asynchronous on the handle's stream (gpx_set_stream) and never allocate device memory;
- *    scratch comes from the caller's workspace (size from the *_workspace_size queries).
+ *    scratch comes from the caller's workspace (size from the *_workspace_size queries).  A workspace's contents on
+ *    entry are arbitrary, and its address needs only 8-byte alignment.
  *  - Errors: return a gpx_status; gpx_last_error(h) gives a message.  NOT_PD is reported through a device
  *    int32 `info` (0 = OK, > 0 failing pivot + 1, LAPACK potrf convention) so the fit stays asynchronous;
  *    gpx_fit_f64_sync reads it back and returns GPX_NOT_PD, like the reference's jitter-retry path
