@@ -283,6 +283,10 @@ _PROTOS = {
     "gpx_debug_get_sweep_head": (c_int32, [_h, POINTER(c_int32)]),
     "gpx_debug_head_product_f64": (c_int32, [_h, POINTER(KernelParamsC), c_int64, _p, c_int64, _p, _p, c_int64, c_int64,
                                              _p, c_int64, _p, _p, c_int64]),
+    "gpx_debug_head_product_list_f64": (c_int32, [_h, POINTER(KernelParamsC), c_int64, _p, c_int64, _p, _p, c_int64,
+                                                  c_int64, _p, c_int64, _p, _p, c_int64, _p, _p]),
+    "gpx_debug_set_sweep_order": (c_int32, [_h, c_int32]),
+    "gpx_debug_get_sweep_order": (c_int32, [_h, POINTER(c_int32)]),
     "gpx_debug_stage_product_workspace_size": (c_int32, [c_int64, POINTER(c_size_t)]),
     "gpx_debug_stage_product_f64": (c_int32, [_h, c_int64, _p, c_int64, _p, c_int64, c_int64, _p, c_int32, c_int32,
                                               c_int32, _p, c_int64, _p, c_size_t]),

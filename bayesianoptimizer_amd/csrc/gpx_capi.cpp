@@ -1272,9 +1272,26 @@ gpx_status gpx_debug_get_sweep_head(gpx_handle h, int32_t* value_host) {
   return GPX_OK;
 }
 
-gpx_status gpx_debug_head_product_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X, int64_t ldx,
-                                      const double* alpha, const double* Xs, int64_t m, int64_t ldxs, const double* W,
-                                      int64_t ldw, double* ss, double* mu_part, int64_t ldmu) {
+gpx_status gpx_debug_set_sweep_order(gpx_handle h, int32_t value) {
+  Context* c = reinterpret_cast<Context*>(h);
+  if (!c) return GPX_INVALID_ARG;
+  if (value != 0 && value != 1) return fail(c, GPX_INVALID_ARG, "sweep_order must be 0 or 1");
+  c->sweep_order = value;
+  return GPX_OK;
+}
+
+gpx_status gpx_debug_get_sweep_order(gpx_handle h, int32_t* value_host) {
+  Context* c = reinterpret_cast<Context*>(h);
+  if (!c) return GPX_INVALID_ARG;
+  GPX_NONNULL(c, value_host);
+  *value_host = c->sweep_order;
+  return GPX_OK;
+}
+
+static gpx_status debug_head_product(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X, int64_t ldx,
+                                     const double* alpha, const double* Xs, int64_t m, int64_t ldxs, const double* W,
+                                     int64_t ldw, double* ss, double* mu_part, int64_t ldmu, const int32_t* list,
+                                     const int32_t* count) {
   Context* c = reinterpret_cast<Context*>(h);
   if (!c) return GPX_INVALID_ARG;
   GPX_TRY(check_sweep_sizes(c, p, n, m, kDebugMaxM));
@@ -1286,7 +1303,26 @@ gpx_status gpx_debug_head_product_f64(gpx_handle h, const gpx_kernel_params* p, 
   if (!gpx::sweep_lazy_ok(*p)) return fail(c, GPX_INVALID_ARG, "the fused head covers the fp64 covariance with d <= 16");
   GPX_USE_DEVICE(c);
   const gpx::SweepModel M{c, *p, (int)n, (int)npad, X, ldx, W, ldw, alpha, 1};
-  return hip_check(c, gpx::launch_debug_head_product(M, {Xs, ldxs, m, 0}, ss, mu_part, ldmu), "debug_head_product");
+  return hip_check(c, gpx::launch_debug_head_product(M, {Xs, ldxs, m, 0}, ss, mu_part, ldmu, list, count),
+                   "debug_head_product");
+}
+
+gpx_status gpx_debug_head_product_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X, int64_t ldx,
+                                      const double* alpha, const double* Xs, int64_t m, int64_t ldxs, const double* W,
+                                      int64_t ldw, double* ss, double* mu_part, int64_t ldmu) {
+  return debug_head_product(h, p, n, X, ldx, alpha, Xs, m, ldxs, W, ldw, ss, mu_part, ldmu, nullptr, nullptr);
+}
+
+gpx_status gpx_debug_head_product_list_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X,
+                                           int64_t ldx, const double* alpha, const double* Xs, int64_t m, int64_t ldxs,
+                                           const double* W, int64_t ldw, double* ss, double* mu_part, int64_t ldmu,
+                                           const int32_t* list, const int32_t* count) {
+  Context* c = reinterpret_cast<Context*>(h);
+  if (!c) return GPX_INVALID_ARG;
+  GPX_NONNULL(c, list);
+  GPX_NONNULL(c, count);
+  if (reinterpret_cast<uintptr_t>(list) % 8) return fail(c, GPX_INVALID_ARG, "list must be 8-byte aligned");
+  return debug_head_product(h, p, n, X, ldx, alpha, Xs, m, ldxs, W, ldw, ss, mu_part, ldmu, list, count);
 }
 
 gpx_status gpx_debug_stage_product_workspace_size(int64_t ncols, size_t* bytes) {

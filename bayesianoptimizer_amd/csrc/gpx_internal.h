@@ -61,6 +61,8 @@ struct Context {
                            // with the lazy head's exact means instead of their bound
   int sweep_head = 1;      // (gpx_debug_set_sweep_head, no option slot) lazy pruned sweep's head: 1 K* rows 0 .. 127 and row tile 0 of the product in one kernel,
                            // 0 the K* launch and the first stage apart
+  int sweep_order = 1;     // (gpx_debug_set_sweep_order, no option slot) seeded lazy pruned sweep: 1 mean-first (prune on the mean's bound with
+                           // the prior variance, the head over what is left), 0 the head over every column first
   // gpx_sweep_stats of the last acquire call: the host-known parts, plus the device counters of the pruned path
   // ({candidates computed to the last row tile, product tiles executed}; they live in that call's workspace)
   int64_t sweep_stats[4] = {0, 0, 0, 0};
@@ -340,7 +342,9 @@ hipError_t launch_debug_stage_product(Context* c, int npad, const double* W, int
                                       int64_t ldss, void* ws);
 // The lazy pruned sweep's fused head through the production kernel (gpx_debug_head_product_f64): ss[c] = row tile 0's
 // variance partial and mu_part[jb * ld + c], jb = 0, 1, for every column up to q.m rounded up to 256 (ld at least that).
-hipError_t launch_debug_head_product(const SweepModel& M, const SweepCands& q, double* ss, double* mu_part, int64_t ld);
+// list != nullptr (gpx_debug_head_product_list_f64): the list-driven instance over the columns list[2 s], s < *count.
+hipError_t launch_debug_head_product(const SweepModel& M, const SweepCands& q, double* ss, double* mu_part, int64_t ld,
+                                     const int32_t* list = nullptr, const int32_t* count = nullptr);
 // The lazy pruned sweep's bound of the posterior mean (gpx_mubound.hip; RBF, fp64 covariance, d <= 16):
 // mu_approx[c] +- mu_slack[c] holds the exact path's mean of candidate c.  prep: mu_prep_doubles(npad, d) doubles,
 // 256-byte aligned; its first int64 ends up as the count of 256-candidate workgroups on the unfactorised path.

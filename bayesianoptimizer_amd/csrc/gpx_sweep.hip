@@ -733,13 +733,37 @@ trmm_stage_narrow_kernel(const double* __restrict__ W, int64_t ldw, int64_t C, i
 // row-block skip is a uniform branch on its counter.
 // ss goes to ss_part[c] (row tile 0) for the staged columns c0s <= c < c1s only, mu_part blocks 0 and 1 for every
 // column of the grid's groups, as the two launches this replaces wrote them.
+// The list-driven instance (list != nullptr; the mean-first order's head over the columns its first prune pass kept,
+// DESIGN §3): group g takes the columns list[128 g .. 128 g + 127].x, slots at or past *count are padding (zeros loaded,
+// nothing stored), the workgroups stride over the ceil(*count / 128) live groups, and both outputs go to the column's
+// own place.  Only the candidate loads' and the stores' addresses differ from the contiguous instance, so a column has
+// the same bits in either.  Workgroup 0 then writes the list's descriptor for the bound pass behind it (desc_out: list
+// 2, *count slots) and adds the groups to the product tiles run (stats[1]).
 constexpr int HP_COLS = 128;  // candidates per workgroup trip
 template <int DMAX, int KIND>
 __global__ void __launch_bounds__(WG, 2)
 head_product_kernel(gpx_kernel_params p, int n, const double* __restrict__ X, int64_t ldx,
                     const double* __restrict__ alpha, const double* __restrict__ Xs, int64_t ldxs, int64_t m_chunk,
                     int64_t C, const double* __restrict__ W, int64_t ldw, int ngroups, int64_t c0s, int64_t c1s,
-                    double* __restrict__ mu_part, double* __restrict__ ss_part) {
+                    double* __restrict__ mu_part, double* __restrict__ ss_part, const int2* __restrict__ list,
+                    const int* __restrict__ count, PruneDesc* __restrict__ desc_out, int64_t* __restrict__ stats) {
+  int cnt = 0;
+  if (list) {
+    cnt = *count;
+    ngroups = (cnt + HP_COLS - 1) / HP_COLS;
+    if (desc_out && blockIdx.x == 0 && threadIdx.x == 0) {
+      PruneDesc o;
+      o.buf = 0;
+      o.col0 = 0;
+      o.ncols = cnt;
+      o.ntiles = ngroups;
+      o.list = 2;
+      o.pad[0] = o.pad[1] = o.pad[2] = 0;
+      *desc_out = o;
+    }
+    if (stats && blockIdx.x == 0 && threadIdx.x == 0) stats[1] += ngroups;
+  }
+  if ((int)blockIdx.x >= ngroups) return;  // (a short list: the launch costs its grid)
   constexpr bool lin = (KIND == GPX_KERNEL_SCALE_LINEAR_MATERN52);
   constexpr int KS = DMAX / 4;
   constexpr int NJB = PRUNE_HEAD_ROWS / NB;
@@ -796,7 +820,9 @@ head_product_kernel(gpx_kernel_params p, int n, const double* __restrict__ X, in
       __syncthreads();  // the row block before this one has read sb / nb to the end (and na is written)
       for (int e = t; e < HP_COLS * DMAX; e += WG) {
         const int r = e / DMAX, k = e % DMAX;
-        const double v = (k < d && c0 + r < m_chunk) ? Xs[(c0 + r) * ldxs + k] : 0.0;
+        int64_t col = c0 + r < m_chunk ? c0 + r : -1;
+        if (list) col = c0 + r < cnt ? list[c0 + r].x : -1;
+        const double v = (k < d && col >= 0) ? Xs[col * ldxs + k] : 0.0;
         const double s = (k < d) ? v / p.lengthscale[k] : 0.0;
         sb[r][k] = s - cen[jb][k];
         if constexpr (lin) rb[r][k] = v;
@@ -862,7 +888,13 @@ head_product_kernel(gpx_kernel_params p, int n, const double* __restrict__ X, in
         double v = mu[cb];
         v += __shfl_xor(v, 16);
         v += __shfl_xor(v, 32);
-        if (lane < 16) mu_part[(int64_t)jb * C + c0 + 32 * w + 16 * cb + lane] = v;
+        int64_t col = c0 + 32 * w + 16 * cb + lane;
+        bool live = lane < 16;
+        if (list) {
+          live = live && col < cnt;
+          col = live ? list[col].x : 0;
+        }
+        if (live) mu_part[(int64_t)jb * C + col] = v;
       }
     }
     // trmm_colsum_store<128>'s sums: the tile's two wave rows apart, then low + high
@@ -881,8 +913,13 @@ head_product_kernel(gpx_kernel_params p, int n, const double* __restrict__ X, in
         v += __shfl_xor(v, 32);
         s[h] = v;
       }
-      const int64_t c = c0 + 32 * w + 16 * cb + m;
-      if (kq == 0 && c >= c0s && c < c1s) ss_part[c] = s[0] + s[1];
+      int64_t c = c0 + 32 * w + 16 * cb + m;
+      bool live = kq == 0 && c >= c0s && c < c1s;
+      if (list) {
+        live = kq == 0 && c < cnt;
+        c = live ? list[c].x : 0;
+      }
+      if (live) ss_part[c] = s[0] + s[1];
     }
   }
 }
@@ -1301,10 +1338,11 @@ __global__ void __launch_bounds__(WG) seed_prune_kernel(const double* __restrict
 
 // The pruned sweep's per-chunk reset (one thread): the first stage's column set (the chunk's columns from col0 on, in
 // place), zero survivor counts, and on the call's first chunk the incumbent (-inf), the counters and, in the top-k form
-// (tk_head), the scored list's and the pool's counts.
+// (tk_head), the scored list's and the pool's counts.  count2 (the mean-first order): one more count to zero.
 __global__ void prune_init_kernel(PruneDesc* __restrict__ desc, int* __restrict__ count,
                                   unsigned long long* __restrict__ tau, int64_t* __restrict__ stats, int col0,
-                                  int ncols, int rows0, int last, int first, int* __restrict__ tk_head) {
+                                  int ncols, int rows0, int last, int first, int* __restrict__ tk_head,
+                                  int* __restrict__ count2 = nullptr) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   if (first && tk_head) tk_head[0] = tk_head[1] = 0;  // the top-k form: empty scored list, empty pool
   PruneDesc d;
@@ -1316,6 +1354,7 @@ __global__ void prune_init_kernel(PruneDesc* __restrict__ desc, int* __restrict_
   d.pad[0] = d.pad[1] = d.pad[2] = 0;
   desc[0] = d;
   for (int s = 0; s < PRUNE_MAX_STAGES; ++s) count[s] = 0;
+  if (count2) *count2 = 0;
   if (first) {
     *tau = tau_key(-INFINITY);
     stats[0] = stats[1] = 0;
@@ -1662,8 +1701,11 @@ static void launch_kstar(const SweepModel& M, const SweepCands& q, const SweepBu
 // The fused head of the lazy form (head_product_kernel): mean partials of row blocks 0 and 1 for the columns the head's
 // K* launch covers (whole 256-column blocks of q.m), row tile 0's variance partial for the staged columns' tiles (from
 // col0 on, ncols of them), both at pitch C.  The grid is what the device holds at once; the workgroups stride.
+// list != nullptr: the list-driven instance over list[0 .. *count - 1] (q.m: the most the list can hold; the same
+// bounded grid, so a full list runs as the contiguous launch and a short one costs the grid); desc_out / stats optional.
 static void launch_head_product(const SweepModel& M, const SweepCands& q, int64_t C, double* mu_part, double* ss_part,
-                                int col0, int64_t ncols) {
+                                int col0, int64_t ncols, const int2* list = nullptr, const int* count = nullptr,
+                                PruneDesc* desc_out = nullptr, int64_t* stats = nullptr) {
   const gpx_kernel_params& p = M.p;
   const int ngroups = (int)((q.m + WG - 1) / WG) * (WG / HP_COLS);
   const int64_t c1s = col0 + (ncols + TT - 1) / TT * TT;
@@ -1678,7 +1720,7 @@ static void launch_head_product(const SweepModel& M, const SweepCands& q, int64_
         }();
         kernel<<<tail_grid(M.c, resident, ngroups), WG, 0, M.c->stream>>>(p, M.n, M.X, M.ldx, M.alpha, q.Xs, q.ldxs, q.m,
                                                                          C, M.W, M.ldw, ngroups, col0, c1s, mu_part,
-                                                                         ss_part);
+                                                                         ss_part, list, count, desc_out, stats);
       });
     }
   });
@@ -1786,10 +1828,10 @@ static int prune_stage_bounds(int nI, int* R) {
 // A stage after the first of a chunk, super-chunk or round: `tiles` wide tiles at most, how many are active only the
 // device knows.  One launch of the dual kernel; its workgroups take the narrow shape when the stage's wide tiles would
 // not give every CU one (trmm_sumsq_body).  The grid is the larger of the two shapes' needs: the narrow shape runs
-// below cus wide tiles only, so it needs fewer than 4 cus workgroups.
+// below cus wide tiles only, so it needs fewer than 4 cus workgroups.  narrow_below: another bound than cus (0: cus).
 static void launch_tail_stage(Context* c, const double* W, int64_t ldw, int64_t C, int nI, double* ss_part,
-                              PruneStage st, int tiles) {
-  const int cus = sweep_cu_count(c);
+                              PruneStage st, int tiles, int narrow_below = 0) {
+  const int cus = narrow_below ? narrow_below : sweep_cu_count(c);
   st.narrow_below = cus;
   const int64_t wide = (int64_t)tiles * st.nrows;
   const int64_t narrow = 4 * (wide < cus ? wide : (int64_t)cus);
@@ -1823,7 +1865,7 @@ static PruneBufs prune_bufs(const double* kstar, int64_t ld0, const PruneState& 
 static void launch_seed_block(const SweepModel& M, const SweepCands& q, const SweepBuffers& b, const PruneState& ps,
                               const FinalizeArgs& fa, const SeedPlan& sp, int R1, bool one_stage, bool first,
                               bool build_kstar, double* rec_val, int64_t* rec_idx, int64_t* host_stats,
-                              const TopkSweep* tk) {
+                              const TopkSweep* tk, int* count2 = nullptr) {
   Context* c = M.c;
   const int64_t C = b.chunk;
   const int nJB = M.npad / NB, nI = M.npad / TT;
@@ -1836,7 +1878,7 @@ static void launch_seed_block(const SweepModel& M, const SweepCands& q, const Sw
   {
     LaunchTimer tm(c, GPX_TIMER_TRMM);
     prune_init_kernel<<<1, 64, 0, c->stream>>>(ps.desc, ps.count, ps.tau, ps.stats, sp.col0, sp.ncols, R1, one_stage,
-                                               first, tk ? tk->head : nullptr);
+                                               first, tk ? tk->head : nullptr, count2);
     if (sp.seed && !build_kstar) product();
   }
   if (!sp.seed) return;
@@ -1866,6 +1908,7 @@ struct StagePlan {
   int cap;               // the most columns the set can have
   double* rec_val;       // the record cursor
   int64_t* rec_idx;
+  int narrow_below = 0;  // launch_tail_stage's bound for the narrow shape (0: the CU count)
 };
 static void launch_stages(const SweepModel& M, const SweepCands& q, const PruneState& ps, const FinalizeArgs& fa,
                           const StagePlan& sg, int64_t C, const TopkSweep* tk) {
@@ -1891,7 +1934,7 @@ static void launch_stages(const SweepModel& M, const SweepCands& q, const PruneS
       if (s == 0 && sg.wide_first)
         trmm_stage_kernel<<<tiles * st.nrows, WG, 0, c->stream>>>(M.W, M.ldw, sg.pitch, nI, sg.ss_part, st);
       else
-        launch_tail_stage(c, M.W, M.ldw, sg.pitch, nI, sg.ss_part, st, tiles);
+        launch_tail_stage(c, M.W, M.ldw, sg.pitch, nI, sg.ss_part, st, tiles, sg.narrow_below);
       if (s == sg.ns - 1) break;
       sel.desc = desc + s;
       sel.count = count + s;
@@ -1948,6 +1991,14 @@ hipError_t launch_sweep_chunk_pruned(const SweepModel& M, const SweepCands& q, c
 //         go through a round like the tail's (gather build, row tiles 1 .. nI - 1 in one stage, finalize mode 1:
 //         records, incumbent, for top-k the scored list and the pool); seed_prune_kernel then tests every other
 //         column's U against that incumbent.  No column is scored twice.  Later super-chunks have no seed.
+//         That is the parent order of a seeded span (sweep_order 0, and always for UCB, the variance acquisition, the
+//         top-k form above k = 64, the exact head means and sweep_head 0).  The default, mean-first (sweep_order 1),
+//         runs no head before the bound pass: U0 = score_ub(mean bound, prior variance), which bounds U from above
+//         because the prior variance bounds the posterior's; the seed is the slice maxima of U0 through EVERY row tile
+//         of the product; seed_prune_kernel keeps S1 = {U0 >= incumbent}; the list-driven head_product_kernel builds K*
+//         rows 0 .. 127 and row tile 0 for S1 alone; and a second bound pass (mode 4 over S1's list) keeps the columns
+//         with U >= incumbent: the parent order's survivors whenever the seed's incumbent is the same.  Later
+//         super-chunks take the same two passes against the running incumbent, without a seed.
 //  tail   rounds of at most C survivors: KSTAR_GATHER rebuilds their full-height columns into the chunk buffer (the bits
 //         of the full build) and, after a mean bound, their exact mean partials into ph.mu_part, then the staged pipeline
 //         of launch_sweep_chunk_pruned (launch_stages) from row tile 1 on, the partials
@@ -1970,9 +2021,27 @@ hipError_t launch_sweep_super_pruned(const SweepModel& M, const SweepCands& q, c
   const FinalizeArgs fa = finalize_args(M.p, a, 1, nullptr, nullptr);
   // the seeded order: the call's first span when the call is longer than one chunk (a list of PRUNE_SEED fits a chunk's)
   const bool seeded = first && q.m > C && C >= PRUNE_SEED;
+  // the mean-first order (sweep_order 1): a seeded span and the spans behind the first, with the mean's bound and the
+  // fused head.  S1, the columns its first prune pass keeps, goes to the head rows' region (idle under sweep_head), its
+  // count to the slot behind the seed list's.  EI and logEI only: the RBF prior variance is the same for every column,
+  // so U0 ranks by the mean alone, and UCB and the variance acquisition, whose order the variance decides, got a weaker
+  // seed and more survivors from it than from the head's bound.  The top-k form up to k = 64 only: its incumbent is the
+  // k-th best of the seed's 1024 exact scores, so near k = 1024 every slice's seed counts, and U0 picks them worse than
+  // the head's bound does.  Both limits are measured in DESIGN §5 (tools/order_limits_probe.py on a build with
+  // GPX_MEAN_FIRST_UNLIMITED, which drops them: a measurement build, never the shipped one).
+#ifdef GPX_MEAN_FIRST_UNLIMITED
+  const bool mean_ranked = true;
+#else
+  const bool mean_ranked = (a->kind == GPX_ACQ_EI || a->kind == GPX_ACQ_LOGEI) && (!tk || tk->k <= 64);
+#endif
+  const bool mean_first = c->sweep_order == 1 && c->sweep_head && mu_bound && mean_ranked && (seeded || !first);
+  static_assert(4 * (PRUNE_MAX_STAGES + 2) <= 256, "two slots behind the stages' counts");
+  int2* s1 = reinterpret_cast<int2*>(ph.head);
+  int* n1 = ps.count + PRUNE_MAX_STAGES + 1;
   const SeedPlan sp = seed_plan(first && !seeded, q.m, C);  // (seeded: no leading block, every column is staged)
-  launch_seed_block(M, q, b, ps, fa, sp, R[1], false, first, true, ph.rec_val + *recs, ph.rec_idx + *recs, host_stats,
-                    tk);
+  // (mean-first: the head's tiles are counted by its own launch, from S1)
+  launch_seed_block(M, q, b, ps, fa, sp, mean_first ? 0 : R[1], false, first, true, ph.rec_val + *recs,
+                    ph.rec_idx + *recs, host_stats, tk, mean_first ? n1 : nullptr);
   *recs += sp.seed_blocks;
   if (sp.ncols == 0) return hipGetLastError();
   // head: the columns of the whole super-chunk (a leading seed block's again: the head kernel has no column offset)
@@ -2005,7 +2074,10 @@ hipError_t launch_sweep_super_pruned(const SweepModel& M, const SweepCands& q, c
   int* nseed = ps.count + PRUNE_MAX_STAGES;
   {
     LaunchTimer tm(c, GPX_TIMER_TRMM);
-    if (c->sweep_head) {
+    if (mean_first) {
+      // no product before the bound pass: it takes the prior variance in the variance bound's place and reads no
+      // partial.  A seeded span keeps these bounds U0 in U; a later span selects S1 against the running incumbent.
+    } else if (c->sweep_head) {
       launch_head_product(M, q, MA, ph.mu_part, ph.ss_part, sp.col0, sp.ncols);
     } else {
       const PruneStage st{prune_bufs(ph.head, MA, ps), ps.desc, 0, R[1], 0};
@@ -2014,19 +2086,25 @@ hipError_t launch_sweep_super_pruned(const SweepModel& M, const SweepCands& q, c
     PruneSel sel{};
     sel.tau = ps.tau;
     sel.desc = ps.desc;
-    sel.count = ps.count;
-    sel.list0 = ph.survivors;  // (the descriptor's list is -1: the survivors go to list0)
+    sel.count = mean_first ? n1 : ps.count;
+    sel.list0 = mean_first ? s1 : ph.survivors;  // (the descriptor's list is -1: the survivors go to list0)
     sel.mu_bound = mu_bound ? ph.mu_part + 2 * MA : nullptr;
     sel.u_out = seeded ? U : nullptr;  // (seeded: no incumbent yet, the bounds are kept)
-    finalize_kernel<<<(sp.ncols + WG - 1) / WG, WG, 0, c->stream>>>(fa, 4, q.Xs, q.ldxs, q.m, MA, 1, nJB, R[1],
-                                                                    ph.mu_part, ph.ss_part, nullptr, 0, nullptr, nullptr,
-                                                                    nullptr, nullptr, q.index_offset, sel);
+    finalize_kernel<<<(sp.ncols + WG - 1) / WG, WG, 0, c->stream>>>(fa, 4, q.Xs, q.ldxs, q.m, MA, 1, nJB,
+                                                                    mean_first ? 0 : R[1], ph.mu_part, ph.ss_part,
+                                                                    nullptr, 0, nullptr, nullptr, nullptr, nullptr,
+                                                                    q.index_offset, sel);
     if (seeded) seed_select_kernel<<<PRUNE_SEED, WG, 0, c->stream>>>(U, q.m, seed, nseed);
   }
   if (seeded) {
     // seed: the best bound of each slice through the gather build and the rest of the product (tile 0's partial is the
-    // head's) as one round of one stage: exact scores, records, the incumbent (top-k: the scored list and the pool)
-    const int Rs[2] = {1, nI};
+    // head's; mean-first: every row tile, the stage kernels' tile 0 has the head's bits) as one round of one stage:
+    // exact scores, records, the incumbent (top-k: the scored list and the pool)
+    const int Rs[2] = {mean_first ? 0 : 1, nI};
+    // (mean-first at padded n = 4096: the seed's 8 x 32 wide tiles are exactly the 256 CUs, one tile each, and the stage
+    // lasts as long as its deepest tile: 0.46 ms in the wide shape against 0.37 ms for the parent's 8 x 31 narrow ones,
+    // DESIGN §5.  So the seed's stage keeps the narrow shape at equality too.)
+    const int seed_narrow = mean_first && sweep_cu_count(c) > 0 ? sweep_cu_count(c) + 1 : 0;
     KstarAux aux{};
     aux.list = reinterpret_cast<const int*>(seed);
     aux.lstride = 2;
@@ -2036,19 +2114,37 @@ hipError_t launch_sweep_super_pruned(const SweepModel& M, const SweepCands& q, c
     aux.desc = ps.desc + 1;
     aux.rcount = ps.count + 1;
     aux.stats = ps.stats;
-    aux.rows0 = nI - 1;
+    aux.rows0 = nI - Rs[0];
     aux.last = 1;
     aux.mu_out = mu_bound ? ph.mu_part : nullptr;
     aux.ldmu = MA;
     launch_kstar(M, q.first(PRUNE_SEED), b, KSTAR_GATHER, aux);
     launch_stages(M, q, ps, fa,
                   StagePlan{prune_bufs(b.kstar, C, ps, seed), ph.mu_part, ph.ss_part, MA, Rs, 1, 1, false, PRUNE_SEED,
-                            ph.rec_val + *recs, ph.rec_idx + *recs},
+                            ph.rec_val + *recs, ph.rec_idx + *recs, seed_narrow},
                   C, tk);
     *recs += PRUNE_SEED / WG;
-    // prune: every other column's bound against the seed's incumbent
+    // prune: every other column's bound against the seed's incumbent (mean-first: pass 1, into S1)
     LaunchTimer tm(c, GPX_TIMER_ACQ);
-    seed_prune_kernel<<<(sp.ncols + WG - 1) / WG, WG, 0, c->stream>>>(U, q.m, seed, ps.tau, ph.survivors, ps.count);
+    seed_prune_kernel<<<(sp.ncols + WG - 1) / WG, WG, 0, c->stream>>>(U, q.m, seed, ps.tau, mean_first ? s1 : ph.survivors,
+                                                                      mean_first ? n1 : ps.count);
+  }
+  if (mean_first) {
+    // the head over S1 alone (it also writes S1's descriptor to ps.desc[0], read by nothing else from here on), then
+    // prune pass 2: the bound pass of the parent's order over S1, with the head's variance partial.  U1 <= U0, so the
+    // survivors are the parent's whenever the incumbent is.
+    LaunchTimer tm(c, GPX_TIMER_TRMM);
+    launch_head_product(M, q.first(sp.ncols), MA, ph.mu_part, ph.ss_part, 0, 0, s1, n1, ps.desc, ps.stats);
+    PruneSel sel{};
+    sel.tau = ps.tau;
+    sel.desc = ps.desc;
+    sel.count = ps.count;
+    sel.list0 = ph.survivors;  // (the descriptor's list is 2: the survivors go to list0)
+    sel.list2 = s1;
+    sel.mu_bound = ph.mu_part + 2 * MA;
+    finalize_kernel<<<(sp.ncols + WG - 1) / WG, WG, 0, c->stream>>>(fa, 4, q.Xs, q.ldxs, q.m, MA, 1, nJB, R[1],
+                                                                    ph.mu_part, ph.ss_part, nullptr, 0, nullptr, nullptr,
+                                                                    nullptr, nullptr, q.index_offset, sel);
   }
   // tail (its passes read the survivors' exact partials, written by their gather)
   for (int64_t r0 = 0; r0 < sp.ncols; r0 += C) {
@@ -2241,8 +2337,9 @@ hipError_t launch_debug_stage_product(Context* c, int npad, const double* W, int
   return hipGetLastError();
 }
 
-hipError_t launch_debug_head_product(const SweepModel& M, const SweepCands& q, double* ss, double* mu_part, int64_t ld) {
-  launch_head_product(M, q, ld, mu_part, ss, 0, (q.m + WG - 1) / WG * WG);
+hipError_t launch_debug_head_product(const SweepModel& M, const SweepCands& q, double* ss, double* mu_part, int64_t ld,
+                                     const int32_t* list, const int32_t* count) {
+  launch_head_product(M, q, ld, mu_part, ss, 0, (q.m + WG - 1) / WG * WG, reinterpret_cast<const int2*>(list), count);
   return hipGetLastError();
 }
 

@@ -218,17 +218,18 @@ class GPEngine:
     # -- fit --------------------------------------------------------------------------------------
     def set_option(self, name: str, value: int) -> None:
         """Per-handle tuning / diagnostic option (include/gpx.h GPX_OPT_*, by the names of _capi.OPTIONS: spin_limit,
-        sweep_fused, gram_split, potrf_lazy, potrf_mode, potrf_switch, potrf_split, sweep_prune), and "sweep_head", the
-        A/B switch of the lazy pruned sweep's head (gpx_debug_set_sweep_head: it has no option slot)."""
-        if name == "sweep_head":
-            self._check(self.lib.gpx_debug_set_sweep_head(self.handle, int(value)))
+        sweep_fused, gram_split, potrf_lazy, potrf_mode, potrf_switch, potrf_split, sweep_prune), and "sweep_head" and
+        "sweep_order", the A/B switches of the lazy pruned sweep's head and of its seeded order (gpx_debug_set_sweep_head,
+        gpx_debug_set_sweep_order: they have no option slot)."""
+        if name in ("sweep_head", "sweep_order"):
+            self._check(getattr(self.lib, f"gpx_debug_set_{name}")(self.handle, int(value)))
             return
         self._check(self.lib.gpx_set_option(self.handle, _capi.OPTIONS[name], int(value)))
 
     def get_option(self, name: str) -> int:
-        if name == "sweep_head":
+        if name in ("sweep_head", "sweep_order"):
             h = ctypes.c_int32()
-            self._check(self.lib.gpx_debug_get_sweep_head(self.handle, ctypes.byref(h)))
+            self._check(getattr(self.lib, f"gpx_debug_get_{name}")(self.handle, ctypes.byref(h)))
             return int(h.value)
         v = ctypes.c_int64()
         self._check(self.lib.gpx_get_option(self.handle, _capi.OPTIONS[name], ctypes.byref(v)))

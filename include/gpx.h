@@ -767,6 +767,22 @@ gpx_status gpx_debug_get_sweep_head(gpx_handle h, int32_t* value_host);
 gpx_status gpx_debug_head_product_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X, int64_t ldx,
                                       const double* alpha, const double* Xs, int64_t m, int64_t ldxs, const double* W,
                                       int64_t ldw, double* ss, double* mu_part, int64_t ldmu);
+/* The same kernel's list-driven instance (the mean-first order's head): of the candidates list[2 s], s = 0 ..
+ * *count - 1 (list: device, 8-byte aligned, pairs of int32 {candidate in [0, m), ignored}, at most m rounded up to 256
+ * pairs; count: device), ss[c] and mu_part[jb * ldmu + c] at the candidate's own place c with the bits gpx_debug_head_product_f64
+ * gives that candidate; no other entry is written, and a count of 0 writes nothing. */
+gpx_status gpx_debug_head_product_list_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X,
+                                           int64_t ldx, const double* alpha, const double* Xs, int64_t m, int64_t ldxs,
+                                           const double* W, int64_t ldw, double* ss, double* mu_part, int64_t ldmu,
+                                           const int32_t* list, const int32_t* count);
+/* The order of the lazy pruned sweep's seeded spans and of the spans behind them (calls longer than one chunk, RBF with
+ * the mean's bound, the fused head, EI or logEI, the top-k form up to k = 64; A/B measurements and tests, no slot among
+ * GPX_OPT_*).  1 (default): mean-first: the
+ * columns are ranked and pruned on the mean's bound with the prior variance, and K* rows 0 .. 127 and row tile 0 of the
+ * product are built only for the columns that pass.  0: the head over every column first.  The same results either
+ * way; gpx_sweep_stats [1] and [2] count what ran.  Any other value is GPX_INVALID_ARG. */
+gpx_status gpx_debug_set_sweep_order(gpx_handle h, int32_t value);
+gpx_status gpx_debug_get_sweep_order(gpx_handle h, int32_t* value_host);
 /* One stage of the pruned sweep's product in a named tile shape, for bit checks (no production path uses it; DESIGN
  * §3): row tiles I0 .. I0 + nrows - 1 of V = W^T K* over slots 0 .. ncols - 1 of a caller's K* buffer.  W: device,
  * padded_n x padded_n upper triangular (pitch ldw), kstar: device, padded_n rows of pitch ldk >= ncols rounded up to

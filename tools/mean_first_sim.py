@@ -1,0 +1,96 @@
+"""CPU simulation of the two seeded orders of the lazy pruned sweep, NumPy fp64, exact means in place of
+the mean bound (whose slack is about 2^-18 sum |alpha| k), logEI.  No GPU.
+
+Per problem, for the parent's order (sweep_order 0: the head over every column, seed = the arg max of U1 in each of
+1,024 slices, prune on U1) and for mean-first (sweep_order 1: seed = the arg max of U0 per slice, prune pass 1 on U0,
+the head over S1, prune pass 2 on U1):
+    U0 = score_ub(mu, k**)                     the prior variance
+    U1 = score_ub(mu, k** - |row tile 0|^2)    the variance left after the product's first 128 rows
+the incumbent tau the seed gives, whether the seed holds the optimum, S1 (columns that need the head), S2 (survivors
+outside the seed) and the 128 x 128 product tiles up to the tail, with the tail's upper bound (every survivor through
+every remaining row tile): parent ceil(m / 128) + 8 (nI - 1) + tail, mean-first 8 nI + ceil(S1 / 128) + tail.
+
+Problems: bench (bench.py's step, seed 0), hard (seed 1000), n1024 (bench's side configuration), t384 and t640 (the
+shapes and inputs of tests/test_gpu_sweep_seed.py and tests/test_gpu_sweep_meanfirst.py at d = 4).  One JSON line each.
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import scipy.linalg as sla
+from bayesianoptimizer_amd import synthetic
+from oracle import gp_oracle as O
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--problems", default="t384,t640,n1024,bench,hard")
+a = ap.parse_args()
+SEED, EPS, BLK = 1024, 1e-9, 1 << 15
+
+
+def keeps(U, tau):  # finalize_kernel mode 4's test
+    return ~(U + EPS * (np.abs(U) + abs(tau) + 1.0) < tau)
+
+
+def inputs(name):
+    if name in ("t384", "t640"):
+        n, m = (384, 400_000) if name == "t384" else (640, 250_000)
+        X, y = O.synthetic_problem(n, 4, 21)
+        return X, y, O.sobol_candidates(m, 4, 22)
+    n, seed = {"bench": (4096, 0), "hard": (4096, 1000), "n1024": (1024, 0)}[name]
+    X, y = synthetic.problem(n, 8, seed)
+    return X, y, synthetic.sobol(1 << 20, 8, seed + 1)
+
+
+for name in a.problems.split(","):
+    X, y, Xs = inputs(name)
+    n, d = X.shape
+    m = Xs.shape[0]
+    kp = O.KernelParams(O.RBF, np.full(d, O.botorch_default_lengthscale(d)), noise=1e-4)
+    st = O.fit(X, y, kp)
+    best_f = float(y.max())
+    nI = (n + 127) // 128
+    rows = min(128, n)
+    L0 = st.L[:rows, :rows]
+    U0, U1 = np.empty(m), np.empty(m)
+    for c in range(0, m, BLK):
+        P = Xs[c:c + BLK]
+        K = O.kernel_matrix(X, P, kp)
+        v0 = sla.solve_triangular(L0, K[:rows], lower=True, check_finite=False)
+        mu = kp.const_mean + st.alpha @ K
+        kd = O.kernel_diag(P, kp)
+        U0[c:c + BLK] = O.acquisition(mu, np.maximum(kd, 1e-10), O.ACQ_LOGEI, best_f)
+        U1[c:c + BLK] = O.acquisition(mu, np.maximum(kd - (v0 * v0).sum(0), 1e-10), O.ACQ_LOGEI, best_f)
+
+    def exact(idx):
+        out = np.empty(len(idx))
+        for c in range(0, len(idx), BLK):
+            out[c:c + BLK] = O.acquisition(*O.posterior(st, Xs[idx[c:c + BLK]]), O.ACQ_LOGEI, best_f)
+        return out
+
+    def seed_of(U):
+        pick = np.array([s * m // SEED + int(np.argmax(U[s * m // SEED:(s + 1) * m // SEED])) for s in range(SEED)])
+        sc = exact(pick)
+        return pick, float(sc.max()), int(pick[int(np.argmax(sc))])
+
+    out = {"problem": name, "n": n, "d": d, "m": m}
+    # the parent's order
+    pick, tau, best = seed_of(U1)
+    k = keeps(U1, tau)
+    k[pick] = False
+    surv = np.flatnonzero(k)
+    opt = max(tau, float(exact(surv).max())) if surv.size else tau
+    tail = -(-surv.size // 128) * (nI - 1)
+    out["parent"] = {"tau": tau, "seed_best": best, "survivors": int(surv.size),
+                     "tiles_before_tail": -(-m // 128) + 8 * (nI - 1), "tail_tiles_at_most": tail}
+    # mean-first
+    pick, tau, best = seed_of(U0)
+    k0 = keeps(U0, tau)
+    k0[pick] = False
+    k1 = k0 & keeps(U1, tau)
+    s1, s2 = int(k0.sum()), int(k1.sum())
+    out["mean_first"] = {"tau": tau, "seed_best": best, "seed_holds_the_optimum": bool(tau >= opt), "S1": s1, "S2": s2,
+                         "tiles_before_tail": 8 * nI + -(-s1 // 128), "tail_tiles_at_most": -(-s2 // 128) * (nI - 1)}
+    print(json.dumps(out), flush=True)

@@ -5,7 +5,11 @@ A call over one chunk's candidates has one tail round (and the leading block as 
 descriptors (slot 1: the gather's set, then one per compaction: buf, col0, ncols, ntiles, list) and the survivors after
 every stage (count[0]: the head's).  After the whole call (one span of 2^20, seeded from the head's bound) the later
 rounds have overwritten them, but count[0] is still the survivors of the last span's prune pass, the seed's columns
-left out, and sweep_stats[1] - 1024 is what the tail computed to the end.  One JSON line per case.  The library is the tree's, or GPX_LIB's.
+left out, and sweep_stats[1] - 1024 is what the tail computed to the end.  In the mean-first order (sweep_order 1, the
+default for this call) descriptor slot 0 of the whole call is no longer the span's contiguous column set: the list-driven
+head overwrites it with the set S1 its first prune pass kept (buf 0, col0 0, ncols = |S1|, ntiles = the head's groups,
+list 2), and count[9] is |S1| again ("s1"; count[8] is the seed list's length).  One JSON line per case.  The library is
+the tree's, or GPX_LIB's.
 """
 import argparse
 import json
@@ -34,7 +38,7 @@ def workspace_state(npad, m):
     at = (-ws.data_ptr()) % 256 + (main + 255) // 256 * 256
     torch.cuda.synchronize()
     return (ws[at:at + 256].view(torch.int32).reshape(8, 8)[:, :5].tolist(),
-            ws[at + 256:at + 288].view(torch.int32).tolist())
+            ws[at + 256:at + 296].view(torch.int32).tolist())
 
 
 for seed in (int(s) for s in a.seeds.split(",")):
@@ -48,4 +52,5 @@ for seed in (int(s) for s in a.seeds.split(",")):
         stats = eng.sweep_stats()
         desc, count = workspace_state(npad, m)
         print(json.dumps({"case": f"seed{seed}_{name}", "m": m, "sweep_stats": list(stats), "best": int(bi.item()),
-                          "descriptors": desc[:7], "counts": count[:7]}), flush=True)
+                          "descriptors": desc[:7], "counts": count[:7], "seed": count[8], "s1": count[9]}),
+              flush=True)
