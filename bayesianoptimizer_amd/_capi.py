@@ -251,6 +251,10 @@ _PROTOS = {
     "gpx_svgp_predict_f64": (c_int32, [_h, POINTER(KernelParamsC), c_int64, c_int64, _p, c_int64, c_int64, _p, _p,
                                        _p, _p, c_int64, c_int64, c_double, _p, c_int64, _p, c_int64, _p, _p,
                                        c_size_t]),
+    "gpx_svgp_acquire_workspace_size": (c_int32, [c_int64, c_int64, c_int64, POINTER(c_size_t)]),
+    "gpx_svgp_acquire_f64": (c_int32, [_h, POINTER(KernelParamsC), c_int64, c_int64, _p, c_int64, c_int64, _p, _p,
+                                       _p, POINTER(c_double), POINTER(c_double), POINTER(c_double), _p, c_int64,
+                                       c_int64, POINTER(AcqParamsC), c_int64, c_int64, _p, _p, _p, _p, c_size_t]),
     "gpx_svgp_moments_grad_workspace_size": (c_int32, [c_int64, c_int64, POINTER(c_size_t)]),
     "gpx_svgp_moments_grad_f64": (c_int32, [_h, POINTER(KernelParamsC), c_int64, _p, c_int64, _p, _p, _p, _p, c_int64,
                                             c_int64, c_int64, _p, _p, _p, _p, _p, c_size_t]),

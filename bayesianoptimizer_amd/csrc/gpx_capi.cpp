@@ -1679,6 +1679,78 @@ gpx_status gpx_svgp_predict_f64(gpx_handle h, const gpx_kernel_params* p, int64_
   return GPX_OK;
 }
 
+gpx_status gpx_svgp_acquire_workspace_size(int64_t M, int64_t m, int64_t k, size_t* bytes) {
+  if (!bytes || M < 1 || M > 65536 || m < 1 || m > ((int64_t)1 << 30) || k < 1 || k > m) return GPX_INVALID_ARG;
+  *bytes = gpx::svgp_acquire_layout(padded(M), m, gpx::topk_workspace_bytes(m)).total;
+  return GPX_OK;
+}
+
+gpx_status gpx_svgp_acquire_f64(gpx_handle h, const gpx_kernel_params* p, int64_t ntask, int64_t M, const double* Z,
+                                int64_t ldz, int64_t stride_z, const double* W, const double* W2, const double* alpha,
+                                const double* weights_host, const double* y_mean_host, const double* y_scale_host,
+                                const double* Xs, int64_t m, int64_t ldxs, const gpx_acq_params* a,
+                                int64_t index_offset, int64_t k, double* val_out, int64_t* idx_out, double* scores_out,
+                                void* ws, size_t ws_bytes) {
+  Context* c = reinterpret_cast<Context*>(h);
+  if (!c) return GPX_INVALID_ARG;
+  GPX_TRY(check_svgp(c, p, ntask, M));
+  GPX_NONNULL(c, Z);
+  GPX_NONNULL(c, W);
+  GPX_NONNULL(c, W2);
+  GPX_NONNULL(c, alpha);
+  GPX_NONNULL(c, weights_host);
+  GPX_NONNULL(c, Xs);
+  GPX_NONNULL(c, val_out);
+  GPX_NONNULL(c, idx_out);
+  GPX_NONNULL(c, ws);
+  for (int64_t t = 0; t < ntask; ++t) {
+    if (!std::isfinite(weights_host[t])) return fail(c, GPX_INVALID_ARG, "objective weights must be finite");
+    if (y_scale_host && !(y_scale_host[t] > 0.0)) return fail(c, GPX_INVALID_ARG, "y_scale must be positive");
+  }
+  if (m < 1 || m > ((int64_t)1 << 30)) return fail(c, GPX_INVALID_ARG, "m must be in [1, 2^30]");
+  GPX_TRY(check_acq(c, a, index_offset, false));
+  if (k < 1 || k > m) return fail(c, GPX_INVALID_ARG, "k must be in [1, m]");
+  GPX_TRY(check_ld(c, ldz, p[0].d, "Z", false));
+  GPX_TRY(check_ld(c, ldxs, p[0].d, "Xs", false));
+  if (ntask > 1 && stride_z < M * ldz) return fail(c, GPX_INVALID_ARG, "task stride of Z smaller than one task");
+  const int64_t Mpad = padded(M);
+  const gpx::SvgpAcquireLayout A = gpx::svgp_acquire_layout(Mpad, m, gpx::topk_workspace_bytes(m));
+  if (ws_bytes < A.total) return fail(c, GPX_INVALID_ARG, "svgp acquire workspace too small");
+  const gpx::SweepBuffers b = gpx::sweep_carve(ws, A.sweep).b;
+  char* base = reinterpret_cast<char*>(gpx::up256(reinterpret_cast<uintptr_t>(ws)));
+  auto dbl = [&](gpx::SvgpAcquireRegion id) { return reinterpret_cast<double*>(base + A.r[id].at); };
+  double* ss2 = dbl(gpx::SQ_SS2_PART);
+  double* scores = scores_out ? scores_out : dbl(gpx::SQ_SCORES);
+  gpx::MultiOutput mo;
+  mo.acc_mu = dbl(gpx::SQ_ACC_MU);
+  mo.acc_var = dbl(gpx::SQ_ACC_VAR);
+  GPX_USE_DEVICE(c);
+  int64_t rec = 0;
+  for (int64_t s = 0; s < m; s += b.chunk) {
+    const int64_t mc = (m - s) < b.chunk ? (m - s) : b.chunk;
+    for (int64_t t = 0; t < ntask; ++t) {
+      mo.weight = weights_host[t];
+      mo.y_mean = y_mean_host ? y_mean_host[t] : 0.0;
+      mo.y_scale = y_scale_host ? y_scale_host[t] : 1.0;
+      mo.first = t == 0;
+      GPX_TRY(hip_check(c,
+                        gpx::launch_svgp_chunk(c, p[t], 0.0, (int)t, (int)M, (int)Mpad, Z + t * stride_z, ldz,
+                                               W + t * Mpad * Mpad, W2 + t * Mpad * Mpad, Mpad, alpha + t * Mpad,
+                                               Xs + s * ldxs, ldxs, mc, b, ss2, nullptr, 0, nullptr, 0, nullptr, &mo),
+                        "svgp acquire"));
+    }
+    // mode 3 of the finalize: the chunk's scores; its block records are not read (the selection below sorts the scores)
+    GPX_TRY(hip_check(c, gpx::launch_multi_score(c, {nullptr, 0, mc, index_offset + s}, mo, *a, scores + s,
+                                                 b.rec_val + rec, b.rec_idx + rec),
+                      "svgp acquire (score)"));
+    rec += (mc + 255) / 256;
+  }
+  GPX_TRY(hip_check(c, gpx::launch_topk(c, scores, m, k, idx_out, val_out, base + A.r[gpx::SQ_SORT_WS].at,
+                                        A.r[gpx::SQ_SORT_WS].bytes),
+                    "svgp acquire (topk)"));
+  return hip_check(c, gpx::launch_index_shift(c, idx_out, k, index_offset), "svgp acquire (indices)");
+}
+
 gpx_status gpx_svgp_moments_grad_workspace_size(int64_t M, int64_t m, size_t* bytes) {
   if (!bytes || M < 1 || M > 65536 || m < 1 || m > GPX_MAX_GRAD_CANDIDATES) return GPX_INVALID_ARG;
   *bytes = gpx::svgp_moments_ws_doubles((int)padded(M), (int)m) * sizeof(double) + 256;

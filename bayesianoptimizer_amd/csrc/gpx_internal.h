@@ -360,11 +360,13 @@ hipError_t launch_record_pack(Context* c, const double* best_val, const int64_t*
 hipError_t launch_argmax_records(Context* c, const int64_t* rec, int64_t count, double* best_val, int64_t* best_idx);
 
 // SVGP predictive of one task over a chunk (gpx_sweep.hip); ss2: (Mpad/128) x C partials of the full W2 product.
+// mo != nullptr (gpx_svgp_acquire_f64): the same K* build and products, then the task's latent moments weighted into
+// mo's accumulators (scored afterwards by launch_multi_score) instead of the predictive's outputs.
 hipError_t launch_svgp_chunk(Context* c, const gpx_kernel_params& p, double min_var, int task, int M, int Mpad,
                              const double* Z, int64_t ldz, const double* W, const double* W2, int64_t ldw,
                              const double* alpha, const double* Xs, int64_t ldxs, int64_t m_chunk,
                              const SweepBuffers& b, double* ss2, double* mean_out, int64_t ldmean, double* var_out,
-                             int64_t ldvar, double* score);
+                             int64_t ldvar, double* score, const MultiOutput* mo = nullptr);
 // The collapsed SVGP fit (gpx_svgpfit.hip; launch_svgp_kchunk: its covariance chunk through the sweep's K* build).
 hipError_t launch_svgp_kchunk(Context* c, const gpx_kernel_params& p, int M, int Mpad, const double* Z, int64_t ldz,
                               const double* zero_alpha, const double* Xs, int64_t ldxs, int64_t m_chunk, int64_t ldk,

@@ -2,7 +2,8 @@
 // gpx_svgp_bound_grad_f64 and gpx_svgp_bound_grad_z_f64.  svgp_layout walks every region once with a bump cursor; the reported sizes, the chunk width
 // a given workspace allows (svgp_chunk_width) and the pointers the launches get (SvgpWorkspace) all come from it.  The
 // fit is the gradient's layout without the gradient's regions, and the inducing-location gradient's is the gradient's
-// plus two regions.  No HIP in here: tests/host/svgp_layout_check.cpp
+// plus two regions.  gpx_svgp_acquire_f64's workspace is described at the end (svgp_acquire_layout).  No HIP in here:
+// tests/host/svgp_layout_check.cpp
 // compiles this file alone with the host compiler and checks it against a second statement of the layout.
 #pragma once
 #include <cstddef>
@@ -158,5 +159,44 @@ struct SvgpWorkspace {
   int64_t pitch() const { return (int64_t)(L.task / sizeof(double)); }          // doubles between the tasks' blocks
   int64_t phi_pitch() const { return (int64_t)(L.phi_task / sizeof(double)); }  // and between their projected chunks
 };
+
+// gpx_svgp_acquire_f64's workspace: the sweep's (sweep_layout of the padded M and one right-hand side: the
+// chunk's K*, the mean partials and the first product's variance partials, the block records the scoring launch
+// writes; its pruned part is carried unused, so a buffer of this call's size serves gpx_svgp_predict_f64 too), and
+// behind its total the call's own regions, each 256-aligned.  The offsets count from the same 256-aligned base as the
+// sweep's, so none depends on the caller's pointer.  tests/host/svgp_acquire_layout_check.cpp checks it against a
+// second statement.
+enum SvgpAcquireRegion {
+  SQ_SS2_PART,  // the second product's variance partials, (Mpad/128) x C doubles
+  SQ_ACC_MU,    // the chunk's objective mean and variance over the tasks, C doubles each
+  SQ_ACC_VAR,
+  SQ_SCORES,    // the m scores where the caller passes scores_out = NULL
+  SQ_SORT_WS,   // the selection's scratch (topk_workspace_bytes)
+  SQ_REGIONS
+};
+struct SvgpAcquireLayout {
+  SweepLayout sweep;  // SR_KSTAR, SR_MU_PART, SR_SS_PART, SR_REC_VAL, SR_REC_IDX are this call's
+  SweepLayout::Region r[SQ_REGIONS];
+  size_t total = 0;   // gpx_svgp_acquire_workspace_size
+};
+// sort_bytes: topk_workspace_bytes(m), which only the HIP side knows
+inline SvgpAcquireLayout svgp_acquire_layout(int64_t Mpad, int64_t m, size_t sort_bytes) {
+  SvgpAcquireLayout A;
+  A.sweep = sweep_layout(Mpad, 1, m);
+  size_t at = up256(A.sweep.total), reported = at + 256;  // (one more alignment step)
+  auto take = [&](SvgpAcquireRegion id, size_t bytes) {
+    A.r[id].at = at;
+    A.r[id].bytes = bytes;
+    at += bytes;
+    reported += bytes;
+  };
+  take(SQ_SS2_PART, up256((size_t)(Mpad / TT) * A.sweep.C * 8));
+  take(SQ_ACC_MU, up256((size_t)A.sweep.C * 8));
+  take(SQ_ACC_VAR, up256((size_t)A.sweep.C * 8));
+  take(SQ_SCORES, up256((size_t)m * 8));
+  take(SQ_SORT_WS, up256(sort_bytes));
+  A.total = reported;
+  return A;
+}
 
 }  // namespace gpx

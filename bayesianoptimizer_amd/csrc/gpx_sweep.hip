@@ -2407,11 +2407,44 @@ __global__ void __launch_bounds__(WG) svgp_finalize_kernel(gpx_kernel_params p, 
   if (score) score[c] = (task == 0 ? 0.0 : score[c]) + var;
 }
 
+// One task of gpx_svgp_acquire_f64's objective in svgp_finalize_kernel's place: the task's LATENT moments from the same
+// partials in the same operation order (no likelihood noise: an analytic acquisition is about f; GPyTorch's 1e-10
+// floor), untransformed and weighted into the chunk's accumulators exactly as finalize_kernel's mode 2 does it.  Mode 3
+// scores them (launch_multi_score): objective_moments and acq_score stay the only statements of the floors and formulas.
+__global__ void __launch_bounds__(WG) svgp_objective_kernel(gpx_kernel_params p, MultiOutput mo,
+                                                            const double* __restrict__ Xs, int64_t ldxs,
+                                                            int64_t m_chunk, int64_t C, int nJB, int nI,
+                                                            const double* __restrict__ mu_part,
+                                                            const double* __restrict__ ss1,
+                                                            const double* __restrict__ ss2) {
+  const int64_t c = (int64_t)blockIdx.x * WG + threadIdx.x;
+  if (c >= m_chunk) return;
+  double kd = p.outputscale;
+  if (p.kind == GPX_KERNEL_SCALE_LINEAR_MATERN52) {
+    double lv = 0.0;
+    for (int k = 0; k < p.d; ++k) {
+      const double v = Xs[c * ldxs + k];
+      lv += v * v * p.linear_variance[k];
+    }
+    kd = p.outputscale * (lv + 1.0);
+  }
+  const double s1 = sum_partials(ss1 + c, nI, C);
+  const double s2 = sum_partials(ss2 + c, nI, C);
+  double var = fmax(kd - s1 + s2, 1e-10);  // gpytorch min_variance (float64) [upstream]
+  double mu = sum_partials(mu_part + c, nJB, C) + p.const_mean;
+  mu = mo.y_mean + mo.y_scale * mu;
+  var = var * (mo.y_scale * mo.y_scale);
+  const double wm = mo.weight * mu, wv = (mo.weight * mo.weight) * var;
+  mo.acc_mu[c] = mo.first ? wm : mo.acc_mu[c] + wm;
+  mo.acc_var[c] = mo.first ? wv : mo.acc_var[c] + wv;
+}
+
+// (mo: gpx_svgp_acquire_f64's form; min_var, task and the output pointers are then not used)
 hipError_t launch_svgp_chunk(Context* c, const gpx_kernel_params& p, double min_var, int task, int M, int Mpad,
                              const double* Z, int64_t ldz, const double* W, const double* W2, int64_t ldw,
                              const double* alpha, const double* Xs, int64_t ldxs, int64_t m_chunk,
                              const SweepBuffers& b, double* ss2, double* mean_out, int64_t ldmean, double* var_out,
-                             int64_t ldvar, double* score) {
+                             int64_t ldvar, double* score, const MultiOutput* mo) {
   const int64_t C = b.chunk;
   const int nJB = Mpad / NB, nI = Mpad / TT;
   const int ncb = (int)((m_chunk + WG - 1) / WG);
@@ -2432,8 +2465,12 @@ hipError_t launch_svgp_chunk(Context* c, const gpx_kernel_params& p, double min_
   }
   {
     LaunchTimer tm(c, GPX_TIMER_ACQ);
-    svgp_finalize_kernel<<<ncb, WG, 0, c->stream>>>(p, min_var, task, Xs, ldxs, m_chunk, C, nJB, nI, b.mu_part,
-                                                    b.ss_part, ss2, mean_out, ldmean, var_out, ldvar, score);
+    if (mo)
+      svgp_objective_kernel<<<ncb, WG, 0, c->stream>>>(p, *mo, Xs, ldxs, m_chunk, C, nJB, nI, b.mu_part, b.ss_part,
+                                                       ss2);
+    else
+      svgp_finalize_kernel<<<ncb, WG, 0, c->stream>>>(p, min_var, task, Xs, ldxs, m_chunk, C, nJB, nI, b.mu_part,
+                                                      b.ss_part, ss2, mean_out, ldmean, var_out, ldvar, score);
   }
   return hipGetLastError();
 }

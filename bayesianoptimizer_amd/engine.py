@@ -1072,6 +1072,51 @@ class GPEngine:
             _ptr(ws), ws.numel()))
         return mean, var, score
 
+    def svgp_acquire(self, prep: dict, Xs, k: int, kind: Union[str, int] = "logei", best_f: float = 0.0,
+                     beta: float = 4.0, weights: Optional[Sequence[float]] = None,
+                     y_mean: Optional[Sequence[float]] = None, y_scale: Optional[Sequence[float]] = None,
+                     index_offset: int = 0, return_scores: bool = False):
+        """The analytic acquisition sweep on a prepared SVGP (gpx_svgp_acquire_f64): the linear objective
+        sum_t w_t (y_mean_t + y_scale_t f_t) over the T tasks' LATENT posteriors (no likelihood noise), scored like
+        ``acquire_multi``, and the k best candidates as device tensors (values[k], indices[k]) in ``topk``'s order
+        (+ the m raw scores with ``return_scores``).  Every candidate is scored in full; ``sweep_stats()`` does not
+        report for it."""
+        Xs = self._as_f64(Xs, "Xs")
+        Z = prep["Z"]
+        T, M, d = Z.shape
+        if Xs.shape[1] != d:
+            raise ValueError(f"Xs has {Xs.shape[1]} columns, model has d={d}")
+        m = Xs.shape[0]
+        if m == 0:
+            raise ValueError("empty candidate set")
+        k = int(k)
+        w = [1.0] * T if weights is None else [float(v) for v in weights]
+        if len(w) != T:
+            raise ValueError(f"expected {T} objective weights, got {len(w)}")
+        ym = [0.0] * T if y_mean is None else [float(v) for v in y_mean]
+        ys = [1.0] * T if y_scale is None else [float(v) for v in y_scale]
+        if len(ym) != T or len(ys) != T:
+            raise ValueError(f"expected {T} y_mean / y_scale entries")
+        kid = ACQ_KINDS[kind.lower()] if isinstance(kind, str) else int(kind)
+        ap = AcqParamsC()
+        ap.kind, ap.best_f, ap.beta, ap.y_mean, ap.y_scale = kid, float(best_f), float(beta), 0.0, 1.0
+        pcs = (KernelParamsC * T)(*[pp.to_c(d) for pp in prep["params"]])
+        nbytes = ctypes.c_size_t()
+        self._check(self.lib.gpx_svgp_acquire_workspace_size(M, m, k, ctypes.byref(nbytes)))
+        val = torch.empty((k,), dtype=torch.float64, device=self.device)
+        idx = torch.empty((k,), dtype=torch.int64, device=self.device)
+        scores = torch.empty((m,), dtype=torch.float64, device=self.device) if return_scores else None
+        ws = self.workspace("svgp_acq", nbytes.value)
+        self._bind_stream()
+        self._check(self.lib.gpx_svgp_acquire_f64(
+            self.handle, pcs, T, M, _ptr(Z), Z.stride(1), Z.stride(0), _ptr(prep["W"]), _ptr(prep["W2"]),
+            _ptr(prep["alpha"]), (ctypes.c_double * T)(*w), (ctypes.c_double * T)(*ym), (ctypes.c_double * T)(*ys),
+            _ptr(Xs), m, Xs.stride(0), ctypes.byref(ap), int(index_offset), k, _ptr(val), _ptr(idx), _ptr(scores),
+            _ptr(ws), ws.numel()))
+        if return_scores:
+            return val, idx, scores
+        return val, idx
+
     def svgp_moments_grad(self, prep: dict, task: int, Xs, q: int = 1, need_grad: bool = True):
         """``moments_grad`` for task ``task`` of a prepared SVGP (gpx_svgp_moments_grad_f64): the latent posterior mean
         (m) and q-batch covariance (m x q) of candidates Xs (m x d, consecutive q-batches) with their derivatives

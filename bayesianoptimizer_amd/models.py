@@ -334,7 +334,8 @@ class SparseGP:
     """The large-n sparse surrogate of the drop-in (GPConfig.large_n_model = "sparse"): a batched SVGP whose
     variational distribution is the closed-form optimum for the given hyperparameters and inducing points
     (SVGPModel.fit_collapsed), served by an SVGPPredictor.  ``posterior`` is the likelihood-wrapped predictive, as
-    the reference reads it (optimization/Bayesian7.py:558,668).  Memory is O(T M^2), independent of n."""
+    the reference reads it (optimization/Bayesian7.py:558,668); ``sweep_objective`` / ``sweep_objective_topk`` score
+    the LATENT posterior, as the analytic acquisitions of an ExactGP do.  Memory is O(T M^2), independent of n."""
 
     independent = True
 
@@ -366,6 +367,30 @@ class SparseGP:
     def _untransform(self):
         return None, None  # the SVGP is fitted to the outcomes as they are given
 
+    fitted = True  # (fitted at construction; what _Analytic.sweep asks an ExactGP)
+
+    def _weights(self, weights) -> List[float]:
+        w = [float(v) for v in weights]
+        if len(w) != self.num_outputs:
+            raise ValueError(f"expected {self.num_outputs} objective weights, got {len(w)}")
+        return w
+
+    def sweep_objective(self, X, kind: str, weights: Sequence[float], best_f: float = 0.0, beta: float = 4.0,
+                        index_offset: int = 0, return_scores: bool = False):
+        """``ExactGP.sweep_objective`` on the sparse model: the linear objective sum_t w_t f_t over the outputs' LATENT
+        posteriors (no likelihood noise, unlike ``posterior``) scored over input-transformed candidates X and reduced
+        to (best value, lowest index among ties) (+ scores): ``GPEngine.svgp_acquire`` with k = 1."""
+        return self.engine.svgp_acquire(self.predictor.prep, X, 1, kind, best_f=best_f, beta=beta,
+                                        weights=self._weights(weights), index_offset=index_offset,
+                                        return_scores=return_scores)
+
+    def sweep_objective_topk(self, X, kind: str, weights: Sequence[float], k: int, best_f: float = 0.0,
+                             beta: float = 4.0, index_offset: int = 0):
+        """``ExactGP.sweep_objective_topk`` on the sparse model: the k best candidates of ``sweep_objective`` as
+        (values[k], indices[k]), descending, ties -> lower index first (one ``GPEngine.svgp_acquire``)."""
+        return self.engine.svgp_acquire(self.predictor.prep, X, int(k), kind, best_f=best_f, beta=beta,
+                                        weights=self._weights(weights), index_offset=index_offset)
+
 
 class _Analytic:
     kind = "logei"
@@ -380,13 +405,18 @@ class _Analytic:
 
     def sweep(self, X, index_offset: int = 0, return_scores: bool = False):
         """Score candidates X on output ``output`` (or on the linear objective ``weights`` over all outputs, in
-        untransformed units: ExactGP.sweep_objective) and reduce to (value, lowest index) on the device."""
+        untransformed units: ExactGP.sweep_objective) and reduce to (value, lowest index) on the device.  The model
+        may be a SparseGP: its latent posterior through SparseGP.sweep_objective."""
         m = self.model
         if not m.fitted:
             m.fit()
         if self.weights is not None:
             return m.sweep_objective(X, self.kind, self.weights, best_f=self.best_f, beta=self.beta,
                                      index_offset=index_offset, return_scores=return_scores)
+        if isinstance(m, SparseGP):  # a one-hot weight on `output`: the sparse sweep has the objective form only
+            w = [1.0 if t == self.output else 0.0 for t in range(m.num_outputs)]
+            return m.sweep_objective(X, self.kind, w, best_f=self.best_f, beta=self.beta, index_offset=index_offset,
+                                     return_scores=return_scores)
         ym, ys = m._untransform()
         t = self.output
         if m.independent:

@@ -19,7 +19,8 @@ hyperparameters are tied), in which case new observations are folded in by the b
 distribution in closed form for the fitted hyperparameters (``SVGPModel.fit_collapsed``, ``models.SparseGP``), serving
 ``predict``, ``evaluate_model``, the pool scan and, through its q-batch moments (``gpx_svgp_moments_grad_f64``),
 ``"qpsd"`` (Bayesian6's large-n mode, ``Bayesian6.py:492-577,896-919``) and ``"qlogei"`` up to ``GPX_MAX_Q`` points per
-round; the other modes raise on it.  Acquisition modes (``acquisition=``):
+round, and with ``GPConfig.sparse_analytic`` the analytic sweeps ``"ei" | "logei" | "ucb"`` on its latent posterior
+(``gpx_svgp_acquire_f64``); the other modes raise on it.  Acquisition modes (``acquisition=``):
 
 * ``"variance"`` (default, Bayesian7's pool scan ``:646-688``): Latin-hypercube pool -> summed posterior variance on
   the device -> top-K on the device (``gpx_topk_f64``, deterministic ties) -> farthest-point sampling on the device
@@ -59,6 +60,8 @@ INPUT_COLUMNS = ("n", "eta", "sigma_y", "width", "height")  # simulator paramete
 # what the sparse surrogate (GPConfig.large_n_model = "sparse") serves: the pool scan, and optimize_acqf on the MC
 # acquisitions that need only q-batch moments (gpx_svgp_moments_grad_f64)
 SPARSE_ACQUISITIONS = ("variance", "qpsd", "qlogei")
+# and, with GPConfig.sparse_analytic, the analytic sweeps (gpx_svgp_acquire_f64)
+SPARSE_ANALYTIC_ACQUISITIONS = ("ei", "logei", "ucb")
 
 
 @dataclass
@@ -108,7 +111,8 @@ class GPConfig:
     # the hyperparameters (SVGPModel.fit_collapsed), refitted every round in O(n M^2) time and O(T M^2) memory.  The
     # hyperparameters come as in the exact mode (subsample marginal likelihood, or the fixed values).  The sparse
     # surrogate serves acquisition="variance" (the reference's pool scan), "qpsd" (Bayesian6's acquisition on its
-    # per-output SVGPs) and "qlogei" (at most GPX_MAX_Q points per round: it has no kriging believer).
+    # per-output SVGPs) and "qlogei" (at most GPX_MAX_Q points per round: it has no kriging believer); with
+    # sparse_analytic (below) also "ei", "logei" and "ucb".
     large_n_model: str = "exact"
     # where the sparse model's hyperparameters come from (with fit_hyperparameters): "subsample", the exact marginal
     # likelihood on the svgp_threshold-point subsample (above), or "bound": the collapsed bound of the sparse model
@@ -120,6 +124,10 @@ class GPConfig:
     # moved together with the hyperparameters to maximise the bound, every output its own copy (the reference's
     # learn_inducing_locations=True, Bayesian7.py:152).  "learned" needs sparse_hyperparameters = "bound".
     sparse_inducing: str = "fixed"
+    # True: the sparse surrogate also serves the analytic sweeps "ei", "logei" and "ucb" on its latent posterior (the
+    # Sobol grid of the exact modes through SparseGP.sweep_objective_topk, gpx_svgp_acquire_f64).  Off by default: the
+    # constructor and acquire() then refuse them, as they did before the sweep existed.
+    sparse_analytic: bool = False
     max_inducing_points: int = 2048
     inducing_subset_size: int = 10000
     # acquisition="qlogei": optimize_acqf settings of optimization/Bayesian.py:100-112
@@ -249,9 +257,9 @@ class BayesianOptimizer:
         if self.config.sparse_inducing == "learned" and self.config.sparse_hyperparameters != "bound":
             raise ValueError("GPConfig.sparse_inducing='learned' requires sparse_hyperparameters='bound': the inducing "
                              "points are learned by maximising the collapsed bound")
-        if self._sparse_policy() and self.acquisition not in SPARSE_ACQUISITIONS:
+        if self._sparse_policy() and self.acquisition not in self._sparse_acquisitions():
             raise ValueError(f"acquisition '{self.acquisition}' is not available with GPConfig.large_n_model='sparse': "
-                             "the sparse surrogate serves acquisition='variance' (the pool scan) only")
+                             f"{self._sparse_serves()}")
         self.seed = kwargs.get("seed", None)
         self._rng = np.random.default_rng(self.seed)
         # the large-n policy's hyperparameter subsamples draw from their own stream (never shift the candidate draws)
@@ -325,6 +333,15 @@ class BayesianOptimizer:
 
     def _sparse_policy(self) -> bool:
         return bool(self.config.large_n_policy) and self.config.large_n_model == "sparse"
+
+    def _sparse_acquisitions(self):
+        return SPARSE_ACQUISITIONS + (SPARSE_ANALYTIC_ACQUISITIONS if self.config.sparse_analytic else ())
+
+    def _sparse_serves(self) -> str:
+        """What the sparse surrogate serves, for the messages that refuse the rest."""
+        names = lambda acqs: ", ".join(f"'{a}'" for a in acqs)  # noqa: E731
+        return (f"the sparse surrogate serves acquisition = {names(SPARSE_ACQUISITIONS)}, and with "
+                f"GPConfig.sparse_analytic=True the analytic sweeps {names(SPARSE_ANALYTIC_ACQUISITIONS)}")
 
     def fit_gp_model(self):
         """Log-standardise (Bayesian7.py:363-385) and build the exact posterior for all outputs on the engine.
@@ -561,9 +578,9 @@ class BayesianOptimizer:
             return torch.empty((0, self.dim), dtype=self.dtype, device=self.gp_device)
         if self.acquisition == "variance":
             return self._pool_scan(k)
-        if isinstance(self.gp_model, SparseGP) and self.acquisition not in SPARSE_ACQUISITIONS:
+        if isinstance(self.gp_model, SparseGP) and self.acquisition not in self._sparse_acquisitions():
             raise ValueError(f"acquisition '{self.acquisition}' is not available on the sparse surrogate "
-                             "(GPConfig.large_n_model='sparse' serves acquisition='variance' only)")
+                             f"(GPConfig.large_n_model='sparse'): {self._sparse_serves()}")
         if self.acquisition == "qlogei":
             return self._acquire_qlogei(k)
         if self.acquisition == "qpsd":
@@ -599,7 +616,8 @@ class BayesianOptimizer:
         """Sobol grid scored on the objective sum_t w_t f_t of the modelled outputs (ExactGP.sweep_objective: the
         combined alpha of one shared factorisation, or the multi-output sweep over independent outputs), best k by
         ExactGP.sweep_objective_topk: the pruned top-k sweep (gpx_acquire_topk_f64 for a shared factorisation,
-        gpx_acquire_topk_multi_f64 over independent outputs), else the full sweep and gpx_topk_f64."""
+        gpx_acquire_topk_multi_f64 over independent outputs), else the full sweep and gpx_topk_f64.  A SparseGP
+        (GPConfig.sparse_analytic) answers the same call from its latent posterior (gpx_svgp_acquire_f64)."""
         gp = self.gp_model
         grid = self._tensor(self._sobol_grid(self.config.raw_samples))
         w = self._acq_weights()

@@ -602,6 +602,42 @@ gpx_status gpx_svgp_predict_f64(gpx_handle h, const gpx_kernel_params* p, int64_
                                 int64_t ldmean, double* var_out, int64_t ldvar, double* score_out, void* ws,
                                 size_t ws_bytes);
 
+/* Analytic acquisition sweep on a prepared SVGP: gpx_acquire_argmax_multi_f64 / gpx_acquire_topk_multi_f64 for the
+ * sparse model, a LINEAR OBJECTIVE f = sum_t w_t (y_mean[t] + y_scale[t] g_t) over its ntask independent tasks.  Z,
+ * ldz, stride_z, W, W2, alpha: as gpx_svgp_predict_f64 (the blocks of gpx_svgp_prepare_f64).  Per task t and candidate
+ * x, with k* = K(Z_t, x):
+ *   mu_t = const_mean_t + k*^T alpha'_t,   var_t = max((k_t(x, x) - |W_t^T k*|^2) + |W2_t^T k*|^2, 1e-10)
+ * var_t is the LATENT variance (no likelihood noise: an analytic acquisition is about f, as gpx_svgp_moments_grad_f64
+ * has it; p[t].noise is not read), in gpx_svgp_predict_f64's operation order; S S^T <= I is not assumed.  Then
+ *   mean = sum_t w_t (y_mean[t] + y_scale[t] mu_t),   variance = max(sum_t w_t^2 y_scale[t]^2 var_t, 1e-12)
+ * (tasks summed in ascending order, the first one starting the sum: gpx_acquire_argmax_multi_f64's arithmetic and
+ * floors) and score = a's kind / best_f / beta of (mean, variance); a->y_mean and a->y_scale are not used.
+ * weights_host: ntask finite host doubles; y_mean_host / y_scale_host: ntask host doubles or NULL = 0 / 1.
+ * scores_out (device, m; NULL = skip) gets the raw scores, a NaN staying a NaN.  val_out / idx_out (device, k each) are
+ * what gpx_topk_f64 of those scores gives: descending, equal scores with the lower index first, NaN keyed as -inf and
+ * -0 as +0, the indices shifted by index_offset; k = 1 is the argmax pair.  A candidate's score does not depend on m,
+ * on its row, on index_offset or on k.  Two bit identities follow from sharing the predictive's launches: VARIANCE with
+ * w_t = 1 and no untransform equals gpx_svgp_predict_f64's score_out of the same model with every noise = 0 and
+ * min_var = 1e-10; ntask = 1, w = 1, UCB with beta = 0 equals its mean_out.
+ * Validation as gpx_svgp_predict_f64 (the model, ldz, stride_z, ldxs) and gpx_acquire_argmax_multi_f64 (a, beta >= 0,
+ * index_offset >= 0, finite weights, y_scale > 0), plus 1 <= k <= m <= 2^30; a workspace smaller than
+ * gpx_svgp_acquire_workspace_size(M, m, k) is GPX_INVALID_ARG.  Every candidate gets both products in full: the sweep
+ * is not pruned (the second product raises the variance, so the exact sweep's bound does not hold), and
+ * gpx_sweep_stats is NOT defined after this call.  Asynchronous on the handle's stream, deterministic, no allocation,
+ * no host synchronisation.
+ * Workspace: gpx_sweep_workspace_size(M, 1, m) (the K* chunk, the mean partials, the first product's variance
+ * partials, block records), then, each rounded up to 256 bytes: the second product's partials, the chunk's two
+ * objective accumulators, m scores (used when scores_out is NULL) and gpx_topk_workspace_size(m).  It is never smaller
+ * than gpx_svgp_predict_workspace_size(M, m). */
+gpx_status gpx_svgp_acquire_workspace_size(int64_t M, int64_t m, int64_t k, size_t* bytes);
+gpx_status gpx_svgp_acquire_f64(gpx_handle h, const gpx_kernel_params* p, int64_t ntask, int64_t M, const double* Z,
+                                int64_t ldz, int64_t stride_z, const double* W, const double* W2, const double* alpha,
+                                const double* weights_host, const double* y_mean_host, const double* y_scale_host,
+                                const double* Xs, int64_t m, int64_t ldxs, const gpx_acq_params* a,
+                                int64_t index_offset, int64_t k, double* val_out /* k, device */,
+                                int64_t* idx_out /* k, device */, double* scores_out /* m, device, or NULL */,
+                                void* ws, size_t ws_bytes);
+
 /* Posterior moments of m candidates Xs (m x d, consecutive q-batches) under ONE task of a prepared SVGP, and their
  * derivatives w.r.t. the candidates: gpx_moments_grad_f64 for the sparse model (optimize_acqf on the per-output SVGPs of
  * optimization/Bayesian6.py:492-577, 896-919).  p: the task's parameters; Z (M x d): its inducing points; W, W2
