@@ -1098,7 +1098,7 @@ gpx_status gpx_posterior_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n
   for (int64_t s = 0; s < m; s += w.b.chunk) {
     const gpx::SweepCands q{Xs + s * ldxs, ldxs, gpx::sweep_span_size(false, s, m, w.b.chunk, 0), 0};
     const gpx::SweepOut out{nullptr, y_mean_host, y_scale_host, mean_out + s * ldmean, ldmean, var_out + s};
-    GPX_TRY(hip_check(c, gpx::launch_sweep_chunk(M, q, w.b, 0, nullptr, out), "posterior"));
+    GPX_TRY(hip_check(c, gpx::launch_sweep_chunk(M, q, w.b, nullptr, out), "posterior"));
   }
   return GPX_OK;
 }
@@ -1151,7 +1151,7 @@ static gpx_status acquire_impl(gpx_handle h, const gpx_kernel_params* p, int64_t
     const hipError_t e =
         lazy    ? gpx::launch_sweep_super_pruned(M, q, b, w.ps, w.ph, a, &rec, s == 0, c->sweep_stats, tk)
         : prune ? gpx::launch_sweep_chunk_pruned(M, q, b, w.ps, a, rec, s == 0, c->sweep_stats, tk)
-                : gpx::launch_sweep_chunk(M, q, b, 1, a, out, rec);
+                : gpx::launch_sweep_chunk(M, q, b, a, out, rec);
     GPX_TRY(hip_check(c, e, "acquire"));
     if (!lazy) rec += (ms + 255) / 256;  // (the lazy path counts its own: the rounds' blocks)
   }
@@ -1481,7 +1481,7 @@ static gpx_status acquire_multi_impl(gpx_handle h, const gpx_kernel_params* p, i
       mo.y_scale = y_scale_host ? y_scale_host[t] : 1.0;
       mo.first = t == 0;
       const gpx::SweepModel M{c, p[t], (int)n, (int)npad, X, ldx, W_host[t], ldw_host[t], alpha_host[t], 1};
-      GPX_TRY(hip_check(c, gpx::launch_sweep_chunk(M, {Xs + s * ldxs, ldxs, mc, 0}, b, 1, a, gpx::SweepOut(), 0, &mo),
+      GPX_TRY(hip_check(c, gpx::launch_sweep_chunk(M, {Xs + s * ldxs, ldxs, mc, 0}, b, a, gpx::SweepOut(), 0, &mo),
                         "acquire (multi-output)"));
     }
     GPX_TRY(hip_check(c, gpx::launch_multi_score(c, {nullptr, 0, mc, index_offset + s}, mo, *a,
@@ -1739,7 +1739,7 @@ gpx_status gpx_svgp_acquire_f64(gpx_handle h, const gpx_kernel_params* p, int64_
                                                Xs + s * ldxs, ldxs, mc, b, ss2, nullptr, 0, nullptr, 0, nullptr, &mo),
                         "svgp acquire"));
     }
-    // mode 3 of the finalize: the chunk's scores; its block records are not read (the selection below sorts the scores)
+    // the accumulators' score pass: the chunk's scores; its block records are not read (the selection below sorts the scores)
     GPX_TRY(hip_check(c, gpx::launch_multi_score(c, {nullptr, 0, mc, index_offset + s}, mo, *a, scores + s,
                                                  b.rec_val + rec, b.rec_idx + rec),
                       "svgp acquire (score)"));

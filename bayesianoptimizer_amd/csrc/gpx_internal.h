@@ -187,8 +187,8 @@ struct SweepCands {
   int64_t ldxs, m, index_offset;  // (the global index of candidate 0)
   SweepCands first(int64_t count) const { return {Xs, ldxs, count, index_offset}; }  // the leading `count` of them
 };
-// Per-candidate outputs of launch_sweep_chunk: the posterior's (mode 0: y_mean / y_scale per output, nullptr = identity)
-// or the acquisition's optional scores (mode 1).
+// Per-candidate outputs of launch_sweep_chunk: the posterior's (y_mean / y_scale per output, nullptr = identity) or the
+// acquisition's optional scores.
 struct SweepOut {
   double* scores = nullptr;
   const double* y_mean = nullptr;
@@ -197,10 +197,10 @@ struct SweepOut {
   int64_t ldmean = 0;
   double* var = nullptr;
 };
-// mode 0: posterior (write mean/var); mode 1: acquisition (records + optional scores); mo != nullptr: accumulate one
-// output of a multi-output objective instead (mode ignored), scored afterwards by launch_multi_score
-hipError_t launch_sweep_chunk(const SweepModel& M, const SweepCands& q, const SweepBuffers& b, int mode,
-                              const gpx_acq_params* a, const SweepOut& out = SweepOut(), int64_t rec_offset = 0,
+// a = nullptr: posterior (write mean/var); else acquisition (records + optional scores); mo != nullptr: accumulate one
+// output of a multi-output objective instead, scored afterwards by launch_multi_score
+hipError_t launch_sweep_chunk(const SweepModel& M, const SweepCands& q, const SweepBuffers& b, const gpx_acq_params* a,
+                              const SweepOut& out = SweepOut(), int64_t rec_offset = 0,
                               const MultiOutput* mo = nullptr);
 
 // ---- pruned acquisition sweep (gpx_sweep.hip) ----------------------------------------------

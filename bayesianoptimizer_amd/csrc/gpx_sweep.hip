@@ -12,12 +12,14 @@
 //                    kernel of the whole hot path.
 //  3. finalize       mu = m + sum mu_part, var = k** - sum ss_part (fixed summation order: deterministic),
 //                    GPyTorch/BoTorch variance floors, Standardize untransform, analytic acquisition, and a
-//                    256-candidate block argmax record (max value, then lowest index; NaN never wins).
+//                    256-candidate block argmax record (max value, then lowest index; NaN never wins).  One body,
+//                    finalize_kernel<PASS>, compiled per pass (FinalizePass): the posterior, one output into a
+//                    multi-output objective's accumulators, and score or bound from the partials or the accumulators.
 // launch_argmax_final reduces the records of the whole sweep in one workgroup.
 // gpx_acquire_argmax_f64 without scores_out takes the PRUNED form of launch 2 (launch_sweep_chunk_pruned):
 // the row tiles run in stages (trmm_stage_kernel; after the first trmm_stage_dual_kernel, whose workgroups take a
-// 128 x 32 tile when the stage has fewer 128 x 128 tiles than the device has CUs); after each stage finalize_kernel
-// mode 4 drops the candidates whose score bound cannot reach the best score computed in full so far, and
+// 128 x 32 tile when the stage has fewer 128 x 128 tiles than the device has CUs); after each stage finalize_kernel's
+// bound pass drops the candidates whose score bound cannot reach the best score computed in full so far, and
 // prune_compact_kernel gathers the surviving K* columns; the (value, index) pair has the bits of the full sweep.  Where
 // the MFMA K* build applies the pruned form is lazy (launch_sweep_super_pruned): K* rows 0 .. 127 for every candidate,
 // built in registers and multiplied into row tile 0 by one kernel (head_product_kernel; gpx_debug_set_sweep_head 0:
@@ -1070,158 +1072,104 @@ __global__ void __launch_bounds__(WG) sweep_small_kernel(gpx_kernel_params p, in
   }
 }
 
-// ---- 3. finalize: posterior (mode 0) or acquisition + block argmax (mode 1) ------------------------------
+// ---- 3. finalize: the passes over a chunk's columns and the pieces they share --------------------------------------
+// The model and the objective of a finalize pass.
 struct FinalizeArgs {
   gpx_kernel_params p;
   double y_mean[GPX_MAX_RHS];
   double y_scale[GPX_MAX_RHS];
   int acq_kind;
   double best_f, beta;
-  // modes 2 / 3: a linear objective sum_t w_t f_t over T independent GPs (gpx_acquire_argmax_multi_f64)
-  double weight;     // mode 2: w_t of this output
-  int first;         // mode 2: the first output of the chunk (overwrites the accumulators)
+  // a linear objective sum_t w_t f_t over T independent GPs (gpx_acquire_argmax_multi_f64)
+  double weight;     // FIN_ACCUMULATE: w_t of this output
+  int first;         // FIN_ACCUMULATE: the first output of the chunk (overwrites the accumulators)
   double* acc_mu;    // sum_t w_t (y_mean_t + y_scale_t mu_t)                 (chunk-sized)
   double* acc_var;   // sum_t w_t^2 y_scale_t^2 max(k** - |v_t|^2, 1e-10)      (chunk-sized)
 };
 
-// The pruned sweep's view of a finalize launch (all nullptr: the plain sweep).  desc: thread t is slot t of the active
-// column set instead of chunk column t.  tau: mode 1 raises the incumbent to its block's best score.  Mode 4 appends
-// the survivors to the list that *desc does not use and counts them in *count.
-struct PruneSel {
+// What a pass reads and writes, one group per concern; a launch site sets the groups its pass has (launch_finalize).
+struct Partials {  // the chunk's partial sums: mu_part[(jb * nrhs + q) * C + c], ss_part[I * C + c]
+  const double* mu_part;
+  const double* ss_part;
+  int64_t C;
+  int nJB, nI, nrhs;  // (a bound pass: nI row tiles done so far)
+};
+// The pruned sweep's active column set (desc = nullptr: thread t is chunk column t < q.m): thread t is slot t of *desc.
+// A bound pass appends its survivors to the list that *desc does not use.
+struct ColumnSet {
   const PruneDesc* desc;
   int2* list0;
   int2* list1;
-  int* count;
-  unsigned long long* tau;
   const int2* list2;  // read only (PruneDesc::list = 2); its survivors go to list0
-  const double* mu_bound;  // mode 4, the lazy head's pass: mu_approx at [c], mu_slack at [C + c] (mu_bound_kernel) stand
-                           // in for the mean partials
-  // the top-k form (gpx_acquire_topk_f64; null everywhere else): mode 1 appends every valid candidate's (score, global
-  // index) to the scored list and leaves the incumbent alone (tau = nullptr): topk_pool_kernel sets it
+};
+struct PosteriorOut {  // FIN_POSTERIOR
+  double* mean;
+  int64_t ldmean;
+  double* var;
+};
+struct ScoreOut {  // the score passes: one (value, index) record per workgroup
+  double* rec_val;
+  int64_t* rec_idx;
+  double* scores;           // optional: every column's score
+  unsigned long long* tau;  // optional: the incumbent, raised to the workgroup's best score (the argmax form)
+  // the top-k form (gpx_acquire_topk_f64; null everywhere else): every valid candidate's (score, global index) is
+  // appended to the scored list and the incumbent left alone (tau = nullptr): topk_pool_kernel sets it
   double* sc_val;
   int64_t* sc_idx;
   int* sc_count;
-  // mode 4 without an incumbent (the seeded order's bound pass): the bound of column c goes to u_out[c], nothing is
-  // selected; seed_select_kernel and seed_prune_kernel read it
-  double* u_out;
 };
-constexpr double PRUNE_EPS = 1e-9;  // margin of the bound test over acq_score's rounding
+struct BoundSel {  // the bound passes
+  int* count;                     // survivors appended so far
+  const unsigned long long* tau;  // the incumbent's key
+  const double* mu_bound;  // the lazy head's pass: mu_approx at [c], mu_slack at [C + c] (mu_bound_kernel) stand in for
+                           // the mean partials
+  double* u_out;  // no incumbent yet (the seeded order's bound pass): the bound of column c goes to u_out[c], nothing
+                  // is selected; seed_select_kernel and seed_prune_kernel read it
+};
+struct FinalizeIo {
+  SweepCands q;  // the candidates: index_offset + c is column c's global index
+  Partials part;
+  ColumnSet cols;
+  PosteriorOut post;
+  ScoreOut score;
+  BoundSel bound;
+};
 
-// The accumulated objective's moments at column c (what mode 2 summed over the outputs), BoTorch's floor on the scored
-// variance: mode 3's operands, and the bound pass's of the multi-output top-k form (multi_bound_select_kernel).
-__device__ __forceinline__ void objective_moments(const FinalizeArgs& fa, int64_t c, double& mu, double& var) {
-  mu = fa.acc_mu[c];
-  var = fmax(fa.acc_var[c], 1e-12);
+// Prior variance k(x, x) of column c.
+__device__ __forceinline__ double prior_variance(const gpx_kernel_params& p, const double* __restrict__ Xs,
+                                                 int64_t ldxs, int64_t c) {
+  if (p.kind != GPX_KERNEL_SCALE_LINEAR_MATERN52) return p.outputscale;
+  double lv = 0.0;
+  for (int k = 0; k < p.d; ++k) {
+    const double v = Xs[c * ldxs + k];
+    lv += v * v * p.linear_variance[k];
+  }
+  return p.outputscale * (lv + 1.0);
 }
 
-// mode 0: posterior (mean / variance out); 1: acquisition + 256-candidate block argmax; 2: one output of a multi-output
-// objective into the accumulators; 3: acquisition + block argmax of the accumulated objective (no partials read);
-// 4: bound and select of the pruned sweep: mode 1's score from the first nI row tiles' partials only, an upper bound of
-// the candidate's score (the variance can only shrink with further tiles, and every acquisition grows with it), and the
-// candidate survives unless the bound lies below the incumbent by more than the margin (a NaN bound survives).
-// Variance floors: GPyTorch's 1e-10 per output in the standardised space, BoTorch's 1e-12 on the scored variance
-// [upstream] (T = 1, w = 1: modes 2 + 3 give mode 1's value bit for bit).
-__global__ void __launch_bounds__(WG) finalize_kernel(FinalizeArgs fa, int mode, const double* __restrict__ Xs,
-                                                      int64_t ldxs, int64_t m_chunk, int64_t C, int nrhs, int nJB,
-                                                      int nI, const double* __restrict__ mu_part,
-                                                      const double* __restrict__ ss_part,
-                                                      double* __restrict__ mean_out, int64_t ldmean,
-                                                      double* __restrict__ var_out, double* __restrict__ scores_out,
-                                                      double* __restrict__ rec_val, int64_t* __restrict__ rec_idx,
-                                                      int64_t index_base, PruneSel ps) {
-  const gpx_kernel_params& p = fa.p;
-  const int64_t t = (int64_t)blockIdx.x * WG + threadIdx.x;
-  int64_t c = t;
-  bool valid = t < m_chunk;
-  int2* survivors = nullptr;
-  if (ps.desc) {
-    const PruneDesc d = *ps.desc;
-    if (mode == 4 && (int64_t)blockIdx.x * WG >= d.ncols) return;
-    valid = t < d.ncols;
-    c = !valid ? 0 : d.list < 0 ? d.col0 + t : (d.list == 2 ? ps.list2 : d.list ? ps.list1 : ps.list0)[t].x;
-    survivors = d.list == 0 ? ps.list1 : ps.list0;
-  }
-  double score = -INFINITY;
-  if (valid) {
-    double mu, var;
-    if (mode == 3) {
-      objective_moments(fa, c, mu, var);
-    } else {
-      // prior variance k(x, x)
-      double kd = p.outputscale;
-      if (p.kind == GPX_KERNEL_SCALE_LINEAR_MATERN52) {
-        double lv = 0.0;
-        for (int k = 0; k < p.d; ++k) {
-          const double v = Xs[c * ldxs + k];
-          lv += v * v * p.linear_variance[k];
-        }
-        kd = p.outputscale * (lv + 1.0);
-      }
-      const double ss = sum_partials(ss_part + c, nI, C);
-      var = fmax(kd - ss, 1e-10);  // gpytorch min_variance (float64) [upstream]
-      if (mode == 0) {
-        for (int q = 0; q < nrhs; ++q) {
-          double mq = sum_partials(mu_part + (int64_t)q * C + c, nJB, (int64_t)nrhs * C);
-          mq += p.const_mean;
-          mean_out[c * ldmean + q] = fa.y_mean[q] + fa.y_scale[q] * mq;
-        }
-        var_out[c] = fmax(var * (fa.y_scale[0] * fa.y_scale[0]), 1e-12);  // BoTorch min_var [upstream]
-        return;
-      }
-      // (mode 4 with a mean bound: the score is non-decreasing in the mean too, so its upper end bounds the score)
-      mu = (mode == 4 && ps.mu_bound) ? ps.mu_bound[c] + ps.mu_bound[C + c] : sum_partials(mu_part + c, nJB, C);
-      mu = fa.y_mean[0] + fa.y_scale[0] * (mu + p.const_mean);
-      var = var * (fa.y_scale[0] * fa.y_scale[0]);
-      if (mode == 2) {
-        const double wm = fa.weight * mu, wv = (fa.weight * fa.weight) * var;
-        fa.acc_mu[c] = fa.first ? wm : fa.acc_mu[c] + wm;
-        fa.acc_var[c] = fa.first ? wv : fa.acc_var[c] + wv;
-        return;
-      }
-      var = fmax(var, 1e-12);
-    }
-    score = acq_score(fa.acq_kind, mu, var, fa.best_f, fa.beta);
-    if (scores_out) scores_out[c] = score;
-    if (score != score && mode != 4) score = -INFINITY;
-  }
-  if (mode == 0 || mode == 2) return;
-  if (mode == 4 && ps.u_out) {
-    if (valid) ps.u_out[c] = score;
-    return;
-  }
-  if (mode == 4) {
-    // survivors as a compact list: one ballot and one atomic add per wave; the slot order may vary from run to run,
-    // no result depends on it
-    const double tau = tau_value(*ps.tau);
-    const bool keep = valid && !(score + PRUNE_EPS * (fabs(score) + fabs(tau) + 1.0) < tau);
-    const unsigned long long mask = __ballot(keep);
-    if (mask == 0) return;
-    const int lane = threadIdx.x & 63;
-    int base = 0;
-    if (lane == 0) base = atomicAdd(ps.count, __popcll(mask));
-    base = __shfl(base, 0);
-    if (keep) survivors[base + __popcll(mask & ((1ull << lane) - 1))] = make_int2((int)c, (int)t);
-    return;
-  }
-  if (ps.sc_count) {
-    // the top-k form's scored list, as mode 4's survivors: one ballot and one atomic add per wave, any slot order.  The
-    // value is gpx_topk_f64's key of the score (NaN is -inf already, -0 becomes +0)
-    const unsigned long long mask = __ballot(valid);
-    if (mask != 0) {
-      const int lane = threadIdx.x & 63;
-      int base = 0;
-      if (lane == 0) base = atomicAdd(ps.sc_count, __popcll(mask));
-      base = __shfl(base, 0);
-      if (valid) {
-        const int slot = base + __popcll(mask & ((1ull << lane) - 1));
-        ps.sc_val[slot] = score + 0.0;
-        ps.sc_idx[slot] = index_base + c;
-      }
-    }
-  }
-  // block argmax
-  double bv = score;
-  int64_t bi = valid ? index_base + c : INT64_MAX;
+// The bound test of the pruned sweep: a candidate whose score bound is `score` survives unless the bound lies below the
+// incumbent by more than the margin of acq_score's rounding.  A NaN bound survives.
+constexpr double PRUNE_EPS = 1e-9;
+__device__ __forceinline__ bool bound_keeps(double score, double tau) {
+  return !(score + PRUNE_EPS * (fabs(score) + fabs(tau) + 1.0) < tau);
+}
+
+// A compact list fed by whole waves: the slot of a lane with `pred` (other lanes: no meaning).  One ballot and one
+// atomic add per wave, none for a wave without such a lane; the slot order may vary from run to run, no result depends
+// on it.
+__device__ __forceinline__ int wave_append(bool pred, int* __restrict__ count) {
+  const unsigned long long mask = __ballot(pred);
+  if (mask == 0) return 0;
+  const int lane = threadIdx.x & 63;
+  int base = 0;
+  if (lane == 0) base = atomicAdd(count, __popcll(mask));
+  base = __shfl(base, 0);
+  return base + __popcll(mask & ((1ull << lane) - 1));
+}
+
+// The argmax of a 256-thread workgroup's (bv, bi) pairs, on thread 0 (argmax_merge: max value, then lowest index).  One
+// __syncthreads, which every thread of the workgroup must reach.
+__device__ __forceinline__ void block_argmax(double& bv, int64_t& bi) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const double v2 = __shfl_xor(bv, o);
@@ -1236,42 +1184,120 @@ __global__ void __launch_bounds__(WG) finalize_kernel(FinalizeArgs fa, int mode,
     wi[w] = bi;
   }
   __syncthreads();
-  if (threadIdx.x == 0) {
+  if (threadIdx.x == 0)
     for (int q = 1; q < 4; ++q) argmax_merge(bv, bi, wv[q], wi[q]);
-    rec_val[blockIdx.x] = bv;
-    rec_idx[blockIdx.x] = bi;
-    if (ps.tau) atomicMax(ps.tau, tau_key(bv));
-  }
 }
 
-// Bound and select of the multi-output top-k form (gpx_acquire_topk_multi_f64): after the head phase the accumulators
-// hold the exact objective mean and, from the first row tile of every output, an upper bound of its variance, so mode
-// 3's score of them bounds the candidate's exact score (every acquisition is non-decreasing in the variance).  Slot t
-// of *desc (chunk column col0 + t) survives unless the bound lies below the incumbent by more than the margin, as in
-// mode 4 (a NaN bound survives): one ballot and one atomic add per wave, any slot order.
-__global__ void __launch_bounds__(WG) multi_bound_select_kernel(FinalizeArgs fa, const PruneDesc* __restrict__ desc,
-                                                                const unsigned long long* __restrict__ tau_key_in,
-                                                                int2* __restrict__ survivors, int* __restrict__ count) {
-  const PruneDesc d = *desc;
-  if ((int64_t)blockIdx.x * WG >= d.ncols) return;
-  const int t = blockIdx.x * WG + threadIdx.x;
-  const bool valid = t < d.ncols;
-  const int64_t c = valid ? d.col0 + t : 0;
+// One output's standardised moments at column c into the objective's accumulators: untransform, weight, overwrite (the
+// chunk's first output) or add.
+__device__ __forceinline__ void accumulate_output(double* acc_mu, double* acc_var, int64_t c, int first, double weight,
+                                                  double y_mean, double y_scale, double mu, double var) {
+  mu = y_mean + y_scale * mu;
+  var = var * (y_scale * y_scale);
+  const double wm = weight * mu, wv = (weight * weight) * var;
+  acc_mu[c] = first ? wm : acc_mu[c] + wm;
+  acc_var[c] = first ? wv : acc_var[c] + wv;
+}
+
+// The accumulated objective's moments at column c (what FIN_ACCUMULATE summed over the outputs), BoTorch's floor on the
+// scored variance.
+__device__ __forceinline__ void objective_moments(const FinalizeArgs& fa, int64_t c, double& mu, double& var) {
+  mu = fa.acc_mu[c];
+  var = fmax(fa.acc_var[c], 1e-12);
+}
+
+// The passes.  Two end early: the posterior (mean / variance out) and one output of a multi-output objective into the
+// accumulators.  The others are a source of moments, the chunk's partials or the accumulators, crossed with a sink:
+//  score  acquisition, optional scores_out and scored list, 256-candidate block argmax record, incumbent raised.  A NaN
+//         score counts as -inf for the record and the list and stays NaN in scores_out.
+//  bound  of the pruned sweep: the score from the first nI row tiles' partials only (the accumulators: from every
+//         output's first tile) is an upper bound of the candidate's score (the variance can only shrink with further
+//         tiles, and every acquisition grows with it); the candidate survives if bound_keeps, or without an incumbent
+//         the bound itself is kept (u_out).
+// Variance floors: GPyTorch's 1e-10 per output in the standardised space, BoTorch's 1e-12 on the scored variance
+// [upstream] (T = 1, w = 1: FIN_ACCUMULATE + FIN_SCORE_ACC give FIN_SCORE's value bit for bit).
+enum FinalizePass { FIN_POSTERIOR, FIN_ACCUMULATE, FIN_SCORE, FIN_SCORE_ACC, FIN_BOUND, FIN_BOUND_ACC };
+
+template <FinalizePass PASS>
+__global__ void __launch_bounds__(WG) finalize_kernel(FinalizeArgs fa, FinalizeIo io) {
+  constexpr bool BOUND = PASS == FIN_BOUND || PASS == FIN_BOUND_ACC;
+  constexpr bool FROM_ACC = PASS == FIN_SCORE_ACC || PASS == FIN_BOUND_ACC;
+  const gpx_kernel_params& p = fa.p;
+  const Partials& pt = io.part;
+  const int64_t t = (int64_t)blockIdx.x * WG + threadIdx.x;
+  int64_t c = t;
+  bool valid = t < io.q.m;
+  int2* survivors = nullptr;
+  if (io.cols.desc) {
+    const PruneDesc d = *io.cols.desc;
+    if (BOUND && (int64_t)blockIdx.x * WG >= d.ncols) return;
+    valid = t < d.ncols;
+    c = !valid       ? 0
+        : d.list < 0 ? d.col0 + t
+                     : (d.list == 2 ? io.cols.list2 : d.list ? io.cols.list1 : io.cols.list0)[t].x;
+    survivors = d.list == 0 ? io.cols.list1 : io.cols.list0;
+  }
   double score = -INFINITY;
   if (valid) {
     double mu, var;
-    objective_moments(fa, c, mu, var);
+    if constexpr (FROM_ACC) {
+      objective_moments(fa, c, mu, var);
+    } else {
+      const double ss = sum_partials(pt.ss_part + c, pt.nI, pt.C);
+      var = fmax(prior_variance(p, io.q.Xs, io.q.ldxs, c) - ss, 1e-10);  // gpytorch min_variance (float64) [upstream]
+      if constexpr (PASS == FIN_POSTERIOR) {
+        for (int q = 0; q < pt.nrhs; ++q) {
+          double mq = sum_partials(pt.mu_part + (int64_t)q * pt.C + c, pt.nJB, (int64_t)pt.nrhs * pt.C);
+          mq += p.const_mean;
+          io.post.mean[c * io.post.ldmean + q] = fa.y_mean[q] + fa.y_scale[q] * mq;
+        }
+        io.post.var[c] = fmax(var * (fa.y_scale[0] * fa.y_scale[0]), 1e-12);  // BoTorch min_var [upstream]
+        return;
+      }
+      // (a bound pass with a mean bound: the score is non-decreasing in the mean too, so its upper end bounds it)
+      mu = (BOUND && io.bound.mu_bound) ? io.bound.mu_bound[c] + io.bound.mu_bound[pt.C + c]
+                                        : sum_partials(pt.mu_part + c, pt.nJB, pt.C);
+      mu += p.const_mean;
+      if constexpr (PASS == FIN_ACCUMULATE) {
+        accumulate_output(fa.acc_mu, fa.acc_var, c, fa.first, fa.weight, fa.y_mean[0], fa.y_scale[0], mu, var);
+        return;
+      }
+      mu = fa.y_mean[0] + fa.y_scale[0] * mu;
+      var = fmax(var * (fa.y_scale[0] * fa.y_scale[0]), 1e-12);
+    }
     score = acq_score(fa.acq_kind, mu, var, fa.best_f, fa.beta);
   }
-  const double tau = tau_value(*tau_key_in);
-  const bool keep = valid && !(score + PRUNE_EPS * (fabs(score) + fabs(tau) + 1.0) < tau);
-  const unsigned long long mask = __ballot(keep);
-  if (mask == 0) return;
-  const int lane = threadIdx.x & 63;
-  int base = 0;
-  if (lane == 0) base = atomicAdd(count, __popcll(mask));
-  base = __shfl(base, 0);
-  if (keep) survivors[base + __popcll(mask & ((1ull << lane) - 1))] = make_int2((int)c, t);
+  if constexpr (PASS == FIN_POSTERIOR || PASS == FIN_ACCUMULATE) {
+    return;
+  } else if constexpr (BOUND) {
+    if (io.bound.u_out) {
+      if (valid) io.bound.u_out[c] = score;
+      return;
+    }
+    const bool keep = valid && bound_keeps(score, tau_value(*io.bound.tau));
+    const int slot = wave_append(keep, io.bound.count);
+    if (keep) survivors[slot] = make_int2((int)c, (int)t);
+  } else {
+    const ScoreOut& so = io.score;
+    if (valid && so.scores) so.scores[c] = score;
+    if (score != score) score = -INFINITY;
+    if (so.sc_count) {
+      // the top-k form's scored list; the value is gpx_topk_f64's key of the score (NaN is -inf already, -0 becomes +0)
+      const int slot = wave_append(valid, so.sc_count);
+      if (valid) {
+        so.sc_val[slot] = score + 0.0;
+        so.sc_idx[slot] = io.q.index_offset + c;
+      }
+    }
+    double bv = score;
+    int64_t bi = valid ? io.q.index_offset + c : INT64_MAX;
+    block_argmax(bv, bi);
+    if (threadIdx.x == 0) {
+      so.rec_val[blockIdx.x] = bv;
+      so.rec_idx[blockIdx.x] = bi;
+      if (so.tau) atomicMax(so.tau, tau_key(bv));
+    }
+  }
 }
 
 // ---- the seeded order of the lazy form (launch_sweep_super_pruned) ---------------------------------------
@@ -1294,30 +1320,15 @@ __global__ void __launch_bounds__(WG) seed_select_kernel(const double* __restric
     const double u = U[c];
     argmax_merge(bv, bi, u != u ? -INFINITY : u, c);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double v2 = __shfl_xor(bv, o);
-    const int64_t i2 = __shfl_xor(bi, o);
-    argmax_merge(bv, bi, v2, i2);
-  }
-  __shared__ double wv[4];
-  __shared__ int64_t wi[4];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) {
-    wv[w] = bv;
-    wi[w] = bi;
-  }
-  __syncthreads();
+  block_argmax(bv, bi);
   if (threadIdx.x == 0) {
-    for (int q = 1; q < 4; ++q) argmax_merge(bv, bi, wv[q], wi[q]);
     seed[s] = make_int2((int)bi, s);
     if (s == 0) *count = PRUNE_SEED;
   }
 }
 
-// The seeded order's prune pass: mode 4's test of the stored bounds U against the incumbent the seed left (a NaN bound
-// survives), the seed's own columns left out (they are scored already); survivors {column, column} to the list as mode
-// 4 appends them: one ballot and one atomic add per wave, any slot order.
+// The seeded order's prune pass: the bound test of the stored bounds U against the incumbent the seed left, the seed's
+// own columns left out (they are scored already); survivors {column, column} to the list.
 __global__ void __launch_bounds__(WG) seed_prune_kernel(const double* __restrict__ U, int64_t m,
                                                         const int2* __restrict__ seed,
                                                         const unsigned long long* __restrict__ tau_key_in,
@@ -1325,15 +1336,9 @@ __global__ void __launch_bounds__(WG) seed_prune_kernel(const double* __restrict
   const int64_t c = (int64_t)blockIdx.x * WG + threadIdx.x;
   const bool valid = c < m && seed[seed_slice_of(c, m)].x != (int)c;
   const double score = valid ? U[c] : -INFINITY;
-  const double tau = tau_value(*tau_key_in);
-  const bool keep = valid && !(score + PRUNE_EPS * (fabs(score) + fabs(tau) + 1.0) < tau);
-  const unsigned long long mask = __ballot(keep);
-  if (mask == 0) return;
-  const int lane = threadIdx.x & 63;
-  int base = 0;
-  if (lane == 0) base = atomicAdd(count, __popcll(mask));
-  base = __shfl(base, 0);
-  if (keep) survivors[base + __popcll(mask & ((1ull << lane) - 1))] = make_int2((int)c, (int)c);
+  const bool keep = valid && bound_keeps(score, tau_value(*tau_key_in));
+  const int slot = wave_append(keep, count);
+  if (keep) survivors[slot] = make_int2((int)c, (int)c);
 }
 
 // The pruned sweep's per-chunk reset (one thread): the first stage's column set (the chunk's columns from col0 on, in
@@ -1427,22 +1432,8 @@ __global__ void __launch_bounds__(WG) argmax_final_kernel(const double* __restri
     if (v != v) v = -INFINITY;
     argmax_merge(bv, bi, v, idx[e * stride]);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double v2 = __shfl_xor(bv, o);
-    const int64_t i2 = __shfl_xor(bi, o);
-    argmax_merge(bv, bi, v2, i2);
-  }
-  __shared__ double wv[4];
-  __shared__ int64_t wi[4];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) {
-    wv[w] = bv;
-    wi[w] = bi;
-  }
-  __syncthreads();
+  block_argmax(bv, bi);
   if (threadIdx.x == 0) {
-    for (int q = 1; q < 4; ++q) argmax_merge(bv, bi, wv[q], wi[q]);
     *best_val = bv;
     *best_idx = bi;
   }
@@ -1457,13 +1448,13 @@ __device__ __forceinline__ bool topk_before(double va, int64_t ia, double vb, in
 }
 constexpr int TOPK_LDS = 2 * GPX_TOPK_SWEEP_MAX;  // entries of the merge buffer: the pool and as many new ones
 
-// One workgroup, enqueued behind every launch that scores candidates in full (finalize_kernel mode 1 with a scored
-// list): merges the list's n entries into the pool of the k best (score, index) pairs scored so far, empties the list
-// and sets the incumbent of the bound passes that follow:
+// One workgroup, enqueued behind every launch that scores candidates in full (a score pass of finalize_kernel with a
+// scored list): merges the list's n entries into the pool of the k best (score, index) pairs scored so far, empties the
+// list and sets the incumbent of the bound passes that follow:
 //     tau = the pool's k-th score once the pool holds k pairs, else -inf.
 // Soundness.  tau is the k-th best of a subset of the call's exact scores, hence <= the k-th best of all of them.  The
-// bound pass (mode 4) drops a candidate only if ub + PRUNE_EPS (|ub| + |tau| + 1) < tau with ub >= its exact score: a
-// dropped candidate scores strictly below k candidates scored in full, so it is not among the call's k best and does
+// bound pass drops a candidate only if its bound ub >= its exact score lies below tau by more than bound_keeps' margin:
+// a dropped candidate scores strictly below k candidates scored in full, so it is not among the call's k best and does
 // not tie with the k-th; a candidate that ties the k-th place is always scored, and the lowest index wins it in the
 // merge.  Every member of the final k best is therefore scored in full and passes through a merge: the pool at the end
 // of the call is the answer.  With k = 1 tau takes the values the argmax form's atomicMax gives it.
@@ -1582,17 +1573,22 @@ __global__ void __launch_bounds__(WG) index_shift_kernel(int64_t* __restrict__ i
 }
 
 // ---- host side -------------------------------------------------------------------------------------------
-// finalize_kernel mode 1's view of a scoring launch: the argmax form raises the incumbent itself, the top-k form feeds
-// the scored list and leaves the incumbent to topk_pool_kernel
-static PruneSel score_sel(PruneSel sel, const PruneState& ps, const TopkSweep* tk) {
-  sel.count = nullptr;
-  sel.tau = tk ? nullptr : ps.tau;
+// The grid of a finalize pass: a workgroup per 256 of the io.q.m columns the launch can have.
+template <FinalizePass PASS>
+static void launch_finalize(Context* c, const FinalizeArgs& fa, const FinalizeIo& io) {
+  finalize_kernel<PASS><<<(unsigned)((io.q.m + WG - 1) / WG), WG, 0, c->stream>>>(fa, io);
+}
+// The sink of a pruned sweep's score pass: the argmax form raises the incumbent itself, the top-k form feeds the scored
+// list and leaves the incumbent to topk_pool_kernel
+static ScoreOut pruned_score_out(double* rec_val, int64_t* rec_idx, const PruneState& ps, const TopkSweep* tk) {
+  ScoreOut so{rec_val, rec_idx};
+  so.tau = tk ? nullptr : ps.tau;
   if (tk) {
-    sel.sc_val = tk->list_val;
-    sel.sc_idx = tk->list_idx;
-    sel.sc_count = tk->head;
+    so.sc_val = tk->list_val;
+    so.sc_idx = tk->list_idx;
+    so.sc_count = tk->head;
   }
-  return sel;
+  return so;
 }
 static void launch_topk_pool(Context* c, const PruneState& ps, const TopkSweep* tk, int64_t C) {
   if (!tk) return;
@@ -1642,6 +1638,29 @@ static int sweep_cu_count(Context* c) {
 static unsigned tail_grid(Context* c, int per_cu, int64_t units) {
   const int64_t bound = (int64_t)per_cu * sweep_cu_count(c);
   return (unsigned)(bound > 0 && bound < units ? bound : units);
+}
+
+// A KSTAR_GATHER round over entries first .. first + cap - 1 of a survivor list of *count {column, slot} pairs: the
+// gather writes the round's first descriptor (rows0 row tiles in its first stage; last: that stage is also the last)
+// and zeroes its stages' counts, with pad marks the last tile's padding slots in the list, and with mu_out scatters
+// the listed candidates' mean partials to mu_out[jb * ldmu + column].
+static KstarAux gather_aux(int2* list, const int* count, int first, int cap, const PruneState& ps, int rows0, bool last,
+                           double* mu_out, int64_t ldmu, bool pad = true) {
+  KstarAux aux{};
+  aux.list = reinterpret_cast<int*>(list);
+  if (pad) aux.pad = reinterpret_cast<int*>(list);
+  aux.lstride = 2;
+  aux.count = count;
+  aux.first = first;
+  aux.cap = cap;
+  aux.desc = ps.desc + 1;
+  aux.rcount = ps.count + 1;
+  aux.stats = ps.stats;
+  aux.rows0 = rows0;
+  aux.last = last;
+  aux.mu_out = mu_out;
+  aux.ldmu = ldmu;
+  return aux;
 }
 
 // K* and the partial means of one chunk (launch 1 of the file comment)
@@ -1748,14 +1767,36 @@ static FinalizeArgs finalize_args(const gpx_kernel_params& p, const gpx_acq_para
   fa.acc_mu = fa.acc_var = nullptr;
   return fa;
 }
+// One output of a multi-output objective in fa's place: its untransform and weight, and the accumulators it goes to
+static void set_output(FinalizeArgs& fa, double y_mean, double y_scale, double weight, bool first, double* acc_mu,
+                       double* acc_var) {
+  fa.y_mean[0] = y_mean;
+  fa.y_scale[0] = y_scale;
+  fa.weight = weight;
+  fa.first = first;
+  fa.acc_mu = acc_mu;
+  fa.acc_var = acc_var;
+}
+// The arguments of the passes that read the accumulators alone: no model, no untransform
+static FinalizeArgs objective_args(const gpx_acq_params& a, double* acc_mu, double* acc_var) {
+  FinalizeArgs fa{};
+  fa.acq_kind = a.kind;
+  fa.best_f = a.best_f;
+  fa.beta = a.beta;
+  fa.acc_mu = acc_mu;
+  fa.acc_var = acc_var;
+  return fa;
+}
 
-hipError_t launch_sweep_chunk(const SweepModel& M, const SweepCands& q, const SweepBuffers& b, int mode,
-                              const gpx_acq_params* a, const SweepOut& out, int64_t rec_offset, const MultiOutput* mo) {
+// K*, the product (launches 1 and 2 of the file comment, or the fused small-n kernel) and one finalize pass over the
+// chunk's columns; io: the pass's outputs
+template <FinalizePass PASS>
+static void sweep_chunk_pass(const SweepModel& M, const SweepCands& q, const SweepBuffers& b, const FinalizeArgs& fa,
+                             FinalizeIo io) {
   Context* c = M.c;
   const gpx_kernel_params& p = M.p;
   const int64_t C = b.chunk;
   int nJB = M.npad / NB, nI = M.npad / TT;
-  const int ncb = (int)((q.m + WG - 1) / WG);  // 256-candidate blocks actually used in this chunk
   if (sweep_fused_ok(c, p, M.npad, M.nrhs)) {
     LaunchTimer tm(c, GPX_TIMER_TRMM);
     const int nwg = (int)((q.m + 63) / 64);
@@ -1780,21 +1821,25 @@ hipError_t launch_sweep_chunk(const SweepModel& M, const SweepCands& q, const Sw
     const int ncbt = (int)((q.m + TT - 1) / TT);
     trmm_sumsq_kernel<<<ncbt * nI, WG, 0, c->stream>>>(M.W, M.ldw, b.kstar, C, nI, ncbt, b.ss_part, 0);
   }
-  {
-    LaunchTimer tm(c, GPX_TIMER_ACQ);
-    FinalizeArgs fa = finalize_args(p, a, M.nrhs, out.y_mean, out.y_scale);
-    if (mo) {  // one output of a multi-output objective: accumulate, score later (launch_multi_score)
-      mode = 2;
-      fa.y_mean[0] = mo->y_mean;
-      fa.y_scale[0] = mo->y_scale;
-      fa.weight = mo->weight;
-      fa.first = mo->first;
-      fa.acc_mu = mo->acc_mu;
-      fa.acc_var = mo->acc_var;
-    }
-    finalize_kernel<<<ncb, WG, 0, c->stream>>>(fa, mode, q.Xs, q.ldxs, q.m, C, M.nrhs, nJB, nI, b.mu_part, b.ss_part,
-                                               out.mean, out.ldmean, out.var, out.scores, b.rec_val + rec_offset,
-                                               b.rec_idx + rec_offset, q.index_offset, PruneSel{});
+  LaunchTimer tm(c, GPX_TIMER_ACQ);
+  io.q = q;
+  io.part = {b.mu_part, b.ss_part, C, nJB, nI, M.nrhs};
+  launch_finalize<PASS>(c, fa, io);
+}
+
+hipError_t launch_sweep_chunk(const SweepModel& M, const SweepCands& q, const SweepBuffers& b, const gpx_acq_params* a,
+                              const SweepOut& out, int64_t rec_offset, const MultiOutput* mo) {
+  FinalizeArgs fa = finalize_args(M.p, a, M.nrhs, out.y_mean, out.y_scale);
+  FinalizeIo io{};
+  if (mo) {  // one output of a multi-output objective: accumulate, score later (launch_multi_score)
+    set_output(fa, mo->y_mean, mo->y_scale, mo->weight, mo->first, mo->acc_mu, mo->acc_var);
+    sweep_chunk_pass<FIN_ACCUMULATE>(M, q, b, fa, io);
+  } else if (!a) {
+    io.post = {out.mean, out.ldmean, out.var};
+    sweep_chunk_pass<FIN_POSTERIOR>(M, q, b, fa, io);
+  } else {
+    io.score = {b.rec_val + rec_offset, b.rec_idx + rec_offset, out.scores};
+    sweep_chunk_pass<FIN_SCORE>(M, q, b, fa, io);
   }
   return hipGetLastError();
 }
@@ -1802,15 +1847,10 @@ hipError_t launch_sweep_chunk(const SweepModel& M, const SweepCands& q, const Sw
 hipError_t launch_multi_score(Context* c, const SweepCands& q, const MultiOutput& mo, const gpx_acq_params& a,
                               double* scores_out, double* rec_val, int64_t* rec_idx) {
   LaunchTimer tm(c, GPX_TIMER_ACQ);
-  FinalizeArgs fa{};
-  fa.acq_kind = a.kind;
-  fa.best_f = a.best_f;
-  fa.beta = a.beta;
-  fa.acc_mu = mo.acc_mu;
-  fa.acc_var = mo.acc_var;
-  const int ncb = (int)((q.m + WG - 1) / WG);
-  finalize_kernel<<<ncb, WG, 0, c->stream>>>(fa, 3, nullptr, 0, q.m, 0, 1, 0, 0, nullptr, nullptr, nullptr, 0, nullptr,
-                                             scores_out, rec_val, rec_idx, q.index_offset, PruneSel{});
+  FinalizeIo io{};
+  io.q = q;
+  io.score = {rec_val, rec_idx, scores_out};
+  launch_finalize<FIN_SCORE_ACC>(c, objective_args(a, mo.acc_mu, mo.acc_var), io);
   return hipGetLastError();
 }
 
@@ -1861,7 +1901,7 @@ static PruneBufs prune_bufs(const double* kstar, int64_t ld0, const PruneState& 
 }
 
 // prune_init_kernel, then the seed block where the plan has one: K* of its columns (build_kstar: the lazy form; the
-// chunked form built the whole chunk's before), the full product in narrow tiles, finalize mode 1, pool.
+// chunked form built the whole chunk's before), the full product in narrow tiles, the score pass, pool.
 static void launch_seed_block(const SweepModel& M, const SweepCands& q, const SweepBuffers& b, const PruneState& ps,
                               const FinalizeArgs& fa, const SeedPlan& sp, int R1, bool one_stage, bool first,
                               bool build_kstar, double* rec_val, int64_t* rec_idx, int64_t* host_stats,
@@ -1888,14 +1928,17 @@ static void launch_seed_block(const SweepModel& M, const SweepCands& q, const Sw
     product();
   }
   LaunchTimer tm(c, GPX_TIMER_ACQ);
-  finalize_kernel<<<sp.seed_blocks, WG, 0, c->stream>>>(fa, 1, q.Xs, q.ldxs, sp.seed, C, 1, nJB, nI, b.mu_part,
-                                                        b.ss_part, nullptr, 0, nullptr, nullptr, rec_val, rec_idx,
-                                                        q.index_offset, score_sel(PruneSel{}, ps, tk));
+  FinalizeIo io{};
+  io.q = q.first(sp.seed);
+  io.part = {b.mu_part, b.ss_part, C, nJB, nI, 1};
+  io.score = pruned_score_out(rec_val, rec_idx, ps, tk);
+  launch_finalize<FIN_SCORE>(c, fa, io);
   launch_topk_pool(c, ps, tk, C);
 }
 
 // The staged product of one column set: per stage s the row tiles R[s] .. R[s+1] - 1 of the active columns, after every
-// stage but the last the bound pass (finalize mode 4) and the compaction; then finalize mode 1 over what is left, pool.
+// stage but the last the bound pass (FIN_BOUND) and the compaction; then the score pass (FIN_SCORE) over what is left,
+// pool.
 struct StagePlan {
   PruneBufs pb;          // the K* source and its pitch, the compact buffers, the index lists
   double* mu_part;       // the partial arrays of the columns' own places, and their pitch
@@ -1914,14 +1957,13 @@ static void launch_stages(const SweepModel& M, const SweepCands& q, const PruneS
                           const StagePlan& sg, int64_t C, const TopkSweep* tk) {
   Context* c = M.c;
   const int nJB = M.npad / NB, nI = M.npad / TT;
-  const int tiles = (sg.cap + TT - 1) / TT, blocks = (sg.cap + WG - 1) / WG;
+  const int tiles = (sg.cap + TT - 1) / TT;
   PruneDesc* desc = ps.desc + sg.desc0;
   int* count = ps.count + sg.desc0;
-  PruneSel sel{};
-  sel.list0 = ps.list[0];
-  sel.list1 = ps.list[1];
-  sel.list2 = sg.pb.list2;
-  sel.tau = ps.tau;
+  FinalizeIo io{};
+  io.q = q.first(sg.cap);
+  io.part = {sg.mu_part, sg.ss_part, sg.pitch, nJB, nI, 1};
+  io.cols = {nullptr, ps.list[0], ps.list[1], sg.pb.list2};
   {
     LaunchTimer tm(c, GPX_TIMER_TRMM);
     // compaction: a workgroup per 256 slots x 32 rows of the set's capacity at most and per 256 slots at least (no
@@ -1936,20 +1978,19 @@ static void launch_stages(const SweepModel& M, const SweepCands& q, const PruneS
       else
         launch_tail_stage(c, M.W, M.ldw, sg.pitch, nI, sg.ss_part, st, tiles, sg.narrow_below);
       if (s == sg.ns - 1) break;
-      sel.desc = desc + s;
-      sel.count = count + s;
-      finalize_kernel<<<blocks, WG, 0, c->stream>>>(fa, 4, q.Xs, q.ldxs, q.m, sg.pitch, 1, nJB, sg.R[s + 1], sg.mu_part,
-                                                    sg.ss_part, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
-                                                    q.index_offset, sel);
+      io.cols.desc = desc + s;
+      io.part.nI = sg.R[s + 1];
+      io.bound = {count + s, ps.tau};
+      launch_finalize<FIN_BOUND>(c, fa, io);
       prune_compact_kernel<<<gc, WG, 0, c->stream>>>(sg.pb, desc + s, desc + s + 1, count + s, M.npad, ROWS,
                                                      sg.R[s + 2] - sg.R[s + 1], s + 2 == sg.ns, ps.stats);
     }
   }
   LaunchTimer tm(c, GPX_TIMER_ACQ);
-  sel.desc = desc + sg.ns - 1;
-  finalize_kernel<<<blocks, WG, 0, c->stream>>>(fa, 1, q.Xs, q.ldxs, q.m, sg.pitch, 1, nJB, nI, sg.mu_part, sg.ss_part,
-                                                nullptr, 0, nullptr, nullptr, sg.rec_val, sg.rec_idx, q.index_offset,
-                                                score_sel(sel, ps, tk));
+  io.cols.desc = desc + sg.ns - 1;
+  io.part.nI = nI;
+  io.score = pruned_score_out(sg.rec_val, sg.rec_idx, ps, tk);
+  launch_finalize<FIN_SCORE>(c, fa, io);
   launch_topk_pool(c, ps, tk, C);
 }
 
@@ -1986,9 +2027,9 @@ hipError_t launch_sweep_chunk_pruned(const SweepModel& M, const SweepCands& q, c
 //         (launch_seed_block); the head's bound pass selects against their best.
 //         A longer call (its first super-chunk): the leading block is a weak seed (on the bench problem its best logEI
 //         is -38.7, the optimum -0.66), and the head's bound ranks the candidates without any incumbent.  So the bound
-//         pass runs first and keeps every column's bound U (finalize mode 4 with u_out); seed_select_kernel takes the
+//         pass runs first and keeps every column's bound U (FIN_BOUND with u_out); seed_select_kernel takes the
 //         column of the largest U in each of PRUNE_SEED contiguous slices of the span (seed_slice_begin); those columns
-//         go through a round like the tail's (gather build, row tiles 1 .. nI - 1 in one stage, finalize mode 1:
+//         go through a round like the tail's (gather build, row tiles 1 .. nI - 1 in one stage, the score pass:
 //         records, incumbent, for top-k the scored list and the pool); seed_prune_kernel then tests every other
 //         column's U against that incumbent.  No column is scored twice.  Later super-chunks have no seed.
 //         That is the parent order of a seeded span (sweep_order 0, and always for UCB, the variance acquisition, the
@@ -1996,7 +2037,7 @@ hipError_t launch_sweep_chunk_pruned(const SweepModel& M, const SweepCands& q, c
 //         runs no head before the bound pass: U0 = score_ub(mean bound, prior variance), which bounds U from above
 //         because the prior variance bounds the posterior's; the seed is the slice maxima of U0 through EVERY row tile
 //         of the product; seed_prune_kernel keeps S1 = {U0 >= incumbent}; the list-driven head_product_kernel builds K*
-//         rows 0 .. 127 and row tile 0 for S1 alone; and a second bound pass (mode 4 over S1's list) keeps the columns
+//         rows 0 .. 127 and row tile 0 for S1 alone; and a second bound pass (FIN_BOUND over S1's list) keeps columns
 //         with U >= incumbent: the parent order's survivors whenever the seed's incumbent is the same.  Later
 //         super-chunks take the same two passes against the running incumbent, without a seed.
 //  tail   rounds of at most C survivors: KSTAR_GATHER rebuilds their full-height columns into the chunk buffer (the bits
@@ -2083,17 +2124,16 @@ hipError_t launch_sweep_super_pruned(const SweepModel& M, const SweepCands& q, c
       const PruneStage st{prune_bufs(ph.head, MA, ps), ps.desc, 0, R[1], 0};
       trmm_stage_kernel<<<(sp.ncols + TT - 1) / TT * st.nrows, WG, 0, c->stream>>>(M.W, M.ldw, MA, nI, ph.ss_part, st);
     }
-    PruneSel sel{};
-    sel.tau = ps.tau;
-    sel.desc = ps.desc;
-    sel.count = mean_first ? n1 : ps.count;
-    sel.list0 = mean_first ? s1 : ph.survivors;  // (the descriptor's list is -1: the survivors go to list0)
-    sel.mu_bound = mu_bound ? ph.mu_part + 2 * MA : nullptr;
-    sel.u_out = seeded ? U : nullptr;  // (seeded: no incumbent yet, the bounds are kept)
-    finalize_kernel<<<(sp.ncols + WG - 1) / WG, WG, 0, c->stream>>>(fa, 4, q.Xs, q.ldxs, q.m, MA, 1, nJB,
-                                                                    mean_first ? 0 : R[1], ph.mu_part, ph.ss_part,
-                                                                    nullptr, 0, nullptr, nullptr, nullptr, nullptr,
-                                                                    q.index_offset, sel);
+    FinalizeIo io{};
+    io.q = q.first(sp.ncols);
+    io.part = {ph.mu_part, ph.ss_part, MA, nJB, mean_first ? 0 : R[1], 1};
+    io.cols.desc = ps.desc;
+    io.cols.list0 = mean_first ? s1 : ph.survivors;  // (the descriptor's list is -1: the survivors go to list0)
+    io.bound.count = mean_first ? n1 : ps.count;
+    io.bound.tau = ps.tau;
+    io.bound.mu_bound = mu_bound ? ph.mu_part + 2 * MA : nullptr;
+    io.bound.u_out = seeded ? U : nullptr;  // (seeded: no incumbent yet, the bounds are kept)
+    launch_finalize<FIN_BOUND>(c, fa, io);
     if (seeded) seed_select_kernel<<<PRUNE_SEED, WG, 0, c->stream>>>(U, q.m, seed, nseed);
   }
   if (seeded) {
@@ -2105,20 +2145,10 @@ hipError_t launch_sweep_super_pruned(const SweepModel& M, const SweepCands& q, c
     // lasts as long as its deepest tile: 0.46 ms in the wide shape against 0.37 ms for the parent's 8 x 31 narrow ones,
     // DESIGN §5.  So the seed's stage keeps the narrow shape at equality too.)
     const int seed_narrow = mean_first && sweep_cu_count(c) > 0 ? sweep_cu_count(c) + 1 : 0;
-    KstarAux aux{};
-    aux.list = reinterpret_cast<const int*>(seed);
-    aux.lstride = 2;
-    aux.count = nseed;
-    aux.first = 0;
-    aux.cap = PRUNE_SEED;
-    aux.desc = ps.desc + 1;
-    aux.rcount = ps.count + 1;
-    aux.stats = ps.stats;
-    aux.rows0 = nI - Rs[0];
-    aux.last = 1;
-    aux.mu_out = mu_bound ? ph.mu_part : nullptr;
-    aux.ldmu = MA;
-    launch_kstar(M, q.first(PRUNE_SEED), b, KSTAR_GATHER, aux);
+    // (pad = false: the seed list is whole tiles and lives in an index list, nothing to mark in it)
+    launch_kstar(M, q.first(PRUNE_SEED), b, KSTAR_GATHER,
+                 gather_aux(seed, nseed, 0, PRUNE_SEED, ps, nI - Rs[0], true, mu_bound ? ph.mu_part : nullptr, MA,
+                            false));
     launch_stages(M, q, ps, fa,
                   StagePlan{prune_bufs(b.kstar, C, ps, seed), ph.mu_part, ph.ss_part, MA, Rs, 1, 1, false, PRUNE_SEED,
                             ph.rec_val + *recs, ph.rec_idx + *recs, seed_narrow},
@@ -2135,16 +2165,14 @@ hipError_t launch_sweep_super_pruned(const SweepModel& M, const SweepCands& q, c
     // survivors are the parent's whenever the incumbent is.
     LaunchTimer tm(c, GPX_TIMER_TRMM);
     launch_head_product(M, q.first(sp.ncols), MA, ph.mu_part, ph.ss_part, 0, 0, s1, n1, ps.desc, ps.stats);
-    PruneSel sel{};
-    sel.tau = ps.tau;
-    sel.desc = ps.desc;
-    sel.count = ps.count;
-    sel.list0 = ph.survivors;  // (the descriptor's list is 2: the survivors go to list0)
-    sel.list2 = s1;
-    sel.mu_bound = ph.mu_part + 2 * MA;
-    finalize_kernel<<<(sp.ncols + WG - 1) / WG, WG, 0, c->stream>>>(fa, 4, q.Xs, q.ldxs, q.m, MA, 1, nJB, R[1],
-                                                                    ph.mu_part, ph.ss_part, nullptr, 0, nullptr, nullptr,
-                                                                    nullptr, nullptr, q.index_offset, sel);
+    FinalizeIo io{};
+    io.q = q.first(sp.ncols);
+    io.part = {ph.mu_part, ph.ss_part, MA, nJB, R[1], 1};
+    io.cols.desc = ps.desc;
+    io.cols.list0 = ph.survivors;  // (the descriptor's list is 2: the survivors go to list0)
+    io.cols.list2 = s1;
+    io.bound = {ps.count, ps.tau, ph.mu_part + 2 * MA};
+    launch_finalize<FIN_BOUND>(c, fa, io);
   }
   // tail (its passes read the survivors' exact partials, written by their gather)
   for (int64_t r0 = 0; r0 < sp.ncols; r0 += C) {
@@ -2159,21 +2187,9 @@ hipError_t launch_sweep_super_pruned(const SweepModel& M, const SweepCands& q, c
       if (nI > 4) Rr[++ns] = 4;
       Rr[++ns] = nI;
     }
-    KstarAux aux{};
-    aux.list = reinterpret_cast<const int*>(ph.survivors);
-    aux.lstride = 2;
-    aux.count = ps.count;
-    aux.first = (int)r0;
-    aux.cap = cap;
-    aux.pad = reinterpret_cast<int*>(ph.survivors);
-    aux.desc = ps.desc + 1;
-    aux.rcount = ps.count + 1;
-    aux.stats = ps.stats;
-    aux.rows0 = Rr[1] - Rr[0];
-    aux.last = ns == 1;
-    aux.mu_out = mu_bound ? ph.mu_part : nullptr;
-    aux.ldmu = MA;
-    launch_kstar(M, q.first(cap), b, KSTAR_GATHER, aux);
+    launch_kstar(M, q.first(cap), b, KSTAR_GATHER,
+                 gather_aux(ph.survivors, ps.count, (int)r0, cap, ps, Rr[1] - Rr[0], ns == 1,
+                            mu_bound ? ph.mu_part : nullptr, MA));
     launch_stages(M, q, ps, fa,
                   StagePlan{prune_bufs(b.kstar, C, ps, ph.survivors + r0), ph.mu_part, ph.ss_part, MA, Rr, ns, 1, false,
                             cap, ph.rec_val + *recs, ph.rec_idx + *recs},
@@ -2187,14 +2203,14 @@ hipError_t launch_sweep_super_pruned(const SweepModel& M, const SweepCands& q, c
 // chunk.  One K*, mu_part and ss_part buffer serves the outputs in turn, always in ascending t, so the accumulators of a
 // candidate scored in full form in the full multi-output sweep's order.
 //  seed   (the call's first chunk) the leading PRUNE_SEED candidates through launch_sweep_chunk with the accumulators,
-//         mode 3 into the scored list, pool: the pool's k-th score is the incumbent.
+//         FIN_SCORE_ACC into the scored list, pool: the pool's k-th score is the incumbent.
 //  head   per output: K* rows 0 .. 127 (KSTAR_FULL) and the other row blocks' mean partials (KSTAR_MU), row tile 0 of
-//         the product, mode 2 over that tile's partial alone: exact mean, upper bound of the variance.  Then
-//         multi_bound_select_kernel: the survivors go to ph.survivors, their count to ps.count[0].
+//         the product, FIN_ACCUMULATE over that tile's partial alone: exact mean, upper bound of the variance.  Then
+//         FIN_BOUND_ACC: the survivors go to ph.survivors, their count to ps.count[0].
 //  tail   per output: KSTAR_GATHER rebuilds the survivors' columns (mean partials scattered to the columns' own places),
-//         every row tile through launch_tail_stage, mode 2 through the round's descriptor with all nI partials.  Then
-//         mode 3 through the descriptor into the scored list, pool.  The grids are sized for every staged column;
-//         workgroups beyond the survivors return at once.
+//         every row tile through launch_tail_stage, FIN_ACCUMULATE through the round's descriptor with all nI partials.
+//         Then FIN_SCORE_ACC through the descriptor into the scored list, pool.  The grids are sized for every staged
+//         column; workgroups beyond the survivors return at once.
 hipError_t launch_topk_multi_chunk(Context* c, int T, const MultiModel* outs, int n, int npad, const double* X,
                                    int64_t ldx, const SweepCands& q, const SweepWorkspace& w, const gpx_acq_params& a,
                                    bool first, int64_t* host_stats) {
@@ -2207,51 +2223,37 @@ hipError_t launch_topk_multi_chunk(Context* c, int T, const MultiModel* outs, in
   auto model = [&](int t) {
     return SweepModel{c, *outs[t].p, n, npad, X, ldx, outs[t].W, outs[t].ldw, outs[t].alpha, 1};
   };
-  auto accumulate = [&](int t) {  // mode 2 of output t
+  auto accumulate = [&](int t) {  // FIN_ACCUMULATE's arguments of output t
     FinalizeArgs fa = finalize_args(*outs[t].p, &a, 1, nullptr, nullptr);
-    fa.y_mean[0] = outs[t].y_mean;
-    fa.y_scale[0] = outs[t].y_scale;
-    fa.weight = outs[t].weight;
-    fa.first = t == 0;
-    fa.acc_mu = w.acc_mu;
-    fa.acc_var = w.acc_var;
+    set_output(fa, outs[t].y_mean, outs[t].y_scale, outs[t].weight, t == 0, w.acc_mu, w.acc_var);
     return fa;
   };
-  FinalizeArgs fs{};  // mode 3 and the bound pass
-  fs.acq_kind = a.kind;
-  fs.best_f = a.best_f;
-  fs.beta = a.beta;
-  fs.acc_mu = w.acc_mu;
-  fs.acc_var = w.acc_var;
-  auto score = [&](int64_t cols, const PruneSel& sel) {  // mode 3 into the scored list, then the pool
+  const FinalizeArgs fs = objective_args(a, w.acc_mu, w.acc_var);  // the accumulators' score and bound passes
+  auto score = [&](int64_t cols, const ColumnSet& set) {  // the accumulators' score into the scored list, then the pool
     LaunchTimer tm(c, GPX_TIMER_ACQ);
-    finalize_kernel<<<(unsigned)((cols + WG - 1) / WG), WG, 0, c->stream>>>(
-        fs, 3, nullptr, 0, cols, 0, 1, 0, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, b.rec_val, b.rec_idx,
-        q.index_offset, score_sel(sel, ps, tk));
+    FinalizeIo io{};
+    io.q = q.first(cols);
+    io.cols = set;
+    io.score = pruned_score_out(b.rec_val, b.rec_idx, ps, tk);
+    launch_finalize<FIN_SCORE_ACC>(c, fs, io);
     launch_topk_pool(c, ps, tk, C);
   };
   // (rows0 = T: the head runs one row tile per output over the staged columns' tiles)
   prune_init_kernel<<<1, 64, 0, c->stream>>>(ps.desc, ps.count, ps.tau, ps.stats, sp.col0, sp.ncols, T, 0, first,
                                              tk->head);
   if (sp.seed) {
-    MultiOutput mo;
-    mo.acc_mu = w.acc_mu;
-    mo.acc_var = w.acc_var;
-    for (int t = 0; t < T; ++t) {
-      mo.weight = outs[t].weight;
-      mo.y_mean = outs[t].y_mean;
-      mo.y_scale = outs[t].y_scale;
-      mo.first = t == 0;
-      (void)launch_sweep_chunk(model(t), q.first(sp.seed), b, 1, &a, SweepOut(), 0, &mo);  // (the error is read below)
-    }
+    for (int t = 0; t < T; ++t)
+      sweep_chunk_pass<FIN_ACCUMULATE>(model(t), q.first(sp.seed), b, accumulate(t), FinalizeIo{});
     host_stats[1] += sp.seed;
     host_stats[2] += (int64_t)T * ((sp.seed + TT - 1) / TT) * nI;
-    score(sp.seed, PruneSel{});
+    score(sp.seed, ColumnSet{});
   }
   if (sp.ncols == 0) return hipGetLastError();
-  const int tiles = (sp.ncols + TT - 1) / TT, blocks = (sp.ncols + WG - 1) / WG;
-  PruneSel sel{};
-  sel.desc = ps.desc;
+  const int tiles = (sp.ncols + TT - 1) / TT;
+  FinalizeIo io{};  // the staged columns' passes: the head's through the chunk's descriptor, the tail's the round's
+  io.q = q.first(sp.ncols);
+  io.part = {b.mu_part, b.ss_part, C, nJB, 1, 1};
+  io.cols.desc = ps.desc;
   for (int t = 0; t < T; ++t) {
     const SweepModel M = model(t);
     launch_kstar(M, q, b, KSTAR_FULL, KstarAux{}, PRUNE_HEAD_ROWS);
@@ -2261,40 +2263,29 @@ hipError_t launch_topk_multi_chunk(Context* c, int T, const MultiModel* outs, in
     LaunchTimer tm(c, GPX_TIMER_TRMM);
     const PruneStage st{prune_bufs(b.kstar, C, ps), ps.desc, 0, 1, 0};
     trmm_stage_kernel<<<tiles, WG, 0, c->stream>>>(M.W, M.ldw, C, nI, b.ss_part, st);
-    finalize_kernel<<<blocks, WG, 0, c->stream>>>(accumulate(t), 2, q.Xs, q.ldxs, q.m, C, 1, nJB, 1, b.mu_part, b.ss_part,
-                                                  nullptr, 0, nullptr, nullptr, nullptr, nullptr, q.index_offset, sel);
+    launch_finalize<FIN_ACCUMULATE>(c, accumulate(t), io);
   }
   {
     LaunchTimer tm(c, GPX_TIMER_ACQ);
-    multi_bound_select_kernel<<<blocks, WG, 0, c->stream>>>(fs, ps.desc, ps.tau, w.ph.survivors, ps.count);
+    FinalizeIo sel = io;
+    sel.cols.list0 = w.ph.survivors;  // (the descriptor's list is -1: the survivors go to list0)
+    sel.bound = {ps.count, ps.tau};
+    launch_finalize<FIN_BOUND_ACC>(c, fs, sel);
   }
-  sel.desc = ps.desc + 1;
-  sel.list2 = w.ph.survivors;
+  io.part.nI = nI;
+  io.cols.desc = ps.desc + 1;
+  io.cols.list2 = w.ph.survivors;
   for (int t = 0; t < T; ++t) {
     const SweepModel M = model(t);
-    KstarAux aux{};
-    aux.list = reinterpret_cast<const int*>(w.ph.survivors);
-    aux.lstride = 2;
-    aux.count = ps.count;
-    aux.first = 0;
-    aux.cap = sp.ncols;
-    aux.pad = reinterpret_cast<int*>(w.ph.survivors);
-    aux.desc = ps.desc + 1;
-    aux.rcount = ps.count + 1;
-    aux.stats = ps.stats;
-    aux.rows0 = nI;
-    aux.last = t == T - 1;  // (the survivors count as computed to the end once, with the last output)
-    aux.mu_out = b.mu_part;
-    aux.ldmu = C;
-    launch_kstar(M, q.first(sp.ncols), b, KSTAR_GATHER, aux);
+    // (last: the survivors count as computed to the end once, with the last output)
+    launch_kstar(M, q.first(sp.ncols), b, KSTAR_GATHER,
+                 gather_aux(w.ph.survivors, ps.count, 0, sp.ncols, ps, nI, t == T - 1, b.mu_part, C));
     LaunchTimer tm(c, GPX_TIMER_TRMM);
     const PruneStage st{prune_bufs(b.kstar, C, ps, w.ph.survivors), ps.desc + 1, 0, nI, 0};
     launch_tail_stage(c, M.W, M.ldw, C, nI, b.ss_part, st, tiles);
-    finalize_kernel<<<blocks, WG, 0, c->stream>>>(accumulate(t), 2, q.Xs, q.ldxs, q.m, C, 1, nJB, nI, b.mu_part,
-                                                  b.ss_part, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
-                                                  q.index_offset, sel);
+    launch_finalize<FIN_ACCUMULATE>(c, accumulate(t), io);
   }
-  score(sp.ncols, sel);
+  score(sp.ncols, io.cols);
   return hipGetLastError();
 }
 
@@ -2389,15 +2380,7 @@ __global__ void __launch_bounds__(WG) svgp_finalize_kernel(gpx_kernel_params p, 
                                                            double* __restrict__ score) {
   const int64_t c = (int64_t)blockIdx.x * WG + threadIdx.x;
   if (c >= m_chunk) return;
-  double kd = p.outputscale;
-  if (p.kind == GPX_KERNEL_SCALE_LINEAR_MATERN52) {
-    double lv = 0.0;
-    for (int k = 0; k < p.d; ++k) {
-      const double v = Xs[c * ldxs + k];
-      lv += v * v * p.linear_variance[k];
-    }
-    kd = p.outputscale * (lv + 1.0);
-  }
+  const double kd = prior_variance(p, Xs, ldxs, c);
   const double s1 = sum_partials(ss1 + c, nI, C);
   const double s2 = sum_partials(ss2 + c, nI, C);
   const double var = fmax(kd - s1 + s2 + p.noise, min_var);
@@ -2409,8 +2392,8 @@ __global__ void __launch_bounds__(WG) svgp_finalize_kernel(gpx_kernel_params p, 
 
 // One task of gpx_svgp_acquire_f64's objective in svgp_finalize_kernel's place: the task's LATENT moments from the same
 // partials in the same operation order (no likelihood noise: an analytic acquisition is about f; GPyTorch's 1e-10
-// floor), untransformed and weighted into the chunk's accumulators exactly as finalize_kernel's mode 2 does it.  Mode 3
-// scores them (launch_multi_score): objective_moments and acq_score stay the only statements of the floors and formulas.
+// floor), into the chunk's accumulators by FIN_ACCUMULATE's own step (accumulate_output).  FIN_SCORE_ACC scores them
+// (launch_multi_score): objective_moments and acq_score stay the only statements of the floors and formulas.
 __global__ void __launch_bounds__(WG) svgp_objective_kernel(gpx_kernel_params p, MultiOutput mo,
                                                             const double* __restrict__ Xs, int64_t ldxs,
                                                             int64_t m_chunk, int64_t C, int nJB, int nI,
@@ -2419,24 +2402,12 @@ __global__ void __launch_bounds__(WG) svgp_objective_kernel(gpx_kernel_params p,
                                                             const double* __restrict__ ss2) {
   const int64_t c = (int64_t)blockIdx.x * WG + threadIdx.x;
   if (c >= m_chunk) return;
-  double kd = p.outputscale;
-  if (p.kind == GPX_KERNEL_SCALE_LINEAR_MATERN52) {
-    double lv = 0.0;
-    for (int k = 0; k < p.d; ++k) {
-      const double v = Xs[c * ldxs + k];
-      lv += v * v * p.linear_variance[k];
-    }
-    kd = p.outputscale * (lv + 1.0);
-  }
+  const double kd = prior_variance(p, Xs, ldxs, c);
   const double s1 = sum_partials(ss1 + c, nI, C);
   const double s2 = sum_partials(ss2 + c, nI, C);
-  double var = fmax(kd - s1 + s2, 1e-10);  // gpytorch min_variance (float64) [upstream]
-  double mu = sum_partials(mu_part + c, nJB, C) + p.const_mean;
-  mu = mo.y_mean + mo.y_scale * mu;
-  var = var * (mo.y_scale * mo.y_scale);
-  const double wm = mo.weight * mu, wv = (mo.weight * mo.weight) * var;
-  mo.acc_mu[c] = mo.first ? wm : mo.acc_mu[c] + wm;
-  mo.acc_var[c] = mo.first ? wv : mo.acc_var[c] + wv;
+  const double var = fmax(kd - s1 + s2, 1e-10);  // gpytorch min_variance (float64) [upstream]
+  const double mu = sum_partials(mu_part + c, nJB, C) + p.const_mean;
+  accumulate_output(mo.acc_mu, mo.acc_var, c, mo.first, mo.weight, mo.y_mean, mo.y_scale, mu, var);
 }
 
 // (mo: gpx_svgp_acquire_f64's form; min_var, task and the output pointers are then not used)

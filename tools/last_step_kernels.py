@@ -6,7 +6,8 @@
 The last traced step is the library's launches from the last Gram launch on.  One JSON line: per kernel its launches and
 their time, and apart the launches under 8 us (the empty tail rounds' and other tiny ones).
 """
-import csv, json, re, sys, collections
+import csv, json, sys, collections
+from trace_names import kernel_name
 rows = sorted(csv.DictReader(open(sys.argv[1])), key=lambda r: int(r["Start_Timestamp"]))
 names = [r["Kernel_Name"] for r in rows]
 start = [i for i, n in enumerate(names) if "gram" in n and "gpx::" in n][-1]
@@ -16,7 +17,7 @@ for r in rows[start:]:
     nm = r["Kernel_Name"]
     if "gpx::" not in nm:
         continue
-    nm = re.sub(r"^void ", "", nm).split("(")[0]
+    nm = kernel_name(nm)
     d = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
     a = agg.setdefault(nm, [0, 0.0, 0, 0.0])
     a[0] += 1; a[1] += d

@@ -30,7 +30,7 @@ a = ap.parse_args()
 SEED, EPS, BLK = 1024, 1e-9, 1 << 15
 
 
-def keeps(U, tau):  # finalize_kernel mode 4's test
+def keeps(U, tau):  # the bound passes' test (bound_keeps in gpx_sweep.hip)
     return ~(U + EPS * (np.abs(U) + abs(tau) + 1.0) < tau)
 
 

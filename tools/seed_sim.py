@@ -25,7 +25,7 @@ a = ap.parse_args()
 D, SEED, EPS = 8, 1024, 1e-9
 
 
-def keeps(U, tau):  # finalize_kernel mode 4's test
+def keeps(U, tau):  # the bound passes' test (bound_keeps in gpx_sweep.hip)
     return ~(U + EPS * (np.abs(U) + abs(tau) + 1.0) < tau)
 
 

@@ -16,11 +16,13 @@ import csv
 import sys
 from collections import defaultdict
 
+from trace_names import kernel_name
+
 TAIL = ("kstar_mfma_kernel", "trmm_stage_dual_kernel", "finalize_kernel", "prune_compact_kernel", "topk_pool_kernel")
 
 
 def short(name):
-    return name.split("(")[0].replace("void ", "").replace("gpx::", "")
+    return kernel_name(name).replace("gpx::", "")
 
 
 def main():

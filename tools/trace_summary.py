@@ -2,6 +2,8 @@
 import csv
 import sys
 
+from trace_names import kernel_name
+
 rows = list(csv.DictReader(open(sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/trace/fit_kernel_trace.csv")))
 names = [r["Kernel_Name"] for r in rows]
 start = [i for i, n in enumerate(names) if "gram_kernel" in n][-1]
@@ -9,7 +11,7 @@ seq = rows[start:]
 prev = int(seq[0]["Start_Timestamp"])
 for r in seq:
     s, e = int(r["Start_Timestamp"]), int(r["End_Timestamp"])
-    nm = r["Kernel_Name"].split("(")[0].replace("void ", "")
+    nm = kernel_name(r["Kernel_Name"])
     if "potrf_step" in nm or "mll_" in nm:
         continue
     if "gpx::" not in nm:
