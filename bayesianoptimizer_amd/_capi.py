@@ -291,6 +291,9 @@ _PROTOS = {
                                                   c_int64, _p, c_int64, _p, _p, c_int64, _p, _p]),
     "gpx_debug_set_sweep_order": (c_int32, [_h, c_int32]),
     "gpx_debug_get_sweep_order": (c_int32, [_h, POINTER(c_int32)]),
+    "gpx_debug_set_sweep_tail_sync": (c_int32, [_h, c_int32]),
+    "gpx_debug_get_sweep_tail_sync": (c_int32, [_h, POINTER(c_int32)]),
+    "gpx_debug_get_tail_rounds": (c_int32, [_h, POINTER(c_int64)]),
     "gpx_debug_stage_product_workspace_size": (c_int32, [c_int64, POINTER(c_size_t)]),
     "gpx_debug_stage_product_f64": (c_int32, [_h, c_int64, _p, c_int64, _p, c_int64, c_int64, _p, c_int32, c_int32,
                                               c_int32, _p, c_int64, _p, c_size_t]),

@@ -151,6 +151,16 @@ gpx_status gpx_create(int32_t device, gpx_handle* out) {
       delete c;
       return GPX_HIP_ERROR;
     }
+    // the pruned sweep's read-back of a span's survivor count (launch_sweep_super_pruned): a pinned word and an event
+    void* word = nullptr;
+    if (hipHostMalloc(&word, 64, hipHostMallocDefault) != hipSuccess ||
+        hipEventCreateWithFlags(&c->tail_event, hipEventDisableTiming) != hipSuccess) {
+      if (word) (void)hipHostFree(word);
+      delete c;
+      return GPX_HIP_ERROR;
+    }
+    c->tail_count = static_cast<int32_t*>(word);
+    *c->tail_count = 0;
   }
   *out = reinterpret_cast<gpx_handle>(c);
   return GPX_OK;
@@ -165,6 +175,8 @@ gpx_status gpx_destroy(gpx_handle h) {
     (void)hipEventDestroy(pt.stop);
   }
   for (auto ev : c->free_events) (void)hipEventDestroy(ev);
+  if (c->tail_event) (void)hipEventDestroy(c->tail_event);
+  if (c->tail_count) (void)hipHostFree(c->tail_count);
   delete c;
   return GPX_OK;
 }
@@ -1141,6 +1153,8 @@ static gpx_status acquire_impl(gpx_handle h, const gpx_kernel_params* p, int64_t
   // [3]: the tiles of the full sweep, with the full path's chunking
   c->sweep_stats[3] = fused ? 0 : m / b.chunk * tiles(b.chunk) + tiles(m % b.chunk);
   c->sweep_stats_dev = prune ? w.ps.stats : nullptr;
+  c->tail_rounds[0] = c->tail_rounds[1] = 0;
+  c->tail_rounds[2] = -1;
   // spans of a chunk, or on the lazy path of a super-chunk (sweep_span_size)
   const gpx::SweepModel M{c, *p, (int)n, (int)npad, X, ldx, W, ldw, alpha, 1};
   int64_t rec = 0;
@@ -1285,6 +1299,30 @@ gpx_status gpx_debug_get_sweep_order(gpx_handle h, int32_t* value_host) {
   if (!c) return GPX_INVALID_ARG;
   GPX_NONNULL(c, value_host);
   *value_host = c->sweep_order;
+  return GPX_OK;
+}
+
+gpx_status gpx_debug_set_sweep_tail_sync(gpx_handle h, int32_t value) {
+  Context* c = reinterpret_cast<Context*>(h);
+  if (!c) return GPX_INVALID_ARG;
+  if (value != 0 && value != 1) return fail(c, GPX_INVALID_ARG, "sweep_tail_sync must be 0 or 1");
+  c->sweep_tail_sync = value;
+  return GPX_OK;
+}
+
+gpx_status gpx_debug_get_sweep_tail_sync(gpx_handle h, int32_t* value_host) {
+  Context* c = reinterpret_cast<Context*>(h);
+  if (!c) return GPX_INVALID_ARG;
+  GPX_NONNULL(c, value_host);
+  *value_host = c->sweep_tail_sync;
+  return GPX_OK;
+}
+
+gpx_status gpx_debug_get_tail_rounds(gpx_handle h, int64_t* out) {
+  Context* c = reinterpret_cast<Context*>(h);
+  if (!c) return GPX_INVALID_ARG;
+  GPX_NONNULL(c, out);
+  for (int i = 0; i < 3; ++i) out[i] = c->tail_rounds[i];
   return GPX_OK;
 }
 

@@ -63,6 +63,14 @@ struct Context {
                            // 0 the K* launch and the first stage apart
   int sweep_order = 1;     // (gpx_debug_set_sweep_order, no option slot) seeded lazy pruned sweep: 1 mean-first (prune on the mean's bound with
                            // the prior variance, the head over what is left), 0 the head over every column first
+  int sweep_tail_sync = 1;  // (gpx_debug_set_sweep_tail_sync, no option slot) lazy pruned sweep's tail: 1 the host reads a span's
+                           // survivor count back and enqueues only the rounds it needs, 0 the worst case, never waiting
+  // the read-back's pinned host word and the event behind its copy (gpx_create .. gpx_destroy)
+  int32_t* tail_count = nullptr;
+  hipEvent_t tail_event = nullptr;
+  // gpx_debug_get_tail_rounds of the last acquire or top-k call, summed over its spans: tail rounds enqueued, their
+  // worst case, the survivor counts read back (-1: none was)
+  int64_t tail_rounds[3] = {0, 0, -1};
   // gpx_sweep_stats of the last acquire call: the host-known parts, plus the device counters of the pruned path
   // ({candidates computed to the last row tile, product tiles executed}; they live in that call's workspace)
   int64_t sweep_stats[4] = {0, 0, 0, 0};

@@ -2043,10 +2043,15 @@ hipError_t launch_sweep_chunk_pruned(const SweepModel& M, const SweepCands& q, c
 //  tail   rounds of at most C survivors: KSTAR_GATHER rebuilds their full-height columns into the chunk buffer (the bits
 //         of the full build) and, after a mean bound, their exact mean partials into ph.mu_part, then the staged pipeline
 //         of launch_sweep_chunk_pruned (launch_stages) from row tile 1 on, the partials
-//         going to the columns' own places in ph.ss_part.  The host cannot know the survivor count, so the worst-case
-//         number of rounds is enqueued and the workgroups of an empty round return at once; the rounds after the first
-//         therefore take fewer, coarser stages (the stage grouping does not change a column's partials).
-// *recs: records used so far (in ph.rec_val / ph.rec_idx).
+//         going to the columns' own places in ph.ss_part.  A span of at most C staged columns has one round and the call
+//         stays asynchronous.  A longer one can need up to ceil(ncols / C); the host learns how many (sweep_tail_sync 1,
+//         the default): behind the last pass that writes the survivor count ps.count[0] a 4-byte copy takes it to the
+//         handle's pinned word with an event behind it, round 0 is enqueued as ever, so the device has work while the
+//         host waits for the event, and rounds 1 .. sweep_tail_rounds(count) - 1 follow, mostly none.  With
+//         sweep_tail_sync 0, or on a stream that is being captured, the worst case is enqueued and the workgroups of an
+//         empty round return at once.  Either way the rounds after the first take fewer, coarser stages (the stage
+//         grouping does not change a column's partials), and a round that is enqueued is the same launches in both.
+// *recs: records used so far (in ph.rec_val / ph.rec_idx); it advances for the rounds enqueued only.
 bool sweep_lazy_ok(const gpx_kernel_params& p) { return !p.cov_fp32 && p.d <= 16; }
 
 hipError_t launch_sweep_super_pruned(const SweepModel& M, const SweepCands& q, const SweepBuffers& b,
@@ -2174,8 +2179,38 @@ hipError_t launch_sweep_super_pruned(const SweepModel& M, const SweepCands& q, c
     io.bound = {ps.count, ps.tau, ph.mu_part + 2 * MA};
     launch_finalize<FIN_BOUND>(c, fa, io);
   }
-  // tail (its passes read the survivors' exact partials, written by their gather)
+  // tail (its passes read the survivors' exact partials, written by their gather).  Nothing from here on writes
+  // ps.count[0] (the rounds' counts start at ps.count + 1), so a span that can need more than one round sends the count
+  // to the host now, behind the last pass that wrote it; round 0 is enqueued before the host waits for it.
+  const int64_t worst = (sp.ncols + C - 1) / C;
+  int64_t rounds = worst;
+  bool readback = worst > 1 && c->sweep_tail_sync && c->tail_count && c->tail_event;
+  if (readback) {
+    // (a wait on an event recorded during capture is an error, and a captured call must replay for any count)
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(c->stream, &cap) != hipSuccess) {
+      (void)hipGetLastError();
+      readback = false;
+    } else if (cap != hipStreamCaptureStatusNone) {
+      readback = false;
+    }
+  }
+  if (readback) {
+    hipError_t e = hipMemcpyAsync(c->tail_count, ps.count, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipEventRecord(c->tail_event, c->stream);
+    if (e != hipSuccess) return e;
+  }
+  c->tail_rounds[1] += worst;
   for (int64_t r0 = 0; r0 < sp.ncols; r0 += C) {
+    if (r0 == C && readback) {
+      const hipError_t e = hipEventSynchronize(c->tail_event);
+      if (e != hipSuccess) return e;
+      const int64_t count = *static_cast<volatile int32_t*>(c->tail_count);
+      c->tail_rounds[2] = (c->tail_rounds[2] < 0 ? 0 : c->tail_rounds[2]) + count;
+      rounds = sweep_tail_rounds(count, sp.ncols, C);
+    }
+    if (r0 / C >= rounds) break;
+    ++c->tail_rounds[0];
     const int cap = (int)(sp.ncols - r0 < C ? sp.ncols - r0 : C);  // the most columns this round can have
     // stage boundaries Rr[0] = 1 < .. < Rr[ns] = nI: round 0 the doubling ones, later rounds 1 < 4 < nI
     int Rr[PRUNE_MAX_STAGES], ns = 0;

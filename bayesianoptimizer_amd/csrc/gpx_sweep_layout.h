@@ -73,6 +73,15 @@ inline int64_t sweep_lazy_records(int64_t npad, int64_t m) {
   const int64_t supers = (m + MA - 1) / MA + 1, rounds = (MA + C - 1) / C;  // (+ 1: room the spans no longer need since the first became a whole one; the reported sizes are pinned)
   return PRUNE_SEED / WG + supers * rounds * (C / WG);
 }
+// Tail rounds of a lazy span with `count` survivors among its ncols staged columns, C at most per round: one at least
+// (round 0 is enqueued before the count is known), and never more than the span's worst case.  A count outside
+// [0, ncols] cannot come from the passes that write it; it gets the worst case.
+inline int64_t sweep_tail_rounds(int64_t count, int64_t ncols, int64_t C) {
+  const int64_t worst = (ncols + C - 1) / C;
+  if (count < 0 || count > ncols) return worst;
+  const int64_t need = count < 1 ? 1 : (count + C - 1) / C;
+  return need < worst ? need : worst;
+}
 // The compact K* buffers hold C/2 and C/4 columns, rounded up to the tile (a compaction at least halves the active
 // columns, so they alternate: DESIGN §3).
 inline int64_t prune_ld(int64_t C, int which) {

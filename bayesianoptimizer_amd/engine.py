@@ -153,6 +153,9 @@ class SVGPTaskState:
         return self.prep["alpha"][self.task]
 
 
+_DEBUG_SWITCHES = ("sweep_head", "sweep_order", "sweep_tail_sync")  # gpx_debug_set_* / gpx_debug_get_*, no option slot
+
+
 def _ptr(t: Optional[torch.Tensor]):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
@@ -218,16 +221,17 @@ class GPEngine:
     # -- fit --------------------------------------------------------------------------------------
     def set_option(self, name: str, value: int) -> None:
         """Per-handle tuning / diagnostic option (include/gpx.h GPX_OPT_*, by the names of _capi.OPTIONS: spin_limit,
-        sweep_fused, gram_split, potrf_lazy, potrf_mode, potrf_switch, potrf_split, sweep_prune), and "sweep_head" and
-        "sweep_order", the A/B switches of the lazy pruned sweep's head and of its seeded order (gpx_debug_set_sweep_head,
-        gpx_debug_set_sweep_order: they have no option slot)."""
-        if name in ("sweep_head", "sweep_order"):
+        sweep_fused, gram_split, potrf_lazy, potrf_mode, potrf_switch, potrf_split, sweep_prune), and "sweep_head",
+        "sweep_order" and "sweep_tail_sync", the A/B switches of the lazy pruned sweep's head, of its seeded order and of
+        its tail's read-back (gpx_debug_set_sweep_head, gpx_debug_set_sweep_order, gpx_debug_set_sweep_tail_sync: they
+        have no option slot)."""
+        if name in _DEBUG_SWITCHES:
             self._check(getattr(self.lib, f"gpx_debug_set_{name}")(self.handle, int(value)))
             return
         self._check(self.lib.gpx_set_option(self.handle, _capi.OPTIONS[name], int(value)))
 
     def get_option(self, name: str) -> int:
-        if name in ("sweep_head", "sweep_order"):
+        if name in _DEBUG_SWITCHES:
             h = ctypes.c_int32()
             self._check(getattr(self.lib, f"gpx_debug_get_{name}")(self.handle, ctypes.byref(h)))
             return int(h.value)
@@ -569,7 +573,12 @@ class GPEngine:
     def acquire(self, state: GPState, Xs, kind: Union[str, int] = "logei", best_f: float = 0.0, beta: float = 4.0,
                 y_mean: float = 0.0, y_scale: float = 1.0, alpha: Optional[torch.Tensor] = None,
                 index_offset: int = 0, return_scores: bool = False):
-        """Score every candidate and return device scalars (best_value, best_index) (+ scores)."""
+        """Score every candidate and return device scalars (best_value, best_index) (+ scores).
+
+        Asynchronous on the stream, with one exception: a call the lazy pruned sweep takes (padded n >= 384) with more
+        candidates than a chunk holds waits once per span for the span's survivor count, a 4-byte copy, and enqueues
+        only the tail rounds the count needs.  ``set_option("sweep_tail_sync", 0)`` enqueues the worst case instead
+        and never waits; so does a call on a stream that is being captured.  ``acquire_topk`` behaves the same."""
         Xs = self._as_f64(Xs, "Xs")
         if Xs.shape[1] != state.d:
             raise ValueError(f"Xs has {Xs.shape[1]} columns, model has d={state.d}")
@@ -644,6 +653,13 @@ class GPEngine:
         128x128 product tiles executed (summed over the outputs), tiles of the full sweep)."""
         out = (ctypes.c_int64 * 4)()
         self._check(self.lib.gpx_sweep_stats(self.handle, out))
+        return tuple(int(v) for v in out)
+
+    def tail_rounds(self):
+        """(tail rounds enqueued, their worst case, sum of the survivor counts read back or -1) of the last `acquire` /
+        `acquire_topk` call, summed over its spans (gpx_debug_get_tail_rounds: host-side values, no synchronisation)."""
+        out = (ctypes.c_int64 * 3)()
+        self._check(self.lib.gpx_debug_get_tail_rounds(self.handle, out))
         return tuple(int(v) for v in out)
 
     def acquire_multi(self, states: Sequence[GPState], Xs, kind: Union[str, int] = "logei", best_f: float = 0.0,

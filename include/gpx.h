@@ -16,7 +16,9 @@
  *    the identity, so L, L^{-1} and alpha are exact block extensions of the unpadded ones.  Buffers named
  *    "padded" must have gpx_padded_n(n) rows/cols.
  *  - Calls are asynchronous on the handle's stream (gpx_set_stream) and never allocate device memory;
- *    scratch comes from the caller's workspace (size from the *_workspace_size queries).  A workspace's contents on
+ *    scratch comes from the caller's workspace (size from the *_workspace_size queries).  The calls that say so
+ *    synchronise; gpx_acquire_argmax_f64 and gpx_acquire_topk_f64 wait once for a 4-byte read-back in the calls
+ *    described at gpx_debug_set_sweep_tail_sync.  A workspace's contents on
  *    entry are arbitrary, and its address needs only 8-byte alignment.
  *  - Errors: return a gpx_status; gpx_last_error(h) gives a message.  NOT_PD is reported through a device
  *    int32 `info` (0 = OK, > 0 failing pivot + 1, LAPACK potrf convention) so the fit stays asynchronous;
@@ -329,7 +331,9 @@ gpx_status gpx_posterior_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n
  * The returned pair is exact: without scores_out the sweep may stop a candidate's variance product early once an upper
  * bound of its score (every acquisition here grows with the variance, and the variance only shrinks as the product
  * proceeds) lies below a score already computed in full; such a candidate cannot be the argmax, and the pair has the
- * bits of the full sweep (GPX_OPT_SWEEP_PRUNE = 0).  scores_out != NULL forces the full sweep: every score is wanted. */
+ * bits of the full sweep (GPX_OPT_SWEEP_PRUNE = 0).  scores_out != NULL forces the full sweep: every score is wanted.
+ * Asynchronous, except that a call of the lazy pruned sweep with more candidates than one of its chunks holds waits
+ * once per such span for the survivor count (gpx_debug_set_sweep_tail_sync; never on a stream in capture). */
 gpx_status gpx_acquire_argmax_f64(gpx_handle h, const gpx_kernel_params* p, int64_t n, const double* X,
                                   int64_t ldx, const double* W, int64_t ldw, const double* alpha,
                                   const double* Xs, int64_t m, int64_t ldxs, const gpx_acq_params* a,
@@ -352,9 +356,9 @@ gpx_status gpx_sweep_stats(gpx_handle h, int64_t* out_host);
  * n < 384) the call runs the full sweep into a score array of its own workspace and gpx_topk_f64's sort.
  * Arguments and validation as gpx_acquire_argmax_f64, plus 1 <= k <= min(m, GPX_TOPK_SWEEP_MAX): the pruned sweep
  * scores its leading GPX_TOPK_SWEEP_MAX candidates in full before its first bound pass, which fills the pool of the k
- * best for every legal k.  Asynchronous on the handle's stream, no allocation, no host synchronisation, the same bits
- * on every call.  gpx_acquire_topk_workspace_size: gpx_sweep_workspace_size(n, 1, m) plus the top-k part (a 256-byte
- * header, the pool of k 16-byte pairs, one 16-byte scored-list entry per candidate of a sweep chunk, the composed
+ * best for every legal k.  Asynchronous on the handle's stream but for the wait gpx_acquire_argmax_f64 names, no
+ * allocation, the same bits on every call.  gpx_acquire_topk_workspace_size: gpx_sweep_workspace_size(n, 1, m) plus
+ * the top-k part (a 256-byte header, the pool of k 16-byte pairs, one 16-byte scored-list entry per candidate of a sweep chunk, the composed
  * path's m scores and gpx_topk_workspace_size(m), each rounded up to 256 bytes). */
 enum { GPX_TOPK_SWEEP_MAX = 1024 };
 gpx_status gpx_acquire_topk_workspace_size(int64_t n, int64_t m, int64_t k, size_t* bytes);
@@ -819,6 +823,19 @@ gpx_status gpx_debug_head_product_list_f64(gpx_handle h, const gpx_kernel_params
  * way; gpx_sweep_stats [1] and [2] count what ran.  Any other value is GPX_INVALID_ARG. */
 gpx_status gpx_debug_set_sweep_order(gpx_handle h, int32_t value);
 gpx_status gpx_debug_get_sweep_order(gpx_handle h, int32_t* value_host);
+/* The tail of the lazy pruned sweep (gpx_acquire_argmax_f64 and gpx_acquire_topk_f64 at padded n >= 384; no
+ * slot among GPX_OPT_*).  1 (default): in every span whose survivors could need more than one round (more staged columns
+ * than a chunk holds) the call copies the span's survivor count to the host, enqueues the first round, waits for the
+ * copy (hipEventSynchronize: the call blocks the calling thread once per such span) and enqueues only the rounds the
+ * count needs.  0: the worst-case number of rounds is enqueued and the call never waits.  A call on a stream that is
+ * being captured behaves as 0, so a captured graph replays for any count.  The same results and gpx_sweep_stats either
+ * way.  Any other value is GPX_INVALID_ARG. */
+gpx_status gpx_debug_set_sweep_tail_sync(gpx_handle h, int32_t value);
+gpx_status gpx_debug_get_sweep_tail_sync(gpx_handle h, int32_t* value_host);
+/* Of the handle's last gpx_acquire_argmax_f64 or gpx_acquire_topk_f64 call, summed over its spans: out[0] tail rounds
+ * enqueued, out[1] their worst case, out[2] the survivor counts read back (-1: no span read one back).  All 0, 0, -1
+ * where the lazy pruned sweep did not run.  Host-side values: no synchronisation, no device access. */
+gpx_status gpx_debug_get_tail_rounds(gpx_handle h, int64_t* out);
 /* One stage of the pruned sweep's product in a named tile shape, for bit checks (no production path uses it; DESIGN
  * §3): row tiles I0 .. I0 + nrows - 1 of V = W^T K* over slots 0 .. ncols - 1 of a caller's K* buffer.  W: device,
  * padded_n x padded_n upper triangular (pitch ldw), kstar: device, padded_n rows of pitch ldk >= ncols rounded up to

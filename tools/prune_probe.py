@@ -1,11 +1,13 @@
 """Sweep-only timings of the pruned acquisition sweep (2^20 candidates, d = 8, RBF, logEI), one JSON line per case:
-[ms of each repetition], sweep_stats, (best value, best index).  Cases: 2^20 identical candidates at n = 4096 (nothing
-prunable) with sweep_prune 0 / 1, the bench problem (seed 0), the seed-1000 problem, and padded n = 384 .. 2048 with
+[ms of each repetition], sweep_stats, (best value, best index), [host wall ms of each repetition: the call followed by
+a device synchronise, which also sees a wait inside the call that device events do not].  Cases: 2^20 identical
+candidates at n = 4096 (nothing prunable) with sweep_prune 0 / 1, the bench problem (seed 0), the seed-1000 problem, and padded n = 384 .. 2048 with
 sweep_prune 0 / 2.  The library is the tree's, or GPX_LIB's (A/B runs alternate processes)."""
 import argparse
 import json
 import os
 import sys
+import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -27,16 +29,18 @@ def run(name, st, Xs, best_f, opt):
     eng.set_option("sweep_prune", opt)
     eng.acquire(st, Xs, "logei", best_f=best_f)  # warm-up (workspace, code objects)
     torch.cuda.synchronize()
-    ms = []
+    ms, wall = [], []
     for _ in range(a.reps):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
         e0.record()
         bv, bi = eng.acquire(st, Xs, "logei", best_f=best_f)
         e1.record()
-        e1.synchronize()
+        torch.cuda.synchronize()
+        wall.append(1e3 * (time.perf_counter() - t0))
         ms.append(e0.elapsed_time(e1))
-    print(json.dumps([f"{a.tag}{name}_opt{opt}", ms, list(eng.sweep_stats()), [float(bv.item()), int(bi.item())]]),
-          flush=True)
+    print(json.dumps([f"{a.tag}{name}_opt{opt}", ms, list(eng.sweep_stats()), [float(bv.item()), int(bi.item())],
+                      wall]), flush=True)
 
 
 def problem(n, seed):
