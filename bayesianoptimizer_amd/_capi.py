@@ -269,6 +269,10 @@ _PROTOS = {
     "gpx_svgp_bound_grad_z_f64": (c_int32, [_h, POINTER(KernelParamsC), c_int64, c_int64, c_double, _p, c_int64,
                                             c_int64, _p, c_int64, c_int64, _p, c_int64, _p, _p, c_int64, c_int64, _p,
                                             _p, c_size_t]),
+    "gpx_svgp_condition_workspace_size": (c_int32, [c_int64, c_int64, c_int64, c_int64, POINTER(c_size_t)]),
+    "gpx_svgp_condition_f64": (c_int32, [_h, POINTER(KernelParamsC), c_int64, c_int64, _p, c_int64, c_int64, _p, _p,
+                                         _p, _p, c_int64, c_int64, _p, c_int64, _p, _p, _p, c_int64, _p, c_int64,
+                                         c_int64, _p, _p, _p, _p, c_size_t]),
     "gpx_topk_workspace_size": (c_int32, [c_int64, POINTER(c_size_t)]),
     "gpx_topk_f64": (c_int32, [_h, _p, c_int64, c_int64, _p, _p, _p, c_size_t]),
     "gpx_fps_f64": (c_int32, [_h, _p, c_int64, c_int64, c_int64, c_int64, c_int64, _p]),

@@ -11,7 +11,7 @@ import sys
 
 ASM_TILE_KERNELS = ("trmm_sumsq_kernel", "trmm_stage_kernel", "trmm_stage_dual_kernel", "potrf_step_kernel",
                     "mll_grad_kernel", "svgp_w2_kernel", "trtri_t_kernel", "trtri_w_kernel", "svgp_project_kernel",
-                    "svgp_syrk_kernel", "svgp_mm_kernel", "svgp_grad_kernel")
+                    "svgp_syrk_kernel", "svgp_mm_kernel", "svgp_grad_kernel", "svgp_compose_kernel")
 # No asm loads, but 128 accumulator registers per lane at two waves per SIMD: a spill would sit in the k loop.
 NO_SPILL_KERNELS = ("head_product_kernel",)
 

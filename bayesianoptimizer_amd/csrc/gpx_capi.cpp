@@ -1865,6 +1865,8 @@ gpx_status check_svgp_data(Context* c, const gpx_kernel_params* p, int64_t ntask
     if (!(p[t].noise > 0.0)) return fail(c, GPX_INVALID_ARG, "the likelihood noise must be positive");
   return GPX_OK;
 }
+gpx_status svgp_system_tail(Context* c, const gpx_kernel_params* p, int64_t ntask, int64_t Mpad, const int32_t* info,
+                            int32_t* info2, const SvgpWorkspace& w, const gpx::Batch& bt);
 // The fit's launches up to m' (arguments checked by the entry points; the device is current): on return, per task, A
 // holds L' (B' = L' L'^T), Wb holds W' = L'^{-T}, and bvec / u / mrev / scal are final.  Where the layout has Wk and Bc
 // (the gradient's), they get copies of W = L_ZZ^{-T} and of B' before those are overwritten.
@@ -1908,7 +1910,16 @@ gpx_status svgp_fit_core(Context* c, const gpx_kernel_params* p, int64_t ntask, 
                                            w.task(0, SV_A), tstride),
                       "svgp fit rank update"));
   }
-  // B' = I + B_acc / s2 = L' L'^T and W' = L'^{-T} (in reversed index order), batched over the tasks
+  return svgp_system_tail(c, p, ntask, Mpad, info, info2, w, bt);
+}
+// The tail of the fit and of the conditioning call behind their chunk loops: from the tasks' accumulators B_acc (in A)
+// and b_acc (in bvec), B' = I + B_acc / s2 = L' L'^T and W' = L'^{-T} (in reversed index order), batched over the tasks,
+// then u and m'.  info: the words svgp_bfinal_kernel reads (a task with info != 0 gets B' = I, b' = 0); info2: the
+// factorisation's (they may be the same words: the launches run in stream order).
+gpx_status svgp_system_tail(Context* c, const gpx_kernel_params* p, int64_t ntask, int64_t Mpad, const int32_t* info,
+                            int32_t* info2, const SvgpWorkspace& w, const gpx::Batch& bt) {
+  using namespace gpx;  // (the region names)
+  const int64_t tstride = w.pitch();
   for (int64_t t = 0; t < ntask; ++t)
     GPX_TRY(hip_check(c,
                       launch_svgp_fit_system(c, (int)Mpad, p[t].noise, info + t, w.task(t, SV_A), w.task(t, SV_BVEC),
@@ -1968,6 +1979,114 @@ gpx_status gpx_svgp_fit_collapsed_f64(gpx_handle h, const gpx_kernel_params* p, 
                                              bound + t * GPX_SVGP_BOUND_NOUT),
                       "svgp fit finish"));
   return GPX_OK;
+}
+
+// ---- Conditioning the sparse model on new data (gpx_svgpcond.hip): the fit's chunk loop with W2^T K in
+// ---- Phi's place and the residual against the current mean, the shared tail, then the compose products ------------
+gpx_status gpx_svgp_condition_workspace_size(int64_t M, int64_t n_new, int64_t ntask, int64_t chunk, size_t* bytes) {
+  int64_t C = svgp_size_chunk(M, n_new, ntask, chunk, bytes);
+  if (!C || n_new > ((int64_t)1 << 30)) return GPX_INVALID_ARG;
+  if (C > up128(n_new)) C = up128(n_new);
+  *bytes = gpx::svgp_layout(gpx::SVGP_CONDITION, padded(M), ntask, C).total + 256;
+  return GPX_OK;
+}
+
+gpx_status gpx_svgp_condition_f64(gpx_handle h, const gpx_kernel_params* p, int64_t ntask, int64_t M, const double* Z,
+                                  int64_t ldz, int64_t stride_z, const double* W, const double* W2, const double* alpha,
+                                  const double* Xn, int64_t n_new, int64_t ldx, const double* Yn, int64_t ldy,
+                                  double* W2_out, double* alpha_out, const double* vmean, int64_t stride_m,
+                                  const double* vchol, int64_t ldc, int64_t stride_c, double* vmean_out,
+                                  double* vchol_out, int32_t* info, void* ws, size_t ws_bytes) {
+  using namespace gpx;  // (the region names)
+  Context* c = reinterpret_cast<Context*>(h);
+  if (!c) return GPX_INVALID_ARG;
+  GPX_TRY(check_svgp(c, p, ntask, M));
+  GPX_NONNULL(c, Z);
+  GPX_NONNULL(c, W);
+  GPX_NONNULL(c, W2);
+  GPX_NONNULL(c, alpha);
+  GPX_NONNULL(c, Xn);
+  GPX_NONNULL(c, Yn);
+  GPX_NONNULL(c, W2_out);
+  GPX_NONNULL(c, alpha_out);
+  GPX_NONNULL(c, info);
+  GPX_NONNULL(c, ws);
+  const int nvar = (vmean != nullptr) + (vchol != nullptr) + (vmean_out != nullptr) + (vchol_out != nullptr);
+  if (nvar != 0 && nvar != 4)
+    return fail(c, GPX_INVALID_ARG, "vmean, vchol, vmean_out and vchol_out must all be set or all be NULL");
+  const bool var = nvar == 4;
+  if (n_new < 1 || n_new > ((int64_t)1 << 30)) return fail(c, GPX_INVALID_ARG, "n_new must be in [1, 2^30]");
+  GPX_TRY(check_ld(c, ldz, p[0].d, "Z", false));
+  GPX_TRY(check_ld(c, ldx, p[0].d, "Xn", false));
+  GPX_TRY(check_ld(c, ldy, ntask, "Yn", false));
+  if (ntask > 1 && stride_z < M * ldz) return fail(c, GPX_INVALID_ARG, "task stride of Z smaller than one task");
+  if (var) {
+    GPX_TRY(check_ld(c, ldc, M, "chol_variational_covar", false));
+    if (ntask > 1 && (stride_m < M || stride_c < M * ldc))
+      return fail(c, GPX_INVALID_ARG, "task strides smaller than one task");
+  }
+  for (int64_t t = 0; t < ntask; ++t)
+    if (!(p[t].noise > 0.0)) return fail(c, GPX_INVALID_ARG, "the likelihood noise must be positive");
+  if (W2_out == W2 || alpha_out == alpha || (var && (vmean_out == vmean || vchol_out == vchol)))
+    return fail(c, GPX_INVALID_ARG, "the outputs must not alias the state they are computed from");
+  const int64_t Mpad = padded(M);
+  const int64_t C = svgp_chunk_width(SVGP_CONDITION, Mpad, ntask, n_new, GPX_SVGP_FIT_CHUNK, ws_bytes);
+  if (!C) return fail(c, GPX_INVALID_ARG, "svgp condition workspace too small");
+  const SvgpWorkspace w(ws, svgp_layout(SVGP_CONDITION, Mpad, ntask, C));
+  const int64_t ldk = w.L.ldk, tstride = w.pitch(), pstride = w.phi_pitch(), mat = Mpad * Mpad;
+  GPX_USE_DEVICE(c);
+  GPX_TRY(hip_check(c, hipMemsetAsync(info, 0, sizeof(int32_t) * ntask, c->stream), "memset info"));
+  // the accumulators: P_acc, b_acc and the scalar sums
+  for (int64_t t = 0; t < ntask; ++t) {
+    GPX_TRY(hip_check(c, hipMemsetAsync(w.task(t, SV_A), 0, (size_t)mat * 8, c->stream), "memset"));
+    GPX_TRY(hip_check(c, hipMemsetAsync(w.task(t, w.L.acc), 0, w.L.acc.bytes, c->stream), "memset"));
+  }
+  // chunks outside, tasks inside, as in the fit: one fixed order of accumulation per task
+  for (int64_t s = 0; s < n_new; s += C) {
+    const int64_t mc = (n_new - s) < C ? (n_new - s) : C;
+    for (int64_t t = 0; t < ntask; ++t) {
+      GPX_TRY(hip_check(c,
+                        launch_svgp_kchunk(c, p[t], (int)M, (int)Mpad, Z + t * stride_z, ldz, alpha + t * Mpad,
+                                           Xn + s * ldx, ldx, mc, ldk, w.shared(SV_KC), w.shared(SV_MU)),
+                        "svgp condition covariance"));
+      GPX_TRY(hip_check(c,
+                        launch_svgp_cond_resid(c, p[t].const_mean, Yn + s * ldy + t, ldy, (int)mc, w.shared(SV_MU), ldk,
+                                               (int)(Mpad / gpx::NB), w.shared(SV_R)),
+                        "svgp condition residual"));
+      GPX_TRY(hip_check(c,
+                        launch_svgp_cond_project(c, (int)Mpad, W2 + t * mat, w.shared(SV_KC),
+                                                 w.shared(SV_PHI) + t * pstride, ldk, (int)mc, w.shared(SV_R),
+                                                 w.task(t, SV_BVEC)),
+                        "svgp condition projection"));
+    }
+    GPX_TRY(hip_check(c,
+                      launch_svgp_fit_syrk(c, (int)ntask, (int)Mpad, w.shared(SV_PHI), pstride, ldk, (int)mc,
+                                           w.task(0, SV_A), tstride),
+                      "svgp condition rank update"));
+  }
+  Batch bt;
+  bt.count = (int)ntask;
+  bt.k = bt.dinv = bt.ws = bt.w = tstride;
+  GPX_TRY(svgp_system_tail(c, p, ntask, Mpad, info, info, w, bt));
+  // W2_new = W2 D and C_new = C D with D = J W' J read in place; alpha'_new = alpha' + W2 g, m_new = m + C g
+  GPX_TRY(hip_check(c,
+                    launch_svgp_compose(c, (int)ntask, (int)M, (int)Mpad, W2, mat, w.task(0, SV_WB), tstride, W2_out,
+                                        Mpad, mat, false),
+                    "svgp condition W2"));
+  if (var) {
+    GPX_TRY(hip_check(c,
+                      launch_svgp_cond_pad(c, (int)ntask, (int)M, (int)Mpad, vchol, ldc, stride_c, w.task(0, SV_SPAD),
+                                           tstride),
+                      "svgp condition pad"));
+    GPX_TRY(hip_check(c,
+                      launch_svgp_compose(c, (int)ntask, (int)M, (int)Mpad, w.task(0, SV_SPAD), tstride,
+                                          w.task(0, SV_WB), tstride, vchol_out, ldc, stride_c, true),
+                      "svgp condition chol"));
+  }
+  return hip_check(c,
+                   launch_svgp_cond_finish(c, (int)ntask, (int)M, (int)Mpad, W2, alpha, w.task(0, SV_MREV), tstride,
+                                           alpha_out, vmean, stride_m, vchol, ldc, stride_c, vmean_out, info),
+                   "svgp condition finish");
 }
 
 gpx_status gpx_svgp_bound_grad_workspace_size(int64_t M, int64_t n, int64_t ntask, int64_t chunk, size_t* bytes) {

@@ -398,6 +398,27 @@ hipError_t launch_svgp_fit_finish(Context* c, int M, int Mpad, int64_t n, double
                                   int64_t ldc, double* bound);
 hipError_t launch_svgp_fit_bound(Context* c, int Mpad, int64_t n, double s2, const double* Lp, const double* u,
                                  const double* scal, double* bound);
+// Conditioning on new data (gpx_svgpcond.hip).  Per chunk and task behind launch_svgp_kchunk(alpha = the
+// task's alpha'): the residual e from the build's nJB rows of mean partials, then (gpx_svgpfit.hip) the projection
+// U' = the row-reversed W2^T K chunk over the full k range and b_acc += U' e.
+hipError_t launch_svgp_cond_resid(Context* c, double const_mean, const double* Y, int64_t ldy, int mc, const double* mu,
+                                  int64_t ldk, int nJB, double* e);
+hipError_t launch_svgp_cond_project(Context* c, int Mpad, const double* W2, const double* kc, double* phi, int64_t ldk,
+                                    int mc, const double* e, double* bacc);
+// spad = tril(vchol) zero-padded (task stride sdst doubles)
+hipError_t launch_svgp_cond_pad(Context* c, int ntask, int M, int Mpad, const double* vchol, int64_t ldc,
+                                int64_t stride_c, double* spad, int64_t sdst);
+// out = A D per task (strides sa / sw / so), D[k][j] = Wp[Mpad-1-k][Mpad-1-j] read in place.  A full: out is Mpad x Mpad
+// with exact zeros in rows / columns >= M; tri (A lower triangular): out is M x M, rows ldo apart, zeros above the
+// diagonal.
+hipError_t launch_svgp_compose(Context* c, int ntask, int M, int Mpad, const double* A, int64_t sa, const double* Wp,
+                               int64_t sw, double* out, int64_t ldo, int64_t so, bool tri);
+// alpha_out = alpha + W2 g and (vchol non-null) vmean_out = vmean + tril(vchol) g with g = the un-reversed m' (task
+// stride smrev); then info[t] = 1 + the first non-finite entry of g where info[t] was 0 and there is one
+hipError_t launch_svgp_cond_finish(Context* c, int ntask, int M, int Mpad, const double* W2, const double* alpha,
+                                   const double* mrev, int64_t smrev, double* alpha_out, const double* vmean,
+                                   int64_t stride_m, const double* vchol, int64_t ldc, int64_t stride_c,
+                                   double* vmean_out, int32_t* info);
 // The bound's hyperparameter gradient (gpx_svgpgrad.hip).  Between the passes, all tasks per launch (task stride ts
 // doubles for every array): T1 = I - S and Q = 2I - S - B - m m^T in natural order from W', B', m' (reversed order);
 // out = scale W T W^T for a symmetric T (tmp: the intermediate W T); m in natural order and sc2[2] = tr T1.

@@ -1,8 +1,10 @@
 // The one description of the SVGP calls' workspaces: gpx_svgp_prepare_f64, gpx_svgp_fit_collapsed_f64,
-// gpx_svgp_bound_grad_f64 and gpx_svgp_bound_grad_z_f64.  svgp_layout walks every region once with a bump cursor; the reported sizes, the chunk width
+// gpx_svgp_bound_grad_f64, gpx_svgp_bound_grad_z_f64 and gpx_svgp_condition_f64.  svgp_layout walks every region once with a bump cursor; the reported sizes, the chunk width
 // a given workspace allows (svgp_chunk_width) and the pointers the launches get (SvgpWorkspace) all come from it.  The
 // fit is the gradient's layout without the gradient's regions, and the inducing-location gradient's is the gradient's
-// plus two regions.  gpx_svgp_acquire_f64's workspace is described at the end (svgp_acquire_layout).  No HIP in here:
+// plus two regions.  The conditioning call's is the fit's without the zero vector and the second info words (the
+// task's alpha' and the caller's info take their places), plus the padded S of the preparation, which the compose step
+// reads as its left operand.  gpx_svgp_acquire_f64's workspace is described at the end (svgp_acquire_layout).  No HIP in here:
 // tests/host/svgp_layout_check.cpp
 // compiles this file alone with the host compiler and checks it against a second statement of the layout.
 #pragma once
@@ -29,7 +31,7 @@ enum SvgpRegion {
   SV_WB,     // fit: Mpad x Mpad, W = L_ZZ^{-T}, then W' = L'^{-T}; gradient: then the products' intermediate U
   SV_DINV,   // the diagonal-block inverses (dinv_bytes)
   SV_SLICE,  // the triangular inverse's scratch; prepare: or the alpha product's, whichever is larger
-  SV_SPAD,   // prepare: Mpad x Mpad, S = tril(chol), zero-padded
+  SV_SPAD,   // prepare, condition: Mpad x Mpad, S = tril(chol), zero-padded
   SV_MPAD,   // prepare: Mpad, m zero-padded
   SV_BVEC,   // fit: Mpad each: b', u, m' (reversed index order) ..
   SV_U,
@@ -60,7 +62,7 @@ enum SvgpRegion {
   SV_REGIONS,
   SV_SHARED = SV_ZERO  // the first shared region
 };
-enum SvgpKind { SVGP_PREPARE, SVGP_FIT, SVGP_GRAD, SVGP_GRAD_Z };
+enum SvgpKind { SVGP_PREPARE, SVGP_FIT, SVGP_GRAD, SVGP_GRAD_Z, SVGP_CONDITION };
 
 struct SvgpLayout {
   struct Region { size_t at = 0, bytes = 0; };  // bytes = 0: not in this call's workspace
@@ -80,6 +82,7 @@ inline SvgpLayout svgp_layout(SvgpKind kind, int64_t Mpad, int64_t ntask, int64_
                               int64_t zdim = 0) {
   SvgpLayout L;
   const bool prep = kind == SVGP_PREPARE, fit = !prep, gz = kind == SVGP_GRAD_Z, grad = kind == SVGP_GRAD || gz;
+  const bool cond = kind == SVGP_CONDITION;  // (the fit's regions but SV_ZERO and SV_INFO2, and SV_SPAD)
   const size_t mat = up256((size_t)Mpad * Mpad * 8), vec = up256((size_t)Mpad * 8);
   size_t at = 0;
   auto take = [&](SvgpRegion id, bool have, size_t bytes) {
@@ -94,7 +97,7 @@ inline SvgpLayout svgp_layout(SvgpKind kind, int64_t Mpad, int64_t ntask, int64_
   take(SV_WB, fit, mat);
   take(SV_DINV, true, up256(dinv_bytes(Mpad)));
   take(SV_SLICE, true, up256(prep && alpha_ws(Mpad, 1) > trtri_ws(Mpad) ? alpha_ws(Mpad, 1) : trtri_ws(Mpad)));
-  take(SV_SPAD, prep, mat);
+  take(SV_SPAD, prep || cond, mat);
   take(SV_MPAD, prep, vec);
   take(SV_BVEC, fit, vec);
   take(SV_U, fit, vec);
@@ -116,8 +119,8 @@ inline SvgpLayout svgp_layout(SvgpKind kind, int64_t Mpad, int64_t ntask, int64_
   L.ldk = (C + 255) / 256 * 256;
   L.phi_task = fit ? up256((size_t)Mpad * L.ldk * 8) : 0;
   const size_t nI = (size_t)(Mpad / 128), ncb = (size_t)(C / 128);
-  take(SV_ZERO, fit, vec);
-  take(SV_INFO2, fit, up256((size_t)ntask * 4));
+  take(SV_ZERO, fit && !cond, vec);
+  take(SV_INFO2, fit && !cond, up256((size_t)ntask * 4));
   take(SV_KC, fit, L.phi_task);
   take(SV_PHI, fit, L.phi_task * (size_t)ntask);
   take(SV_MU, fit, up256((size_t)(Mpad / NB) * L.ldk * 8));

@@ -31,6 +31,9 @@ using FitTile = MfmaTile<128, 128, 16, true, true>;  // (the accumulator layout 
 static_assert(FitTile::LDS_DOUBLES * 8 == trmm_asm::LDS_BYTES, "hand-placed tile uses MfmaTile's LDS image");
 
 // Phi'[Mpad - 1 - (128 I + m)][128 cb + c] = sum_{k < 128 (I + 1)} W[k][128 I + m] K[k][128 cb + c], 0 for columns >= mc
+// FULL (gpx_svgp_condition_f64: W is the full W2 = W C): the sum over every k < Mpad.  A compile-time variant, so each
+// kernel holds one k loop.
+template <bool FULL>
 __global__ void __launch_bounds__(WG) svgp_project_kernel(int Mpad, const double* __restrict__ W,
                                                           const double* __restrict__ kc, int64_t ldk, int ncb, int mc,
                                                           double* __restrict__ phi) {
@@ -38,9 +41,12 @@ __global__ void __launch_bounds__(WG) svgp_project_kernel(int Mpad, const double
   const int nI = Mpad / 128;
   const int I = nI - 1 - (int)blockIdx.x / ncb, cb = (int)blockIdx.x % ncb;  // deepest row tiles first
   // A(m, k) = W[k][128 I + m], B(k, c) = K[k][128 cb + c]; W's diagonal 128-block is the last 8 k-tiles (run_tri)
-  trmm_asm::TileT<true, true, false, 0> tile;
+  trmm_asm::TileT<true, true, false, FULL ? 2 : 0> tile;
   tile.zero();
-  tile.run_tri(W + (int64_t)I * 128, Mpad, kc + (int64_t)cb * 128, ldk, (I + 1) * 8, smem);
+  if constexpr (FULL)
+    tile.run(W + (int64_t)I * 128, Mpad, kc + (int64_t)cb * 128, ldk, nI * 8, smem);
+  else
+    tile.run_tri(W + (int64_t)I * 128, Mpad, kc + (int64_t)cb * 128, ldk, (I + 1) * 8, smem);
 #pragma unroll
   for (int i = 0; i < FitTile::WM; ++i)
 #pragma unroll
@@ -213,9 +219,19 @@ hipError_t launch_svgp_fit_project(Context* c, const gpx_kernel_params& p, int M
                                    double* phi, int64_t ldk, const double* X, int64_t ldx, const double* Y, int64_t ldy,
                                    int mc, double* r, double* bacc, double* scal) {
   const int nI = Mpad / 128, ncb = (mc + 127) / 128;
-  svgp_project_kernel<<<nI * ncb, WG, 0, c->stream>>>(Mpad, W, kc, ldk, ncb, mc, phi);
+  svgp_project_kernel<false><<<nI * ncb, WG, 0, c->stream>>>(Mpad, W, kc, ldk, ncb, mc, phi);
   svgp_resid_kernel<<<1, WG, 0, c->stream>>>(p, X, ldx, Y, ldy, mc, r, scal);
   svgp_rhs_kernel<<<(Mpad + 3) / 4, WG, 0, c->stream>>>(Mpad, phi, ldk, mc, r, bacc);
+  return hipGetLastError();
+}
+
+// The conditioning call's projection (gpx_svgpcond.hip): U' = the row-reversed W2^T K chunk, W2 full, and
+// b_acc += U' e with the chunk's residual e (already formed).
+hipError_t launch_svgp_cond_project(Context* c, int Mpad, const double* W2, const double* kc, double* phi, int64_t ldk,
+                                    int mc, const double* e, double* bacc) {
+  const int nI = Mpad / 128, ncb = (mc + 127) / 128;
+  svgp_project_kernel<true><<<nI * ncb, WG, 0, c->stream>>>(Mpad, W2, kc, ldk, ncb, mc, phi);
+  svgp_rhs_kernel<<<(Mpad + 3) / 4, WG, 0, c->stream>>>(Mpad, phi, ldk, mc, e, bacc);
   return hipGetLastError();
 }
 

@@ -92,8 +92,13 @@ __device__ __forceinline__ void wait_lgkm(Frag& f) {
 //       MfmaTile's 16-byte load split in halves, because an asm operand cannot name half of a register quad), 8
 //       ds_write_b64 into k-rows kk, kk + 1 at column m ^ kk; fragment reads from one base address per k-substep (the
 //       swizzle makes the lane's column depend on the substep through (4 S) & 12).
-template <bool KM>
+//   REV (row-major only): the operand's k runs DOWN the row, X(m, k) = G[m * ld - k] with G at the row's k = 0 element
+//       (at() takes the pointer to k-tile 0's lowest address, G - 15).  The same loads from descending tile bases; the
+//       pair a thread holds is written to the mirrored k-rows (element kk of the 16 to k-row 15 - kk), so the LDS image
+//       and the fragment reads are those of an operand stored in ascending k.
+template <bool KM, bool REV = false>
 struct Operand {
+  static_assert(!(KM && REV), "the reversed form is the row-major operand's");
   v2d rk[4];     // KM staging
   double rr[8];  // !KM staging: rr[2q], rr[2q + 1] = elements (t/8 + 32q, kk), (.., kk + 1)
   unsigned voff, soff_q;  // global byte offset of this thread's first element; the q-th load adds q * soff_q
@@ -115,7 +120,8 @@ struct Operand {
       const int kk = 2 * (t & 7);
       voff = (unsigned)(((int64_t)(t >> 3) * ld + kk) * 8);
       soff_q = (unsigned)(32 * ld * 8);
-      wbase = lds0 + region + (unsigned)((kk * 144 + ((t >> 3) ^ kk)) * 8);
+      const int kw = REV ? 14 - kk : kk;  // the even k-row of the pair's two LDS rows
+      wbase = lds0 + region + (unsigned)((kw * 144 + ((t >> 3) ^ kw)) * 8);
 #pragma unroll
       for (int s = 0; s < 4; ++s)
         rbase[s] = lds0 + region + (unsigned)((kr * 144 + w0 + (m ^ (kr & 2) ^ ((4 * s) & 12))) * 8);
@@ -141,15 +147,18 @@ struct Operand {
         default: dsw<BB * BUF + 3 * 4 * PITCH>(wbase, rk[3]); break;
       }
     } else {
-      switch (q) {  // element (row t/8 + 32 (q/2), k = kk + (q & 1)): LDS k-row kk + (q & 1), column (t/8 ^ kk) + 32 (q/2)
-        case 0: dsw8<BB * BUF + 0 * 256>(wbase, rr[0]); break;
-        case 1: dsw8<BB * BUF + PITCH + 0 * 256>(wbase, rr[1]); break;
-        case 2: dsw8<BB * BUF + 1 * 256>(wbase, rr[2]); break;
-        case 3: dsw8<BB * BUF + PITCH + 1 * 256>(wbase, rr[3]); break;
-        case 4: dsw8<BB * BUF + 2 * 256>(wbase, rr[4]); break;
-        case 5: dsw8<BB * BUF + PITCH + 2 * 256>(wbase, rr[5]); break;
-        case 6: dsw8<BB * BUF + 3 * 256>(wbase, rr[6]); break;
-        default: dsw8<BB * BUF + PITCH + 3 * 256>(wbase, rr[7]); break;
+      // element (row t/8 + 32 (q/2), k = kk + (q & 1)): LDS k-row kk + (q & 1), column (t/8 ^ kk) + 32 (q/2); REV:
+      // k-row 15 - kk - (q & 1), the pair's rows swapped (P0 / P1: the byte offset of the even / odd element's row)
+      constexpr int P0 = REV ? PITCH : 0, P1 = REV ? 0 : PITCH;
+      switch (q) {
+        case 0: dsw8<BB * BUF + P0 + 0 * 256>(wbase, rr[0]); break;
+        case 1: dsw8<BB * BUF + P1 + 0 * 256>(wbase, rr[1]); break;
+        case 2: dsw8<BB * BUF + P0 + 1 * 256>(wbase, rr[2]); break;
+        case 3: dsw8<BB * BUF + P1 + 1 * 256>(wbase, rr[3]); break;
+        case 4: dsw8<BB * BUF + P0 + 2 * 256>(wbase, rr[4]); break;
+        case 5: dsw8<BB * BUF + P1 + 2 * 256>(wbase, rr[5]); break;
+        case 6: dsw8<BB * BUF + P0 + 3 * 256>(wbase, rr[6]); break;
+        default: dsw8<BB * BUF + P1 + 3 * 256>(wbase, rr[7]); break;
       }
     }
   }
@@ -166,13 +175,13 @@ struct Operand {
   }
   // descriptor based at k-tile kt
   __device__ __forceinline__ rsrc_t at(const double* G, int64_t ld, int kt) const {
-    return rsrc_of(KM ? G + (int64_t)kt * 16 * ld : G + (int64_t)kt * 16);
+    return rsrc_of(KM ? G + (int64_t)kt * 16 * ld : (REV ? G - (int64_t)kt * 16 : G + (int64_t)kt * 16));
   }
 };
 
 // s_waitcnt vmcnt(N) completing the staged k-tile (N: younger loads that may stay in flight, e.g. accumulator seeds)
-template <int N, bool AKM, bool BKM>
-__device__ __forceinline__ void wait_vm(Operand<AKM>& A, Operand<BKM>& B) {
+template <int N, bool AKM, bool BKM, bool AREV>
+__device__ __forceinline__ void wait_vm(Operand<AKM, AREV>& A, Operand<BKM>& B) {
   if constexpr (AKM && BKM)
     asm volatile("s_waitcnt vmcnt(%8)"
                  : "+v"(A.rk[0]), "+v"(A.rk[1]), "+v"(A.rk[2]), "+v"(A.rk[3]), "+v"(B.rk[0]), "+v"(B.rk[1]),
@@ -195,8 +204,8 @@ __device__ __forceinline__ void wait_vm(Operand<AKM>& A, Operand<BKM>& B) {
                    "+v"(B.rr[4]), "+v"(B.rr[5]), "+v"(B.rr[6]), "+v"(B.rr[7])
                  : "i"(N));
 }
-template <bool AKM, bool BKM>
-__device__ __forceinline__ void wait_vm0(Operand<AKM>& A, Operand<BKM>& B) {
+template <bool AKM, bool BKM, bool AREV>
+__device__ __forceinline__ void wait_vm0(Operand<AKM, AREV>& A, Operand<BKM>& B) {
   wait_vm<0>(A, B);
 }
 
@@ -205,11 +214,12 @@ __device__ __forceinline__ void wait_vm0(Operand<AKM>& A, Operand<BKM>& B) {
 // TAG: kernels of one translation unit that each want the k loop inlined instantiate the tile with different tags (the
 // loop's member functions are not forced inline: with one caller each they are inlined, with two they become calls and
 // the tile's registers go to scratch).
-template <bool AKM, bool BKM, bool NEG = false, int TAG = 0>
+// AREV: the row-major A runs down its rows, A(m, k) = Ag[m lda + 15 - k] (Operand's REV; Ag: k-tile 0's lowest address).
+template <bool AKM, bool BKM, bool NEG = false, int TAG = 0, bool AREV = false>
 struct TileT {
   d4 acc[4][4];  // acc[i][j][r]: row (w >> 1) * 64 + 16 i + (lane >> 4) + 4 r, column (w & 1) * 64 + 16 j + (lane & 15)
   Frag f0, f1;
-  Operand<AKM> A;
+  Operand<AKM, AREV> A;
   Operand<BKM> B;
   static constexpr int NL = Operand<AKM>::NLOAD + Operand<BKM>::NLOAD;    // global loads per k-tile (8 / 12 / 16)
   static constexpr int NW = Operand<AKM>::NWRITE + Operand<BKM>::NWRITE;  // LDS writes per k-tile

@@ -1214,6 +1214,55 @@ class GPEngine:
                 raise err
         return vmean, vchol, bound
 
+    def svgp_condition(self, prep: dict, X, Y, vmean=None, vchol=None, chunk: Optional[int] = 0):
+        """Condition a prepared SVGP on new observations (gpx_svgp_condition_f64): the exact Bayesian update of every
+        task's q(u) by (X, Y), X: k x d input-transformed, Y: k x T.  For a state from ``svgp_fit_collapsed`` the result
+        is the collapsed fit of the old and the new points together; K_ZZ is not factorised again and the old points
+        are not visited.  Returns (prep_new, vmean_new, vchol_new): ``prep_new`` shares ``Z``, ``W``, ``params`` and
+        ``M`` with ``prep`` and has new ``W2`` and ``alpha``; the variational pair is updated where ``vmean`` (T x M)
+        and ``vchol`` (T x M x M, lower triangle used) are given, else both are None.  ``prep`` stays valid.  Raises
+        NotPositiveDefiniteError naming a task whose update failed (non-finite input)."""
+        Z = prep["Z"]
+        T, M, d = Z.shape
+        X = self._rows_f64(X, "X")
+        Y = torch.as_tensor(Y)
+        Y = self._rows_f64(Y.unsqueeze(-1) if Y.dim() == 1 else Y, "Y")
+        k = X.shape[0]
+        if X.shape[1] != d or Y.shape != (k, T):
+            raise ValueError(f"X must be k x {d} and Y k x {T}")
+        if (vmean is None) != (vchol is None):
+            raise ValueError("vmean and vchol must be given together")
+        pcs = (KernelParamsC * T)(*[pp.to_c(d) for pp in prep["params"]])
+        Mpad = self.padded_n(M)
+        W2 = torch.empty((T, Mpad, Mpad), dtype=torch.float64, device=self.device)
+        alpha = torch.empty((T, Mpad), dtype=torch.float64, device=self.device)
+        info = torch.zeros((T,), dtype=torch.int32, device=self.device)
+        vm_new = vc_new = None
+        sm = ldc = sc = 0
+        if vmean is not None:
+            vmean = torch.as_tensor(vmean).to(device=self.device, dtype=torch.float64).contiguous()
+            vchol = torch.as_tensor(vchol).to(device=self.device, dtype=torch.float64).contiguous()
+            if vmean.shape != (T, M) or vchol.shape != (T, M, M):
+                raise ValueError("vmean must be T x M and vchol T x M x M")
+            vm_new, vc_new = torch.empty_like(vmean), torch.empty_like(vchol)
+            sm, ldc, sc = M, M, M * M
+        nbytes = ctypes.c_size_t()
+        self._check(self.lib.gpx_svgp_condition_workspace_size(M, k, T, int(chunk or 0), ctypes.byref(nbytes)))
+        ws = self.workspace("svgp_cond", nbytes.value)
+        self._bind_stream()
+        # (the library derives the chunk width from the size it is told, not from the cached buffer's)
+        self._check(self.lib.gpx_svgp_condition_f64(
+            self.handle, pcs, T, M, _ptr(Z), Z.stride(1), Z.stride(0), _ptr(prep["W"]), _ptr(prep["W2"]),
+            _ptr(prep["alpha"]), _ptr(X), k, X.stride(0), _ptr(Y), Y.stride(0), _ptr(W2), _ptr(alpha), _ptr(vmean), sm,
+            _ptr(vchol), ldc, sc, _ptr(vm_new), _ptr(vc_new), _ptr(info), _ptr(ws), nbytes.value))
+        bad = info.cpu().numpy()
+        for t in range(T):
+            err = info_error(int(bad[t]), f"task {t}: the conditioning update")
+            if err is not None:
+                raise err
+        prep_new = {"Z": Z, "W": prep["W"], "W2": W2, "alpha": alpha, "params": prep["params"], "M": prep["M"]}
+        return prep_new, vm_new, vc_new
+
     def svgp_bound_value_grad(self, params: Sequence[KernelParams], Z, X, Y, jitter: float = 1e-4,
                               chunk: Optional[int] = None, inducing_grad: bool = False):
         """The collapsed bound F of ``svgp_fit_collapsed`` and the gradient of -F with respect to the natural

@@ -356,6 +356,23 @@ class SparseGP:
         mean, var = self.predictor.predict(X, transformed=True)
         return Posterior(mean=mean, variance=var)
 
+    def condition_on_observations(self, X, Y) -> "SparseGP":
+        """A new SparseGP that knows the observations (X: k x d input-transformed, Y: k x T) too: the exact update of
+        the variational posterior on the device (``SVGPPredictor.condition_on_observations``,
+        gpx_svgp_condition_f64), which for this model's collapsed q(u) is the collapsed fit of all points, without a
+        fit.  Hyperparameters and inducing points are kept; this model is left as it is."""
+        X = torch.as_tensor(X).to(device=self.train_X.device, dtype=self.train_X.dtype)
+        Y = torch.as_tensor(Y).to(device=self.train_Y.device, dtype=self.train_Y.dtype)
+        if Y.dim() == 1:
+            Y = Y.unsqueeze(-1)
+        new = SparseGP.__new__(SparseGP)
+        new.engine = self.engine
+        new.train_X, new.train_Y = torch.cat([self.train_X, X]), torch.cat([self.train_Y, Y])
+        new.predictor = self.predictor.condition_on_observations(X, Y, transformed=True)
+        new.svgp = new.predictor.model
+        new.params = new.svgp.params
+        return new
+
     @property
     def states(self):
         """One SVGPTaskState per output: what acqf's moment-based acquisitions (qLogExpectedImprovement,

@@ -19,7 +19,8 @@ hyperparameters are tied), in which case new observations are folded in by the b
 distribution in closed form for the fitted hyperparameters (``SVGPModel.fit_collapsed``, ``models.SparseGP``), serving
 ``predict``, ``evaluate_model``, the pool scan and, through its q-batch moments (``gpx_svgp_moments_grad_f64``),
 ``"qpsd"`` (Bayesian6's large-n mode, ``Bayesian6.py:492-577,896-919``) and ``"qlogei"`` up to ``GPX_MAX_Q`` points per
-round, and with ``GPConfig.sparse_analytic`` the analytic sweeps ``"ei" | "logei" | "ucb"`` on its latent posterior
+round (more with ``GPConfig.sparse_condition``: the sparse model is conditioned on each chunk,
+``gpx_svgp_condition_f64``), and with ``GPConfig.sparse_analytic`` the analytic sweeps ``"ei" | "logei" | "ucb"`` on its latent posterior
 (``gpx_svgp_acquire_f64``); the other modes raise on it.  Acquisition modes (``acquisition=``):
 
 * ``"variance"`` (default, Bayesian7's pool scan ``:646-688``): Latin-hypercube pool -> summed posterior variance on
@@ -128,6 +129,10 @@ class GPConfig:
     # Sobol grid of the exact modes through SparseGP.sweep_objective_topk, gpx_svgp_acquire_f64).  Off by default: the
     # constructor and acquire() then refuse them, as they did before the sweep existed.
     sparse_analytic: bool = False
+    # True: acquisition="qlogei" on the sparse surrogate serves more than GPX_MAX_Q points per round: after each chunk
+    # the sparse model is conditioned on the chunk's posterior means (kriging believer, as on the exact model) through
+    # SparseGP.condition_on_observations (gpx_svgp_condition_f64).  Off by default: such a round is refused.
+    sparse_condition: bool = False
     max_inducing_points: int = 2048
     inducing_subset_size: int = 10000
     # acquisition="qlogei": optimize_acqf settings of optimization/Bayesian.py:100-112
@@ -629,12 +634,13 @@ class BayesianOptimizer:
         """optimize_acqf on MC qLogEI (Bayesian.py:96-113: 512 Sobol base samples, 10 restarts, 1024 raw samples,
         batch_limit 5, maxiter 200) in the unit cube through the log-input transform.  Chunks of at most GPX_MAX_Q
         points; after each, the model is conditioned on the chunk with its posterior mean (kriging believer).  The
-        sparse surrogate has no such conditioning: it serves k <= GPX_MAX_Q, one joint q-batch."""
+        sparse surrogate is conditioned that way only with GPConfig.sparse_condition
+        (SparseGP.condition_on_observations); without it, it serves k <= GPX_MAX_Q, one joint q-batch."""
         from .acqf import LinearMCObjective, SobolQMCNormalSampler, optimize_acqf, qLogExpectedImprovement
 
         cfg = self.config
         model = self.gp_model
-        if isinstance(model, SparseGP) and k > _capi.GPX_MAX_Q:
+        if isinstance(model, SparseGP) and k > _capi.GPX_MAX_Q and not cfg.sparse_condition:
             raise ValueError(f"acquisition 'qlogei' on the sparse surrogate serves at most {_capi.GPX_MAX_Q} points per "
                              f"round (asked for {k}): the sparse model cannot be conditioned on a chunk")
         w = self._acq_weights()
@@ -659,6 +665,9 @@ class BayesianOptimizer:
             if remaining > 0:  # condition on the chunk: fantasy observations = current posterior means
                 Xf = x_tf(cand.to(self.gp_device))
                 fantasy = model.posterior(Xf).mean
+                if isinstance(model, SparseGP):
+                    model = model.condition_on_observations(Xf, fantasy)
+                    continue
                 model = ExactGP(torch.cat([model.train_X, Xf]), torch.cat([model.train_Y, fantasy]), model.params,
                                 engine=self.engine, jitter_schedule=model.jitter_schedule).fit()
         return torch.cat(picked)

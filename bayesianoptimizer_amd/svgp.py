@@ -140,11 +140,27 @@ class SVGPPredictor:
     (``optimization/Bayesian7.py:558,668``); ``pool_scan`` ≙ the acquisition block ``:646-688``."""
 
     def __init__(self, model: SVGPModel, engine: Optional[GPEngine] = None,
-                 input_transform: Optional[LogInputStandardizer] = None):
+                 input_transform: Optional[LogInputStandardizer] = None, prep: Optional[dict] = None):
+        """``prep``: the prepared state of ``model`` where the caller already has it (``condition_on_observations``);
+        by default it is built here (``GPEngine.svgp_prepare``)."""
         self.engine = engine or GPEngine()
         self.model = model
         self.input_transform = input_transform
-        self.prep = self.engine.svgp_prepare(model.params, model.Z, model.vmean, model.vchol, jitter=model.jitter)
+        if prep is None:
+            prep = self.engine.svgp_prepare(model.params, model.Z, model.vmean, model.vchol, jitter=model.jitter)
+        self.prep = prep
+
+    def condition_on_observations(self, X: torch.Tensor, Y: torch.Tensor, transformed: bool = False) -> "SVGPPredictor":
+        """A new predictor whose model knows the observations (X, Y) too (X: k x d, unit cube unless ``transformed``;
+        Y: k x T): the exact update of q(u) on the device (``GPEngine.svgp_condition``), without a factorisation of
+        K_ZZ, a pass over the old points or an ``svgp_prepare``.  Hyperparameters, Z and the jitter are kept; the new
+        model's ``bound`` is None (the bound of the enlarged data cannot be updated from q alone).  This predictor and
+        its model are left as they are."""
+        m = self.model
+        prep, vmean, vchol = self.engine.svgp_condition(self.prep, self._std(X, transformed), Y, vmean=m.vmean,
+                                                        vchol=m.vchol)
+        model = SVGPModel(Z=m.Z, vmean=vmean, vchol=vchol, params=m.params, jitter=m.jitter, bound=None)
+        return SVGPPredictor(model, engine=self.engine, input_transform=self.input_transform, prep=prep)
 
     def _std(self, X: torch.Tensor, transformed: bool) -> torch.Tensor:
         X = X.to(device=self.engine.device, dtype=torch.float64)

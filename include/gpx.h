@@ -743,6 +743,45 @@ gpx_status gpx_svgp_bound_grad_z_f64(gpx_handle h, const gpx_kernel_params* p, i
                                      int64_t ldx, const double* Y, int64_t ldy, double* out, double* dZ, int64_t lddz,
                                      int64_t stride_dz, int32_t* info, void* ws, size_t ws_bytes);
 
+/* ---- Conditioning the sparse model on new data -------------------------------------------------------------------- */
+/* The exact Bayesian update of every task's whitened q(u) = N(m, C C^T) by new Gaussian observations (Xn, Yn):
+ *   q'(u) proportional to q(u) prod_i N(y_i | const_mean + phi_i^T u, s2),  phi_i = L_ZZ^{-1} k(Z, x_i),  s2 = noise.
+ * In the basis of the current posterior, u = m + C u~, with U = C^T Phi_n = W2^T K(Z, Xn) and the residual against the
+ * current predictive mean e = y_n - (const_mean + K(Z, Xn)^T alpha'):
+ *   P = I + U U^T / s2,  D lower triangular with positive diagonal and D D^T = P^{-1},  g = D D^T U e / s2,
+ *   m_new = m + C g,  C_new = C D,  W2_new = W2 D,  alpha'_new = alpha' + W2 g.
+ * For a state from gpx_svgp_fit_collapsed_f64 with the same p, Z and jitter, (m_new, C_new) is the collapsed fit of the
+ * old and the new points together (Cholesky factors are unique).  For any other state it is the same update of that q:
+ * S S^T <= I is not assumed, so a loaded checkpoint can be conditioned.  The bound of the enlarged data set is not
+ * returned: it cannot be updated from (m, C) alone.  K_ZZ is not factorised again and the old points are not visited.
+ * Z, W, W2, alpha: the prepared state, as gpx_svgp_predict_f64 takes it.  Xn: n_new x d, already input-transformed; Yn:
+ * n_new x ntask, read by column; 1 <= n_new <= 2^30.
+ * W2_out (ntask x Mpad x Mpad), alpha_out (ntask x Mpad): in the layout of the prepared blocks, rows / columns / entries
+ * >= M exactly 0: with the unchanged Z and W they are a prepared state for gpx_svgp_predict_f64, gpx_svgp_acquire_f64,
+ * gpx_svgp_moments_grad_f64 and this call again.
+ * vmean, vchol (optional): the variational pair in the layout gpx_svgp_prepare_f64 reads (the lower triangle of vchol
+ * only); vmean_out, vchol_out: the updated pair with the inputs' strides, vchol_out's strict upper triangle written as
+ * exactly 0, its diagonal positive.  The four are given together or all NULL (any other mix: GPX_INVALID_ARG).
+ * No output may be the input it is computed from (W2_out == W2, alpha_out == alpha, vmean_out == vmean, vchol_out ==
+ * vchol: GPX_INVALID_ARG), and outputs must not overlap inputs: the old state stays valid.
+ * info: int32[ntask], 0, or the failing pivot + 1 of P's factorisation, or, where that went through (P does not depend
+ * on Yn) but the update g is not finite, 1 + the index of its first non-finite entry; either needs non-finite input,
+ * since P >= I.  A failed task's outputs are unspecified; the other tasks are computed.
+ * Asynchronous on the handle's stream, no allocation, no host synchronisation; fixed-order reductions and no
+ * floating-point atomics: equal inputs and an equal chunk width give equal bits.
+ * Workspace: gpx_svgp_condition_workspace_size(M, n_new, ntask, chunk); the chunk rule is gpx_svgp_fit_collapsed_f64's
+ * (Xn is streamed in chunks of columns; `chunk` rounded up to a multiple of 128, 0 = GPX_SVGP_FIT_CHUNK; the call derives
+ * its width from ws_bytes; below the chunk = 128 size: GPX_INVALID_ARG), and the size does not grow with n_new beyond
+ * one chunk: about ntask 3 Mpad^2 8 + (1 + ntask) Mpad ldk 8 bytes. */
+gpx_status gpx_svgp_condition_workspace_size(int64_t M, int64_t n_new, int64_t ntask, int64_t chunk, size_t* bytes);
+gpx_status gpx_svgp_condition_f64(gpx_handle h, const gpx_kernel_params* p, int64_t ntask, int64_t M, const double* Z,
+                                  int64_t ldz, int64_t stride_z, const double* W, const double* W2, const double* alpha,
+                                  const double* Xn, int64_t n_new, int64_t ldx, const double* Yn, int64_t ldy,
+                                  double* W2_out, double* alpha_out, const double* vmean /* or NULL */,
+                                  int64_t stride_m, const double* vchol /* or NULL */, int64_t ldc, int64_t stride_c,
+                                  double* vmean_out /* or NULL */, double* vchol_out /* or NULL */, int32_t* info,
+                                  void* ws, size_t ws_bytes);
+
 /* The k largest scores in descending order (replaces torch.topk, Bayesian7.py:681): stable, so equal scores keep
  * the lower index first; NaN ranks last.  idx_out: int64[k], val_out: double[k] (NULL = skip). */
 gpx_status gpx_topk_workspace_size(int64_t m, size_t* bytes);
